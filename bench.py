@@ -10,10 +10,14 @@ is partitioned N ways (strong scaling) and halos travel as RCCL send/recv over x
   python bench.py --gpus 1 --steps 20 --warmup 3
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-A "step" is one full RHS evaluation over the whole mesh (all N ranks).  The JSON line also
-carries `sypd` (RK4 steps, halo exchanges included), `roofline` (dominant kernel, live HIP
-events on the launch stream) and, at N = 1, `cpu_baseline` (the CPU oracle timed on a
-the same full mesh -- a bounded number of evaluations -- on the host cores).
+A "step" is one full RHS evaluation over the whole mesh (all N ranks).  A plain run does only
+what the headline figure needs: set-up, warm-up, the K timed steps, the outputs of the last one
+(--dump-outputs DIR) and the JSON line.  With --full the line also carries `sypd` (RK4 steps,
+halo exchanges included), `roofline` (dominant kernel, live HIP events on the launch stream
+and, at N = 1, HBM traffic from two rocprofv3 --pmc child runs), at N = 1 `realistic` (the
+same measurement on a culled sphere) and `cpu_baseline` (the CPU oracle timed on the same
+full mesh -- a bounded number of evaluations -- on the host cores), and at N > 1 the halo
+wire's check, the overlapped-vs-sequential cross-check and `rhs_with_halo_exchange`.
 """
 import argparse
 import json
@@ -172,7 +176,14 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=os.environ.get("OMEGA_BENCH_WORKLOAD", "qu30"), choices=sorted(WORKLOADS))
-    ap.add_argument("--rk4-steps", type=int, default=-1, help="RK4 steps for SYPD (default: max(2, steps//4))")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure as well: RK4 steps (sypd), the per-kernel "
+                         "roofline with live HBM traffic, the realistic mesh and the CPU baseline at N = 1, the halo wire and "
+                         "its cross-checks at N > 1.  Off: set-up, warm-up, the timed steps and the record only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last one computed (the three tendency arrays, float64, "
+                         "a fixed seeded sample of global cells / edges, all levels) as DIR/<name>.npy")
+    ap.add_argument("--rk4-steps", type=int, default=-1, help="--full: RK4 steps for SYPD (default: max(2, steps//4))")
     ap.add_argument("--dt", type=float, default=0.0,
                     help="time step [s]; 0 = Default.yml's 10 minutes at 30 km cells, scaled with the workload's cell size")
     ap.add_argument("--block", type=int, default=1,
@@ -188,13 +199,13 @@ def parse_args(argv=None):
                          "run of 8 / 16 / 32 local cells a compact patch on the surface (default; against the Morton curve: "
                          "RHS -1..-3 %% planar, -2.8 %% on the icosahedral sphere), curve / hilbert = along a Morton / Hilbert "
                          "curve through the cell centres, global = the reference's global-id order")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the CPU baseline")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="N = 1: skip the two rocprofv3 --pmc child runs (FETCH_SIZE; WRITE_SIZE) that measure roofline.traffic "
+                    help="--full, N = 1: skip the two rocprofv3 --pmc child runs (FETCH_SIZE; WRITE_SIZE) that measure roofline.traffic "
                          "in this very run; traffic then comes from a committed profiles/*_pmc.json measured on the same kernel "
                          "sources, or is null")
     ap.add_argument("--realistic", default="auto",
-                    help="N = 1: after the headline measurement, the same W + K evaluations on a realistically shaped mesh "
+                    help="--full, N = 1: after the headline measurement, the same W + K evaluations on a realistically shaped mesh "
                          "(record key `realistic`).  auto (default) = fib7_coast when the headline workload is qu30, none "
                          "otherwise; `none`; or a workload name")
     ap.add_argument("--unfused", action="store_true", help="time the reference-structured launch sequence instead")
@@ -305,6 +316,8 @@ def launch_ranks(args, argv):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs writes the outputs of one rank's whole mesh: run it with --gpus 1")
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if world == 0 and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -315,7 +328,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but the launcher started WORLD_SIZE = {world} ranks")
     N = world
     live = live_note = None
-    if N == 1 and not args.no_live_traffic:
+    if args.full and N == 1 and not args.no_live_traffic:
         live, live_note = live_traffic(args)      # (child processes; this one has not loaded the HIP runtime yet)
         if live is None:
             print(f"[bench] no live HBM-traffic measurement: {live_note}", file=sys.stderr, flush=True)
@@ -352,7 +365,7 @@ def main():
             local_rank = 0
         os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")   # one node: the side channel stays on the loopback device
         dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=300))
-    if N == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and N == 1 and rank == 0 and not args.no_cpu_baseline:
         from oracle import oracle as O   # the checker's -O3 -march=native build: compiled (a child `make`) before this
         O.use_native_build()             # process touches the GPU
     oa.device_init(local_rank)
@@ -458,14 +471,18 @@ def main():
     barrier()
     dev_ms = ev0.elapsed_ms(ev1)
     graph_stats = tend.graph_stats()
-    # per-kernel durations for the roofline: HIP events between the launches, in a second pass of the same K steps
-    # directly after the timed region (which therefore carries no event records between its kernels)
-    tend.kernel_timing(True)
-    for _ in range(args.steps):
-        tend.compute_all_tendencies(state, aux, tracers, stream=stream)
-    oa.device_synchronize()
-    tend.kernel_timing(False)
-    ktimes = tend.collect_kernel_times()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, g, decomp, mesh, tend)
+    ktimes = []
+    if args.full:
+        # per-kernel durations for the roofline: HIP events between the launches, in a second pass of the same K steps
+        # directly after the timed region (which therefore carries no event records between its kernels)
+        tend.kernel_timing(True)
+        for _ in range(args.steps):
+            tend.compute_all_tendencies(state, aux, tracers, stream=stream)
+        oa.device_synchronize()
+        tend.kernel_timing(False)
+        ktimes = tend.collect_kernel_times()
     wall_rhs = allmax(wall_rhs)
     ms_per_step = 1e3 * wall_rhs / args.steps
 
@@ -538,7 +555,7 @@ def main():
     wire_errors = None
     wire_check = None
     state_checksums = None
-    nrk = args.rk4_steps if args.rk4_steps >= 0 else max(2, args.steps // 4)
+    nrk = (args.rk4_steps if args.rk4_steps >= 0 else max(2, args.steps // 4)) if args.full else 0
     overlap = N > 1 and not (args.no_overlap or args.no_fuse_stages or args.unfused)
     emitted = []
 
@@ -573,7 +590,7 @@ def main():
                           "terms": "Default.yml (del2+del4, center fluxes)", "fused_rhs": not args.unfused,
                           "launcher": launcher,
                           "partition": f"{args.partition}{N}" + (f" (edge cut {edge_cut})" if N > 1 else ""), "halo_width": halo_width,
-                          "halo_wire": "none (1 rank)" if N == 1 else
+                          "halo_wire": "none (1 rank)" if N == 1 else "not set up (the stepping part runs with --full)" if not args.full else
                           ("RCCL send/recv inside libomega_amd (" + json.dumps(comm.info()) + ")" if comm else
                            ((wire_note + (" " + json.dumps(wire.info()) if wire else "")) if wire_note else
                             "none: " + "; ".join(wire_errors or ["?"])[:300])),
@@ -585,7 +602,7 @@ def main():
                           "device_ms_per_step": dev_ms / args.steps, "setup_s": round(setup_s, 1),
                           "untimed_settle": {"ms": args.settle_ms, "rhs_evaluations": settle_evals,
                                              "why": "load step -> ~25 ms power-management transient (profiles/r03_probe_step_ramp.json)"},
-                          "hip_graph": graph_stats},
+                          "hip_graph": graph_stats, "full": args.full},
                "sypd": sypd, "rk4": {"steps": nrk, "dt_s": args.dt, "ms_per_step": None if t_rk4 is None else 1e3 * t_rk4,
                        "cell_level_updates_per_sec": None if t_rk4 is None else 4.0 * cell_levels / t_rk4,
                        "stage_updates": "separate kernels" if (args.no_fuse_stages or args.unfused) else "fused into the RHS kernels",
@@ -604,7 +621,7 @@ def main():
     # N > 1: if the stepping part (wire set-up, RK4, cross-check) hangs -- a peer died, a collective never returns -- the
     # RHS measurement above must not be lost with it: rank 0 prints the record with rk4.error set and leaves.
     watchdog = None
-    if N > 1 and rank == 0 and args.rk4_timeout > 0:
+    if args.full and N > 1 and rank == 0 and args.rk4_timeout > 0:
         import threading
 
         def give_up():
@@ -665,7 +682,7 @@ def main():
             wire = None
         return errs
 
-    if N > 1:
+    if args.full and N > 1:
         if args.backend in ("rccl", "auto"):
             wire_errors = setup_rccl()
             if not wire_errors:
@@ -715,7 +732,6 @@ def main():
             print("[bench] no halo wire: " + "; ".join(wire_errors), file=sys.stderr, flush=True)
 
     # ------------------------------------------------ RK4 steps (SYPD)
-    nrk = args.rk4_steps if args.rk4_steps >= 0 else max(2, args.steps // 4)
     sypd = t_rk4 = rk4_error = None
     if wire_errors:     # strict: no wire, no stepping part; the RHS record stands and the run exits non-zero
         rk4_error = "no halo wire could be initialised: " + "; ".join(wire_errors)[:600]
@@ -853,10 +869,10 @@ def main():
 
     # ------------------------------------------------ CPU baseline (rank 0, N = 1 only): the oracle
     cpu = None
-    if N == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and N == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(nx, ny, K, NT, dc, args.dt) if (nx > 0 and not args.workload.endswith("_coast")) else None
 
-    if N == 1 and rank == 0:
+    if args.full and N == 1 and rank == 0:
         wl = ("fib7_coast" if args.workload == "qu30" else "none") if args.realistic == "auto" else args.realistic
         if wl != "none":
             # (the headline problem's arrays are released first: configs[3] holds 5 GB, the block needs 2)
@@ -948,6 +964,34 @@ def live_traffic(args):
     return out, (f"measured in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two child runs of `bench.py --workload "
                  f"{args.workload} --steps 3 --warmup 1` before the timed process touched the GPU ({time.time() - t0:.0f} s, >= {n} launches "
                  "per kernel); FETCH_SIZE x 2 (gfx950 half-count of 16-B-per-lane reads) + WRITE_SIZE")
+
+
+DUMP_BYTES = 48 << 20    # --dump-outputs: all files together stay below this (the sample shrinks with levels and tracers)
+DUMP_ROWS = 4096
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, g, decomp, mesh, tend):
+    """--dump-outputs DIR (N = 1): what computeAllTendencies handed its caller in the last timed step -- LayerThicknessTend
+    [cells, K], NormalVelocityTend [edges, K], TracerTend [NT, cells, K], float64 -- on a fixed, seeded sample of the global
+    cells and edges, rows in global-id order (so the files do not depend on the local numbering the library chose)."""
+    K, NT = tend.K, tend.NT
+    n = min(DUMP_ROWS, DUMP_BYTES // (8 * K * (2 + NT)))
+    rng = np.random.default_rng(DUMP_SEED)
+    picks = []
+    for id_name, n_owned, n_global in (("CellID", mesh.NCellsOwned, int(g["nCells"])),
+                                       ("EdgeID", mesh.NEdgesOwned, int(g["nEdges"]))):
+        where = np.full(n_global, -1, dtype=np.int64)      # global id (0-based) -> local row
+        where[np.asarray(decomp.get_array(id_name)[:n_owned]) - 1] = np.arange(n_owned)
+        rows = where[np.sort(rng.choice(n_global, min(n, n_global), replace=False))]
+        if (rows < 0).any():
+            raise RuntimeError(f"--dump-outputs: a sampled {id_name} is not owned by this rank")
+        picks.append(rows)
+    cells, edges = picks
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "layer_thickness_tend.npy"), tend.get(0)[cells])
+    np.save(os.path.join(out_dir, "normal_velocity_tend.npy"), tend.get(1)[edges])
+    np.save(os.path.join(out_dir, "tracer_tend.npy"), tend.get(2)[:, cells])
 
 
 def staged_bytes_exact(nc, ne, nv, nt, k):

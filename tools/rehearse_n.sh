@@ -10,7 +10,7 @@ for o in "$@"; do
    port=$((port + 1))
    name=$((port - 29550))_$(echo "${o:-default}" | tr ',=' '__')
    OMEGA_AMD_OPTIONS="$o" timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-      --master-port $port bench.py --gpus $N --steps 5 --warmup 2 --single-device --workload $W \
+      --master-port $port bench.py --full --gpus $N --steps 5 --warmup 2 --single-device --workload $W \
       > gpurun_out/${TAG}_${name}.json 2> gpurun_out/${TAG}_${name}.err
    python3 - <<PY
 import json

@@ -75,7 +75,7 @@ def main():
     out = os.path.join(ROOT, "gpurun_out")
     fetch, write = counters(os.path.join(out, tag + "_pmc_fetch")), counters(os.path.join(out, tag + "_pmc_write"))
     res = {"_note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum (separate runs) of "
-                    "`python3 bench.py --steps 8 --warmup 2 --rk4-steps 2 --no-cpu-baseline " + " ".join(sys.argv[2:]) +
+                    "`python3 bench.py --full --steps 8 --warmup 2 --rk4-steps 2 --no-cpu-baseline " + " ".join(sys.argv[2:]) +
                     "`; FETCH_SIZE (KB) x 1024 x 2 (gfx950 half-count of 16-B-per-lane reads) + WRITE_SIZE (KB) x 1024",
            "kernel_source_sha": kernel_source_sha(), "bench_args": sys.argv[2:]}
     total = 0.0
