@@ -35,6 +35,8 @@ typedef struct omg_tracers omg_tracers; /* O/src/ocn/Tracers.h   class Tracers  
 typedef struct omg_aux omg_aux;         /* O/src/ocn/AuxiliaryState.h                */
 typedef struct omg_tend omg_tend;       /* O/src/ocn/Tendencies.h                    */
 typedef struct omg_stepper omg_stepper; /* O/src/timeStepping/TimeStepper.h          */
+typedef struct omg_vcoord omg_vcoord;   /* O/src/ocn/VertCoord.h class VertCoord     */
+typedef struct omg_eos omg_eos;         /* O/src/ocn/Eos.h       class Eos           */
 
 enum { OMG_ON_CELL = 0, OMG_ON_EDGE = 1, OMG_ON_VERTEX = 2 }; /* O/src/base/Halo.h:45 MeshElement */
 
@@ -443,6 +445,69 @@ int omg_stepper_change_time_step(omg_stepper *st, double time_step_seconds);
 int omg_update_by_tend(double *out_dev, const double *in_dev, const double *tend_dev, double coeff, int n_rows,
                        int nvertlayers, void *stream);
 int omg_stepper_coeff_seconds(double mult, double time_step_seconds, double *out);
+
+/* ---- VertCoord (O/src/ocn/VertCoord.h:28-209, VertCoord.cpp:484-864) and Eos (O/src/ocn/Eos.h:278-328,
+ * Eos.cpp:113-176).  Numerical contract: omega_amd/csrc/VertCoord.h and Eos.h.  Level-indexed device arrays are
+ * [NCellsSize][omg_level_pitch(K)] (interface arrays: omg_level_pitch(K + 1)); per-cell arrays [NCellsSize]; a NULL
+ * per-cell array reads as zero. ---- */
+/* VertCoord::VertCoord (VertCoord.cpp:50-127): min/max_level_cell are the mesh file's global 1-based
+ * minLevelCell / maxLevelCell [nCells] gathered through d (both NULL: every layer active; d may then be NULL);
+ * movement_weight_type "Uniform" or "Fixed" (VertCoord.cpp:614-650; anything else fails).  Fails for a host-only
+ * mesh.  The edge and vertex layer ranges are computed here. */
+int omg_vcoord_create(const omg_mesh *m, const omg_decomp *d, int nvertlayers, double rho0,
+                      const char *movement_weight_type, const int32_t *min_level_cell, const int32_t *max_level_cell,
+                      omg_vcoord **out);
+int omg_vcoord_destroy(omg_vcoord *v);
+/* VertCoord::minMaxLayerEdge (VertCoord.cpp:484-535) / minMaxLayerVertex (VertCoord.cpp:539-610), from the current
+ * MinLayerCell / MaxLayerCell */
+int omg_vcoord_min_max_layer_edge(omg_vcoord *v, void *stream);
+int omg_vcoord_min_max_layer_vertex(omg_vcoord *v, void *stream);
+/* VertCoord::computePressure (VertCoord.cpp:654-696) */
+int omg_vcoord_compute_pressure(omg_vcoord *v, const double *layer_thickness_dev, const double *surface_pressure_dev,
+                                void *stream);
+/* VertCoord::computeZHeight (VertCoord.cpp:700-739) */
+int omg_vcoord_compute_zheight(omg_vcoord *v, const double *layer_thickness_dev, const double *spec_vol_dev,
+                               void *stream);
+/* VertCoord::computeGeopotential (VertCoord.cpp:743-781) */
+int omg_vcoord_compute_geopotential(omg_vcoord *v, const double *tidal_potential_dev,
+                                    const double *self_attraction_loading_dev, void *stream);
+/* VertCoord::computeTargetThickness (VertCoord.cpp:785-838) */
+int omg_vcoord_compute_target_thickness(omg_vcoord *v, void *stream);
+/* the fused column pass (VertCoord::computeColumn): one launch equal, bit for bit, to computePressure ->
+ * Eos::computeSpecVol(T, S, PressureMid * 1.0e-4) -> computeZHeight -> computeGeopotential, with the thickness of
+ * s at thick_time_level and T, S = tracers temp_index, salt_index of t at tracer_time_level (TracerDefs.inc: 0, 1);
+ * displaced != 0 also writes SpecVolDisplaced at displacement kdisp (Eos.cpp:144-176) */
+int omg_vcoord_compute_column(omg_vcoord *v, const omg_state *s, int thick_time_level, const omg_tracers *t,
+                              int tracer_time_level, const omg_eos *e, int temp_index, int salt_index,
+                              const double *surface_pressure_dev, const double *tidal_potential_dev,
+                              const double *self_attraction_loading_dev, int displaced, int kdisp, void *stream);
+/* arrays by reference member name (VertCoord.h:71-120): real "PressureInterface", "PressureMid", "ZInterface",
+ * "ZMid", "GeopotentialMid", "LayerThicknessTarget", "RefLayerThickness", "VertCoordMovementWeights",
+ * "BottomDepth"; int32 "MinLayerCell", "MaxLayerCell", "Min/MaxLayerEdgeTop/Bot", "Min/MaxLayerVertexTop/Bot" */
+int omg_vcoord_copy_to_host(const omg_vcoord *v, const char *name, double *host, size_t n);
+int omg_vcoord_copy_to_device(omg_vcoord *v, const char *name, const double *host, size_t n);
+int omg_vcoord_device_ptr(const omg_vcoord *v, const char *name, double **dev, size_t *n);
+int omg_vcoord_copy_to_host_i4(const omg_vcoord *v, const char *name, int32_t *host, size_t n);
+int omg_vcoord_copy_to_device_i4(omg_vcoord *v, const char *name, const int32_t *host, size_t n);
+/* "Rho0", "Gravity" (VertCoord's own g = 9.80616, VertCoord.cpp:659) */
+int omg_vcoord_get_real(const omg_vcoord *v, const char *name, double *value);
+
+/* Eos::init (Eos.cpp:60-110): eos_type "Linear" / "linear" or "teos10" / "teos-10" / "TEOS-10" (anything else
+ * fails); the linear parameters DRhoDT, DRhoDS, RhoT0S0 (Eos.h:247-249; defaults -0.2, 0.8, 1000).  Fails for a
+ * host-only mesh. */
+int omg_eos_create(const omg_mesh *m, int nvertlayers, const char *eos_type, double drhodt, double drhods,
+                   double rhot0s0, omg_eos **out);
+int omg_eos_destroy(omg_eos *e);
+/* Eos::computeSpecVol (Eos.cpp:113-140) / computeSpecVolDisp (Eos.cpp:144-176); the pressure used is
+ * pressure * p_scale (1.0: dbar as given; 1.0e-4: a Pa array such as VertCoord's PressureMid) */
+int omg_eos_compute_spec_vol(omg_eos *e, const double *conserv_temp_dev, const double *abs_salinity_dev,
+                             const double *pressure_dev, double p_scale, void *stream);
+int omg_eos_compute_spec_vol_disp(omg_eos *e, const double *conserv_temp_dev, const double *abs_salinity_dev,
+                                  const double *pressure_dev, int kdisp, double p_scale, void *stream);
+/* "SpecVol", "SpecVolDisplaced" (Eos.h:281-282) */
+int omg_eos_copy_to_host(const omg_eos *e, const char *name, double *host, size_t n);
+int omg_eos_copy_to_device(omg_eos *e, const char *name, const double *host, size_t n);
+int omg_eos_device_ptr(const omg_eos *e, const char *name, double **dev, size_t *n);
 
 #ifdef __cplusplus
 }

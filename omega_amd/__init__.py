@@ -2,7 +2,7 @@
 
 Thin ctypes plumbing used by tests/, bench.py and __graft_entry__.py: the product is the
 C++/HIP library under omega_amd/csrc (classes named after Omega's own: Decomp, Halo,
-HorzMesh, OceanState, Tracers, AuxiliaryState, Tendencies, TimeStepper).  There is no
+HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, Tendencies, TimeStepper).  There is no
 Python or CPU implementation of the hot path here: if the shared library is missing,
 importing the binding raises, and without a HIP device every device call fails.
 """
@@ -872,6 +872,205 @@ class AuxiliaryState:
     def __del__(self):
         try:
             lib().omg_aux_destroy(self.h)
+        except Exception:
+            pass
+
+
+def _level_dev(x, rows: int, k: int, keep: list):
+    """A level-indexed input as a device pointer: an int is taken as a device address of [rows][level_pitch(k)]
+    doubles, a numpy array [rows][k] is staged into a padded device copy (kept alive in `keep`)."""
+    if isinstance(x, (int, np.integer)):
+        return C.c_void_p(int(x))
+    a = np.asarray(x, dtype=np.float64)
+    assert a.shape == (rows, k), f"expected shape {(rows, k)}, got {a.shape}"
+    pad = np.zeros((rows, level_pitch(k)))
+    pad[:, :k] = a
+    b = DeviceBuffer(pad)
+    keep.append(b)
+    return C.c_void_p(b.ptr)
+
+
+def _cell_dev(x, rows: int, keep: list):
+    """A per-cell input as a device pointer: None (NULL: read as zero), an int device address or a numpy array."""
+    if x is None:
+        return None
+    if isinstance(x, (int, np.integer)):
+        return C.c_void_p(int(x))
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    assert a.shape == (rows,), f"expected shape {(rows,)}, got {a.shape}"
+    b = DeviceBuffer(a)
+    keep.append(b)
+    return C.c_void_p(b.ptr)
+
+
+def tracer_rows_ptr(tracers: Tracers, index: int, time_level: int = 0) -> int:
+    """Device address of the rows of tracer `index` ([NCellsSize][level_pitch(K)]) in the tracer array: a view
+    with no copy, what Eos.compute_spec_vol takes for T and S."""
+    if not 0 <= index < tracers.NT:
+        raise OmegaAmdError(f"tracer index {index} out of range (0..{tracers.NT - 1})")
+    return tracers.device_ptr(time_level) + index * tracers.mesh.NCellsSize * level_pitch(tracers.K) * 8
+
+
+class Eos:
+    """Eos (omega_amd/csrc/Eos.h): specific volume, linear or TEOS-10.  Level-indexed inputs are numpy arrays
+    [NCellsSize][K] or device addresses of [NCellsSize][level_pitch(K)] doubles."""
+
+    def __init__(self, mesh: HorzMesh, nvertlayers: int, eos_type: str = "teos10", drhodt: float = -0.2,
+                 drhods: float = 0.8, rhot0s0: float = 1000.0):
+        self.mesh, self.K = mesh, nvertlayers
+        h = C.c_void_p()
+        _chk(lib().omg_eos_create(mesh.h, nvertlayers, eos_type.encode(), C.c_double(drhodt), C.c_double(drhods),
+                                  C.c_double(rhot0s0), C.byref(h)))
+        self.h = h
+
+    def compute_spec_vol(self, conserv_temp, abs_salinity, pressure, p_scale: float = 1.0, stream=None):
+        keep, n = [], self.mesh.NCellsSize
+        _chk(lib().omg_eos_compute_spec_vol(self.h, _level_dev(conserv_temp, n, self.K, keep),
+                                            _level_dev(abs_salinity, n, self.K, keep),
+                                            _level_dev(pressure, n, self.K, keep), C.c_double(p_scale), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def compute_spec_vol_disp(self, conserv_temp, abs_salinity, pressure, kdisp: int, p_scale: float = 1.0,
+                              stream=None):
+        keep, n = [], self.mesh.NCellsSize
+        _chk(lib().omg_eos_compute_spec_vol_disp(self.h, _level_dev(conserv_temp, n, self.K, keep),
+                                                 _level_dev(abs_salinity, n, self.K, keep),
+                                                 _level_dev(pressure, n, self.K, keep), int(kdisp),
+                                                 C.c_double(p_scale), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def get(self, name: str) -> np.ndarray:
+        out = np.zeros((self.mesh.NCellsSize, self.K))
+        _chk(lib().omg_eos_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
+        return out
+
+    def set(self, name: str, values: np.ndarray):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        _chk(lib().omg_eos_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
+
+    def device_ptr(self, name: str) -> int:
+        p = PD()
+        _chk(lib().omg_eos_device_ptr(self.h, name.encode(), C.byref(p), None))
+        return C.cast(p, C.c_void_p).value
+
+    def __del__(self):
+        try:
+            lib().omg_eos_destroy(self.h)
+        except Exception:
+            pass
+
+
+VCOORD_SHAPES = {"PressureInterface": "CK1", "PressureMid": "CK", "ZInterface": "CK1", "ZMid": "CK",
+                 "GeopotentialMid": "CK", "LayerThicknessTarget": "CK", "RefLayerThickness": "CK",
+                 "VertCoordMovementWeights": "K", "BottomDepth": "C"}
+VCOORD_I4 = {"MinLayerCell": "C", "MaxLayerCell": "C", "MinLayerEdgeTop": "E", "MaxLayerEdgeTop": "E",
+             "MinLayerEdgeBot": "E", "MaxLayerEdgeBot": "E", "MinLayerVertexTop": "V", "MaxLayerVertexTop": "V",
+             "MinLayerVertexBot": "V", "MaxLayerVertexBot": "V"}
+
+
+class VertCoord:
+    """VertCoord (omega_amd/csrc/VertCoord.h): layer ranges, pressure, z-height, geopotential, target thickness and
+    the fused column pass.  min_level_cell / max_level_cell: the mesh file's global 1-based arrays [nCells], gathered
+    through `decomp` (default: the mesh's)."""
+
+    def __init__(self, mesh: HorzMesh, nvertlayers: int, rho0: float = 1026.0, movement_weight_type: str = "Uniform",
+                 min_level_cell=None, max_level_cell=None, decomp: Decomp | None = None):
+        self.mesh, self.K = mesh, nvertlayers
+        d = decomp if decomp is not None else getattr(mesh, "decomp", None)
+        mn = None if min_level_cell is None else np.ascontiguousarray(min_level_cell, dtype=np.int32)
+        mx = None if max_level_cell is None else np.ascontiguousarray(max_level_cell, dtype=np.int32)
+        h = C.c_void_p()
+        _chk(lib().omg_vcoord_create(mesh.h, d.h if d is not None else None, nvertlayers, C.c_double(rho0),
+                                     movement_weight_type.encode(), _pi(mn), _pi(mx), C.byref(h)))
+        self.h = h
+
+    def min_max_layer_edge(self, stream=None):
+        _chk(lib().omg_vcoord_min_max_layer_edge(self.h, _sh(stream)))
+
+    def min_max_layer_vertex(self, stream=None):
+        _chk(lib().omg_vcoord_min_max_layer_vertex(self.h, _sh(stream)))
+
+    def compute_pressure(self, layer_thickness, surface_pressure=None, stream=None):
+        keep, n = [], self.mesh.NCellsSize
+        _chk(lib().omg_vcoord_compute_pressure(self.h, _level_dev(layer_thickness, n, self.K, keep),
+                                               _cell_dev(surface_pressure, n, keep), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def compute_zheight(self, layer_thickness, spec_vol, stream=None):
+        keep, n = [], self.mesh.NCellsSize
+        _chk(lib().omg_vcoord_compute_zheight(self.h, _level_dev(layer_thickness, n, self.K, keep),
+                                              _level_dev(spec_vol, n, self.K, keep), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def compute_geopotential(self, tidal_potential=None, self_attraction_loading=None, stream=None):
+        keep, n = [], self.mesh.NCellsSize
+        _chk(lib().omg_vcoord_compute_geopotential(self.h, _cell_dev(tidal_potential, n, keep),
+                                                   _cell_dev(self_attraction_loading, n, keep), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def compute_target_thickness(self, stream=None):
+        _chk(lib().omg_vcoord_compute_target_thickness(self.h, _sh(stream)))
+
+    def compute_column(self, state: OceanState, tracers: Tracers, eos: Eos, surface_pressure=None,
+                       tidal_potential=None, self_attraction_loading=None, kdisp: int | None = None,
+                       thick_tl: int = 0, tracer_tl: int = 0, temp_index: int = 0, salt_index: int = 1, stream=None):
+        """The fused pass: PressureInterface/Mid, eos.SpecVol (pressure PressureMid * 1e-4 dbar), ZInterface/ZMid,
+        GeopotentialMid -- and eos.SpecVolDisplaced when kdisp is given -- in one launch."""
+        keep, n = [], self.mesh.NCellsSize
+        _chk(lib().omg_vcoord_compute_column(self.h, state.h, thick_tl, tracers.h, tracer_tl, eos.h, temp_index,
+                                             salt_index, _cell_dev(surface_pressure, n, keep),
+                                             _cell_dev(tidal_potential, n, keep),
+                                             _cell_dev(self_attraction_loading, n, keep), int(kdisp is not None),
+                                             int(kdisp or 0), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def _shape(self, spec):
+        m = self.mesh
+        rows = {"C": m.NCellsSize, "E": m.NEdgesSize, "V": m.NVerticesSize}
+        if spec == "K":
+            return (self.K,)
+        if spec == "CK":
+            return (rows["C"], self.K)
+        if spec == "CK1":
+            return (rows["C"], self.K + 1)
+        return (rows[spec],)
+
+    def get(self, name: str) -> np.ndarray:
+        if name in VCOORD_I4:
+            out = np.zeros(self._shape(VCOORD_I4[name]), dtype=np.int32)
+            _chk(lib().omg_vcoord_copy_to_host_i4(self.h, name.encode(), _pi(out), C.c_size_t(out.size)))
+            return out
+        out = np.zeros(self._shape(VCOORD_SHAPES.get(name, "CK")))
+        _chk(lib().omg_vcoord_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
+        return out
+
+    def set(self, name: str, values: np.ndarray):
+        if name in VCOORD_I4:
+            v = np.ascontiguousarray(values, dtype=np.int32)
+            _chk(lib().omg_vcoord_copy_to_device_i4(self.h, name.encode(), _pi(v), C.c_size_t(v.size)))
+            return
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        _chk(lib().omg_vcoord_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
+
+    def device_ptr(self, name: str) -> int:
+        p = PD()
+        _chk(lib().omg_vcoord_device_ptr(self.h, name.encode(), C.byref(p), None))
+        return C.cast(p, C.c_void_p).value
+
+    def get_real(self, name: str) -> float:
+        v = C.c_double()
+        _chk(lib().omg_vcoord_get_real(self.h, name.encode(), C.byref(v)))
+        return v.value
+
+    def __del__(self):
+        try:
+            lib().omg_vcoord_destroy(self.h)
         except Exception:
             pass
 

@@ -17,6 +17,8 @@
 #include "Rccl.h"
 #include "Tuning.h"
 #include "TimeStepper.h"
+#include "VertCoord.h"
+#include "Eos.h"
 
 #include <cstring>
 #include <map>
@@ -57,6 +59,12 @@ struct omg_tend {
 };
 struct omg_stepper {
    std::unique_ptr<TimeStepper> St;
+};
+struct omg_vcoord {
+   std::unique_ptr<VertCoord> V;
+};
+struct omg_eos {
+   std::unique_ptr<Eos> E;
 };
 
 static thread_local std::string LastError;
@@ -1379,6 +1387,258 @@ int omg_stepper_coeff_seconds(double mult, double dt, double *out) {
    OMG_TRY
    OMG_ARG(out);
    *out = TimeStepper::coeffSeconds(mult, dt);
+   OMG_CATCH
+}
+
+// ---------------------------------------------------------------- VertCoord / Eos
+/// a raw device array [rows][levelPitch(k)] of the caller's as a 2-D array handle (no ownership)
+static Array2DReal levelView(const double *Dev, int Rows, int K) {
+   Array2DReal A;
+   A.Ptr    = const_cast<Real *>(Dev);
+   A.Ext[0] = Rows, A.Ext[1] = K;
+   A.Pitch  = levelPitch(K);
+   return A;
+}
+/// a raw device array [rows] of the caller's (NULL: empty, read as zero)
+static Array1DReal cellView(const double *Dev, int Rows) {
+   Array1DReal A;
+   A.Ptr    = const_cast<Real *>(Dev);
+   A.Ext[0] = Dev ? Rows : 0;
+   A.Pitch  = 1;
+   return A;
+}
+int omg_vcoord_create(const omg_mesh *m, const omg_decomp *d, int nvertlayers, double rho0,
+                      const char *movement_weight_type, const int32_t *min_level_cell, const int32_t *max_level_cell,
+                      omg_vcoord **out) {
+   OMG_TRY
+   OMG_ARG(m && out && movement_weight_type);
+   auto *R = new omg_vcoord;
+   try {
+      R->V.reset(new VertCoord("Default", m->M.get(), d ? d->D.get() : nullptr, nvertlayers, rho0,
+                               movement_weight_type, min_level_cell, max_level_cell));
+   } catch (...) {
+      delete R;
+      throw;
+   }
+   *out = R;
+   OMG_CATCH
+}
+int omg_vcoord_destroy(omg_vcoord *v) {
+   delete v;
+   return 0;
+}
+int omg_vcoord_min_max_layer_edge(omg_vcoord *v, void *stream) {
+   OMG_TRY
+   OMG_ARG(v);
+   v->V->minMaxLayerEdge((hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vcoord_min_max_layer_vertex(omg_vcoord *v, void *stream) {
+   OMG_TRY
+   OMG_ARG(v);
+   v->V->minMaxLayerVertex((hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vcoord_compute_pressure(omg_vcoord *v, const double *layer_thickness, const double *surface_pressure,
+                                void *stream) {
+   OMG_TRY
+   OMG_ARG(v && layer_thickness);
+   const HorzMesh *M = v->V->Mesh;
+   v->V->computePressure(levelView(layer_thickness, M->NCellsSize, v->V->NVertLayers),
+                         cellView(surface_pressure, M->NCellsSize), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vcoord_compute_zheight(omg_vcoord *v, const double *layer_thickness, const double *spec_vol, void *stream) {
+   OMG_TRY
+   OMG_ARG(v && layer_thickness && spec_vol);
+   const HorzMesh *M = v->V->Mesh;
+   v->V->computeZHeight(levelView(layer_thickness, M->NCellsSize, v->V->NVertLayers),
+                        levelView(spec_vol, M->NCellsSize, v->V->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vcoord_compute_geopotential(omg_vcoord *v, const double *tidal_potential,
+                                    const double *self_attraction_loading, void *stream) {
+   OMG_TRY
+   OMG_ARG(v);
+   const HorzMesh *M = v->V->Mesh;
+   v->V->computeGeopotential(cellView(tidal_potential, M->NCellsSize), cellView(self_attraction_loading, M->NCellsSize),
+                             (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vcoord_compute_target_thickness(omg_vcoord *v, void *stream) {
+   OMG_TRY
+   OMG_ARG(v);
+   v->V->computeTargetThickness((hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vcoord_compute_column(omg_vcoord *v, const omg_state *s, int thick_time_level, const omg_tracers *t,
+                              int tracer_time_level, const omg_eos *e, int temp_index, int salt_index,
+                              const double *surface_pressure, const double *tidal_potential,
+                              const double *self_attraction_loading, int displaced, int kdisp, void *stream) {
+   OMG_TRY
+   OMG_ARG(v && s && t && e);
+   const int N = v->V->Mesh->NCellsSize;
+   v->V->computeColumn(s->S.get(), thick_time_level, t->T.get(), tracer_time_level, *e->E, cellView(surface_pressure, N),
+                       cellView(tidal_potential, N), cellView(self_attraction_loading, N), displaced != 0, kdisp,
+                       (hipStream_t)stream, temp_index, salt_index);
+   OMG_CATCH
+}
+static ArrRef vcoordLookup(const VertCoord &V, const std::string &Name) {
+   const std::map<std::string, ArrRef> M{{"PressureInterface", arrRef(V.PressureInterface)},
+                                         {"PressureMid", arrRef(V.PressureMid)},
+                                         {"ZInterface", arrRef(V.ZInterface)},
+                                         {"ZMid", arrRef(V.ZMid)},
+                                         {"GeopotentialMid", arrRef(V.GeopotentialMid)},
+                                         {"LayerThicknessTarget", arrRef(V.LayerThicknessTarget)},
+                                         {"RefLayerThickness", arrRef(V.RefLayerThickness)},
+                                         {"VertCoordMovementWeights", arrRef(V.VertCoordMovementWeights)},
+                                         {"BottomDepth", arrRef(V.BottomDepth)}};
+   auto It = M.find(Name);
+   if (It == M.end())
+      OMEGA_ABORT("VertCoord: no real array named " + Name);
+   return It->second;
+}
+static const Array1DI4 &vcoordLookupI4(const VertCoord &V, const std::string &Name) {
+   const std::map<std::string, const Array1DI4 *> M{
+       {"MinLayerCell", &V.MinLayerCell},           {"MaxLayerCell", &V.MaxLayerCell},
+       {"MinLayerEdgeTop", &V.MinLayerEdgeTop},     {"MaxLayerEdgeTop", &V.MaxLayerEdgeTop},
+       {"MinLayerEdgeBot", &V.MinLayerEdgeBot},     {"MaxLayerEdgeBot", &V.MaxLayerEdgeBot},
+       {"MinLayerVertexTop", &V.MinLayerVertexTop}, {"MaxLayerVertexTop", &V.MaxLayerVertexTop},
+       {"MinLayerVertexBot", &V.MinLayerVertexBot}, {"MaxLayerVertexBot", &V.MaxLayerVertexBot}};
+   auto It = M.find(Name);
+   if (It == M.end())
+      OMEGA_ABORT("VertCoord: no integer array named " + Name);
+   return *It->second;
+}
+static int refCopyToHost(const ArrRef &R, const char *name, double *host, size_t n) {
+   if (n < R.size())
+      OMEGA_ABORT(std::string("output buffer too small for ") + name);
+   copyRowsToHost(host, R.Ptr, R.Pitch, R.Rows, R.Width);
+   return 0;
+}
+static int refCopyToDevice(const ArrRef &R, const char *name, const double *host, size_t n) {
+   if (n != R.size())
+      OMEGA_ABORT(std::string("size mismatch for ") + name);
+   copyRowsToDevice(R.Ptr, R.Pitch, host, R.Rows, R.Width);
+   return 0;
+}
+int omg_vcoord_copy_to_host(const omg_vcoord *v, const char *name, double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(v && name && host);
+   refCopyToHost(vcoordLookup(*v->V, name), name, host, n);
+   OMG_CATCH
+}
+int omg_vcoord_copy_to_device(omg_vcoord *v, const char *name, const double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(v && name && host);
+   refCopyToDevice(vcoordLookup(*v->V, name), name, host, n);
+   OMG_CATCH
+}
+int omg_vcoord_device_ptr(const omg_vcoord *v, const char *name, double **dev, size_t *n) {
+   OMG_TRY
+   OMG_ARG(v && name && dev);
+   const ArrRef R = vcoordLookup(*v->V, name);
+   *dev = R.Ptr;
+   if (n)
+      *n = R.size();
+   OMG_CATCH
+}
+int omg_vcoord_copy_to_host_i4(const omg_vcoord *v, const char *name, int32_t *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(v && name && host);
+   const Array1DI4 &A = vcoordLookupI4(*v->V, name);
+   if (n < A.size())
+      OMEGA_ABORT(std::string("output buffer too small for ") + name);
+   HIP_CHECK(hipDeviceSynchronize());
+   copyToHost(host, A.Ptr, A.bytes());
+   OMG_CATCH
+}
+int omg_vcoord_copy_to_device_i4(omg_vcoord *v, const char *name, const int32_t *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(v && name && host);
+   const Array1DI4 &A = vcoordLookupI4(*v->V, name);
+   if (n != A.size())
+      OMEGA_ABORT(std::string("size mismatch for ") + name);
+   HIP_CHECK(hipDeviceSynchronize());
+   copyToDevice(A.Ptr, host, A.bytes());
+   HIP_CHECK(hipDeviceSynchronize());
+   OMG_CATCH
+}
+int omg_vcoord_get_real(const omg_vcoord *v, const char *name, double *value) {
+   OMG_TRY
+   OMG_ARG(v && name && value);
+   const std::string N(name);
+   if (N == "Rho0")
+      *value = v->V->Rho0;
+   else if (N == "Gravity")
+      *value = VertCoord::Gravity;
+   else
+      OMEGA_ABORT("VertCoord: no scalar named " + N);
+   OMG_CATCH
+}
+
+int omg_eos_create(const omg_mesh *m, int nvertlayers, const char *eos_type, double drhodt, double drhods,
+                   double rhot0s0, omg_eos **out) {
+   OMG_TRY
+   OMG_ARG(m && out && eos_type);
+   auto *R = new omg_eos;
+   try {
+      R->E.reset(new Eos("Default", m->M.get(), nvertlayers, eos_type, drhodt, drhods, rhot0s0));
+   } catch (...) {
+      delete R;
+      throw;
+   }
+   *out = R;
+   OMG_CATCH
+}
+int omg_eos_destroy(omg_eos *e) {
+   delete e;
+   return 0;
+}
+int omg_eos_compute_spec_vol(omg_eos *e, const double *conserv_temp, const double *abs_salinity,
+                             const double *pressure, double p_scale, void *stream) {
+   OMG_TRY
+   OMG_ARG(e && conserv_temp && abs_salinity && pressure);
+   const int N = e->E->Mesh->NCellsSize, K = e->E->NVertLayers;
+   e->E->computeSpecVol(levelView(conserv_temp, N, K), levelView(abs_salinity, N, K), levelView(pressure, N, K),
+                        p_scale, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_eos_compute_spec_vol_disp(omg_eos *e, const double *conserv_temp, const double *abs_salinity,
+                                  const double *pressure, int kdisp, double p_scale, void *stream) {
+   OMG_TRY
+   OMG_ARG(e && conserv_temp && abs_salinity && pressure);
+   const int N = e->E->Mesh->NCellsSize, K = e->E->NVertLayers;
+   e->E->computeSpecVolDisp(levelView(conserv_temp, N, K), levelView(abs_salinity, N, K), levelView(pressure, N, K),
+                            kdisp, p_scale, (hipStream_t)stream);
+   OMG_CATCH
+}
+static ArrRef eosLookup(const Eos &E, const std::string &Name) {
+   if (Name == "SpecVol")
+      return arrRef(E.SpecVol);
+   if (Name == "SpecVolDisplaced")
+      return arrRef(E.SpecVolDisplaced);
+   OMEGA_ABORT("Eos: no array named " + Name);
+}
+int omg_eos_copy_to_host(const omg_eos *e, const char *name, double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(e && name && host);
+   refCopyToHost(eosLookup(*e->E, name), name, host, n);
+   OMG_CATCH
+}
+int omg_eos_copy_to_device(omg_eos *e, const char *name, const double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(e && name && host);
+   refCopyToDevice(eosLookup(*e->E, name), name, host, n);
+   OMG_CATCH
+}
+int omg_eos_device_ptr(const omg_eos *e, const char *name, double **dev, size_t *n) {
+   OMG_TRY
+   OMG_ARG(e && name && dev);
+   const ArrRef R = eosLookup(*e->E, name);
+   *dev = R.Ptr;
+   if (n)
+      *n = R.size();
    OMG_CATCH
 }
 
