@@ -509,6 +509,24 @@ int omg_eos_copy_to_host(const omg_eos *e, const char *name, double *host, size_
 int omg_eos_copy_to_device(omg_eos *e, const char *name, const double *host, size_t n);
 int omg_eos_device_ptr(const omg_eos *e, const char *name, double **dev, size_t *n);
 
+/* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
+ * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at
+ * dev + i * row_pitch (row_pitch 0: nrow).  x holds the right-hand side on entry and the solution on return; only
+ * x[0:nbatch][0:nrow] is written, the coefficient arrays are left unchanged, nothing is allocated.  Asynchronous on
+ * stream (NULL: the null stream). ---- */
+/* ThomasSolver::solve (TriDiagSolvers.h:97-134): DL x(k-1) + D x(k) + DU x(k+1) = x */
+int omg_tridiag_thomas_solve(const double *dl_dev, const double *d_dev, const double *du_dev, double *x_dev, int nbatch,
+                             int nrow, int row_pitch, void *stream);
+/* PCRSolver::solve (TriDiagSolvers.h:217-244) */
+int omg_tridiag_pcr_solve(const double *dl_dev, const double *d_dev, const double *du_dev, double *x_dev, int nbatch,
+                          int nrow, int row_pitch, void *stream);
+/* ThomasDiffusionSolver::solve (TriDiagSolvers.h:324-359): -G(k-1) x(k-1) + (H(k) + G(k-1) + G(k)) x(k) - G(k) x(k+1) = x */
+int omg_tridiag_thomas_diff_solve(const double *g_dev, const double *h_dev, double *x_dev, int nbatch, int nrow,
+                                  int row_pitch, void *stream);
+/* PCRDiffusionSolver::solve (TriDiagSolvers.h:458-483) */
+int omg_tridiag_pcr_diff_solve(const double *g_dev, const double *h_dev, double *x_dev, int nbatch, int nrow,
+                               int row_pitch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

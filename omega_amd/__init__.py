@@ -389,6 +389,47 @@ def device_resource_count() -> int:
     return n.value
 
 
+_TRIDIAG = {("general", "pcr"): "omg_tridiag_pcr_solve", ("general", "thomas"): "omg_tridiag_thomas_solve",
+            ("diffusion", "pcr"): "omg_tridiag_pcr_diff_solve", ("diffusion", "thomas"): "omg_tridiag_thomas_diff_solve"}
+
+
+def _tridiag(form, algorithm, coeffs, x, stream, nbatch, nrow, row_pitch):
+    """The batched tridiagonal solvers (omega_amd/csrc/TriDiagSolvers.h).  With numpy arrays: [NBatch][NRow] inputs,
+    staged to the device, solved, and the solution returned as a new array.  With device addresses (ints): solved in
+    place on `stream` (asynchronous), nbatch / nrow / row_pitch (0 = nrow) given."""
+    key = (form, algorithm)
+    if key not in _TRIDIAG:
+        raise ValueError(f"algorithm must be 'pcr' or 'thomas', not {algorithm!r}")
+    fn = getattr(lib(), _TRIDIAG[key])
+    if isinstance(x, (int, np.integer)):
+        if nbatch is None or nrow is None:
+            raise ValueError("the device-address form needs nbatch and nrow")
+        ptrs = [C.c_void_p(int(a)) for a in coeffs] + [C.c_void_p(int(x))]
+        _chk(fn(*ptrs, int(nbatch), int(nrow), int(row_pitch), _sh(stream)))
+        return None
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (*coeffs, x)]
+    shape = arrs[-1].shape
+    if len(shape) != 2 or any(a.shape != shape for a in arrs):
+        raise OmegaAmdError(f"tridiagonal solve: every array must be [NBatch][NRow] of one shape, got "
+                            f"{[a.shape for a in arrs]}")
+    bufs = [DeviceBuffer(a) for a in arrs]
+    _chk(fn(*[C.c_void_p(b.ptr) for b in bufs], shape[0], shape[1], 0, _sh(stream)))
+    if stream is not None:
+        stream.synchronize()
+    return bufs[-1].to_host()
+
+
+def tridiag_solve(dl, d, du, x, algorithm: str = "pcr", stream=None, nbatch=None, nrow=None, row_pitch: int = 0):
+    """Solve DL x(k-1) + D x(k) + DU x(k+1) = X per row: ThomasSolver / PCRSolver::solve (TriDiagSolvers.h)."""
+    return _tridiag("general", algorithm, (dl, d, du), x, stream, nbatch, nrow, row_pitch)
+
+
+def tridiag_diff_solve(g, h, x, algorithm: str = "pcr", stream=None, nbatch=None, nrow=None, row_pitch: int = 0):
+    """Solve -G(k-1) x(k-1) + (H(k) + G(k-1) + G(k)) x(k) - G(k) x(k+1) = X per row: ThomasDiffusionSolver /
+    PCRDiffusionSolver::solve (TriDiagSolvers.h)."""
+    return _tridiag("diffusion", algorithm, (g, h), x, stream, nbatch, nrow, row_pitch)
+
+
 def global_sum_dd(local_hi_lo, group=None, halo=None, stream=None) -> float:
     """globalSum (Reductions.h:71-84): all-gather the ranks' (hi, lo) partial sums and combine them with the
     ddSum operator in rank order -- the same value on every rank and for every partition.  With `halo` the gather

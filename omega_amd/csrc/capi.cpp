@@ -19,6 +19,7 @@
 #include "TimeStepper.h"
 #include "VertCoord.h"
 #include "Eos.h"
+#include "TriDiagSolvers.h"
 
 #include <cstring>
 #include <map>
@@ -1639,6 +1640,49 @@ int omg_eos_device_ptr(const omg_eos *e, const char *name, double **dev, size_t 
    *dev = R.Ptr;
    if (n)
       *n = R.size();
+   OMG_CATCH
+}
+
+// ---- batched tridiagonal solvers (TriDiagSolvers.h)
+/// a caller's [nbatch][nrow] device array of row pitch row_pitch (0: nrow) as the solvers' Array2DReal
+static Array2DReal rowsView(const double *Dev, int NBatch, int NRow, int RowPitch) {
+   Array2DReal A;
+   A.Ptr    = const_cast<Real *>(Dev);
+   A.Ext[0] = NBatch, A.Ext[1] = NRow;
+   A.Pitch  = RowPitch == 0 ? NRow : RowPitch;
+   return A;
+}
+int omg_tridiag_thomas_solve(const double *dl, const double *d, const double *du, double *x, int nbatch, int nrow,
+                             int row_pitch, void *stream) {
+   OMG_TRY
+   OMG_ARG(row_pitch >= 0);
+   ThomasSolver::solve(rowsView(dl, nbatch, nrow, row_pitch), rowsView(d, nbatch, nrow, row_pitch),
+                       rowsView(du, nbatch, nrow, row_pitch), rowsView(x, nbatch, nrow, row_pitch),
+                       (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_tridiag_pcr_solve(const double *dl, const double *d, const double *du, double *x, int nbatch, int nrow,
+                          int row_pitch, void *stream) {
+   OMG_TRY
+   OMG_ARG(row_pitch >= 0);
+   PCRSolver::solve(rowsView(dl, nbatch, nrow, row_pitch), rowsView(d, nbatch, nrow, row_pitch),
+                    rowsView(du, nbatch, nrow, row_pitch), rowsView(x, nbatch, nrow, row_pitch), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_tridiag_thomas_diff_solve(const double *g, const double *h, double *x, int nbatch, int nrow, int row_pitch,
+                                  void *stream) {
+   OMG_TRY
+   OMG_ARG(row_pitch >= 0);
+   ThomasDiffusionSolver::solve(rowsView(g, nbatch, nrow, row_pitch), rowsView(h, nbatch, nrow, row_pitch),
+                                rowsView(x, nbatch, nrow, row_pitch), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_tridiag_pcr_diff_solve(const double *g, const double *h, double *x, int nbatch, int nrow, int row_pitch,
+                               void *stream) {
+   OMG_TRY
+   OMG_ARG(row_pitch >= 0);
+   PCRDiffusionSolver::solve(rowsView(g, nbatch, nrow, row_pitch), rowsView(h, nbatch, nrow, row_pitch),
+                             rowsView(x, nbatch, nrow, row_pitch), (hipStream_t)stream);
    OMG_CATCH
 }
 

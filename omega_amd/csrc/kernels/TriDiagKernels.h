@@ -1,0 +1,241 @@
+// TriDiagKernels.h -- the bodies of the batched tridiagonal solvers behind TriDiagSolvers.h (the reference's
+// components/omega/src/base/TriDiagSolvers.h) as device functions, and the host-callable launchers of their array form
+// (kernels/TriDiagKernels.hip).  The numerical contract is written down in TriDiagSolvers.h.
+//
+// The device functions are the counterpart of the reference's team-level solve(Member, Scratch): a kernel that has
+// assembled its columns itself (in registers, one row per lane, for PCR; in any memory, one column per lane, for Thomas)
+// solves them in place.  Every expression keeps the reference's association; the library is built with
+// -ffp-contract=off and divides with the IEEE `/`, so the results are bit for bit those of the reference run serially.
+#ifndef OMEGA_AMD_TRIDIAGKERNELS_H
+#define OMEGA_AMD_TRIDIAGKERNELS_H
+
+#include "../Base.h"
+
+namespace OMEGA {
+
+/// Largest system the solvers accept (one row per lane of a workgroup for PCR)
+constexpr int TriDiagMaxRows = 1024;
+
+// ---------------------------------------------------------------------------------------------------------------------
+// device bodies
+// ---------------------------------------------------------------------------------------------------------------------
+
+/// Number of PCR levels, ceil(log2(NRow)) for NRow > 1 (TriDiagSolvers.h:160, in integers: exact for NRow <= 2^31)
+__host__ __device__ inline int pcrLevels(int NRow) {
+   int L = 0;
+   while ((1 << L) < NRow)
+      ++L;
+   return L;
+}
+
+/// PCRSolver::solve(Member, Scratch) (TriDiagSolvers.h:152-213) for the row K of one system of NRow rows whose
+/// coefficients this thread holds (DL, D, DU, X); returns the solution of row K.
+///
+/// Every thread of the workgroup calls it with the same NRow (it holds pcrLevels(NRow) __syncthreads()); a thread
+/// with no row passes Active = false and only joins the barriers.  `Sys` points to row 0 of the thread's system in a
+/// workspace of 2 x 4 arrays of `Span` doubles each (array A of buffer B at Sys[(B * 4 + A) * Span + row]), in LDS;
+/// several systems may share one workspace at different offsets.  The workspace is read until the function returns:
+/// a caller that reuses it barriers first.
+__device__ inline Real pcrSolveRow(bool Active, int K, int NRow, Real DL, Real D, Real DU, Real X, Real *Sys,
+                                   int Span) {
+   if (NRow == 1) // the reference's 1 << -1; defined as the 1x1 solve (TriDiagSolvers.h)
+      return X / D;
+   const int NLevels = pcrLevels(NRow);
+   int B             = 0;
+   for (int Lev = 1; Lev < NLevels; ++Lev) {
+      Real *W = Sys + B * 4 * Span;
+      if (Active) {
+         W[0 * Span + K] = DL, W[1 * Span + K] = D, W[2 * Span + K] = DU, W[3 * Span + K] = X;
+      }
+      __syncthreads();
+      if (Active) {
+         const int HalfStride = 1 << (Lev - 1);
+         int Kmh              = K - HalfStride;
+         Kmh                  = Kmh < 0 ? 0 : Kmh;
+         int Kph              = K + HalfStride;
+         Kph                  = Kph >= NRow ? NRow - 1 : Kph;
+
+         const Real Alpha = -DL / W[1 * Span + Kmh];
+         const Real Gamma = -DU / W[1 * Span + Kph];
+
+         const Real NewD  = D + Alpha * W[2 * Span + Kmh] + Gamma * W[0 * Span + Kph];
+         const Real NewX  = X + Alpha * W[3 * Span + Kmh] + Gamma * W[3 * Span + Kph];
+         const Real NewDL = Alpha * W[0 * Span + Kmh];
+         const Real NewDU = Gamma * W[2 * Span + Kph];
+         DL = NewDL, D = NewD, DU = NewDU, X = NewX;
+      }
+      B ^= 1; // the next level writes the other buffer: one barrier per level
+   }
+   Real *W = Sys + B * 4 * Span;
+   if (Active) {
+      W[0 * Span + K] = DL, W[1 * Span + K] = D, W[2 * Span + K] = DU, W[3 * Span + K] = X;
+   }
+   __syncthreads();
+   if (!Active)
+      return X;
+   const int Stride = 1 << (NLevels - 1);
+   // The 2x2 systems (K, K + Stride): the reference's thread K (K < NRow / 2) writes both rows; here each row's thread
+   // computes its own row with the same expressions.  K + Stride < NRow implies K < NRow / 2 because Stride >= NRow / 2.
+   if (K + Stride < NRow) {
+      const int P     = K + Stride;
+      const Real Det  = D * W[1 * Span + P] - W[0 * Span + P] * DU;
+      const Real Xk   = X;
+      const Real Xkps = W[3 * Span + P];
+      return (W[1 * Span + P] * Xk - DU * Xkps) / Det;
+   }
+   if (K - Stride >= 0) {
+      const int P     = K - Stride;
+      const Real Det  = W[1 * Span + P] * D - DL * W[2 * Span + P];
+      const Real Xk   = W[3 * Span + P];
+      const Real Xkps = X;
+      return (-DL * Xk + W[1 * Span + P] * Xkps) / Det;
+   }
+   return X / D; // 1x1 system
+}
+
+/// PCRDiffusionSolver::solve(Member, Scratch) (TriDiagSolvers.h:377-454) for row K, as pcrSolveRow; the workspace
+/// holds 2 x 3 arrays (G, H, X) of `Span` doubles: array A of buffer B at Sys[(B * 3 + A) * Span + row].
+__device__ inline Real pcrDiffSolveRow(bool Active, int K, int NRow, Real G, Real H, Real X, Real *Sys, int Span) {
+   if (NRow == 1) // the reference's 1 << -1; defined as the 1x1 solve (TriDiagSolvers.h)
+      return X / (H + G);
+   const int NLevels = pcrLevels(NRow);
+   int B             = 0;
+   for (int Lev = 1; Lev < NLevels; ++Lev) {
+      Real *W = Sys + B * 3 * Span;
+      if (Active) {
+         W[0 * Span + K] = G, W[1 * Span + K] = H, W[2 * Span + K] = X;
+      }
+      __syncthreads();
+      if (Active) {
+         const int Stride     = 1 << Lev;
+         const int HalfStride = 1 << (Lev - 1);
+
+         int Kmh         = K - HalfStride;
+         const Real Gkmh = Kmh < 0 ? 0 : W[0 * Span + Kmh];
+         Kmh             = Kmh < 0 ? 0 : Kmh;
+
+         const int Kms   = K - Stride;
+         const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
+
+         int Kph = K + HalfStride;
+         Kph     = Kph >= NRow ? NRow - 1 : Kph;
+
+         const Real Alpha = Gkmh / (W[1 * Span + Kmh] + Gkms + Gkmh);
+         const Real Beta  = G / (W[1 * Span + Kph] + G + W[0 * Span + Kph]);
+
+         const Real NewG = W[0 * Span + Kph] * Beta;
+         const Real NewX = X + Alpha * W[2 * Span + Kmh] + Beta * W[2 * Span + Kph];
+         const Real NewH = H + Alpha * W[1 * Span + Kmh] + Beta * W[1 * Span + Kph];
+         G = NewG, H = NewH, X = NewX;
+      }
+      B ^= 1;
+   }
+   Real *W = Sys + B * 3 * Span;
+   if (Active) {
+      W[0 * Span + K] = G, W[1 * Span + K] = H, W[2 * Span + K] = X;
+   }
+   __syncthreads();
+   if (!Active)
+      return X;
+   const int Stride = 1 << (NLevels - 1);
+   if (K + Stride < NRow) { // 2x2 system (K, K + Stride), row K
+      const int P      = K + Stride;
+      const int Kms    = K - Stride;
+      const Real Gkms  = Kms < 0 ? 0 : W[0 * Span + Kms];
+      const Real Dk    = H + Gkms + G;
+      const Real Dkps  = W[1 * Span + P] + G + W[0 * Span + P];
+      const Real DUk   = -G;
+      const Real DLkps = -G;
+      const Real Det   = Dk * Dkps - DLkps * DUk;
+      const Real Xk    = X;
+      const Real Xkps  = W[2 * Span + P];
+      return (Dkps * Xk - DUk * Xkps) / Det;
+   }
+   if (K - Stride >= 0) { // 2x2 system (K - Stride, K), row K
+      const int P      = K - Stride;
+      const int Kms    = P - Stride;
+      const Real Gp    = W[0 * Span + P];
+      const Real Gkms  = Kms < 0 ? 0 : W[0 * Span + Kms];
+      const Real Dk    = W[1 * Span + P] + Gkms + Gp;
+      const Real Dkps  = H + Gp + G;
+      const Real DUk   = -Gp;
+      const Real DLkps = -Gp;
+      const Real Det   = Dk * Dkps - DLkps * DUk;
+      const Real Xk    = W[2 * Span + P];
+      const Real Xkps  = X;
+      return (-DLkps * Xk + Dk * Xkps) / Det;
+   }
+   const int Kms   = K - Stride; // 1x1 system
+   const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
+   return X / (H + Gkms + G);
+}
+
+/// ThomasSolver::solve(Member, Scratch) (TriDiagSolvers.h:69-93) for one column of NRow rows, by one thread.  Row K of
+/// DL / D / DU is at [K * InStride], of X at [K * XStride] (overwritten with the solution), and `Dw` is a workspace of
+/// NRow doubles at [K * WStride] that takes the eliminated diagonal (the reference's scratch copy of D).
+__device__ inline void thomasSolveColumn(int NRow, const Real *DL, const Real *D, const Real *DU, int InStride,
+                                         Real *X, int XStride, Real *Dw, int WStride) {
+   Real Dp = D[0], Xp = X[0];
+   Dw[0] = Dp;
+   for (int K = 1; K < NRow; ++K) {
+      const Real W = DL[K * InStride] / Dp;
+      Dp           = D[K * InStride] - W * DU[(K - 1) * InStride];
+      Xp           = X[K * XStride] - W * Xp;
+      Dw[K * WStride] = Dp;
+      X[K * XStride]  = Xp;
+   }
+   Xp = Xp / Dp;
+   X[(NRow - 1) * XStride] = Xp;
+   for (int K = NRow - 2; K >= 0; --K) {
+      Xp             = (X[K * XStride] - DU[K * InStride] * Xp) / Dw[K * WStride];
+      X[K * XStride] = Xp;
+   }
+}
+
+/// ThomasDiffusionSolver::solve(Member, Scratch) (TriDiagSolvers.h:276-320) for one column, as thomasSolveColumn;
+/// `Hw` takes the eliminated diagonal (the reference's in-place H).  The reference's Alpha array is carried as one
+/// running value: its loop over K only reads the original G and H.
+__device__ inline void thomasDiffSolveColumn(int NRow, const Real *G, const Real *H, int InStride, Real *X,
+                                             int XStride, Real *Hw, int WStride) {
+   Real Alpha = 0;
+   Real Hp    = H[0] + G[0];
+   Real Xp    = X[0];
+   Hw[0]      = Hp;
+   for (int K = 1; K < NRow; ++K) {
+      const Real Gm = G[(K - 1) * InStride], Hm = H[(K - 1) * InStride];
+      Alpha           = Gm * (Hm + Alpha) / (Hm + Alpha + Gm);
+      const Real AddH = Alpha + G[K * InStride];
+      Xp              = X[K * XStride] + Gm / Hp * Xp;
+      Hp              = H[K * InStride] + AddH;
+      Hw[K * WStride] = Hp;
+      X[K * XStride]  = Xp;
+   }
+   Xp = Xp / Hp;
+   X[(NRow - 1) * XStride] = Xp;
+   for (int K = NRow - 2; K >= 0; --K) {
+      Xp             = (X[K * XStride] + G[K * InStride] * Xp) / Hw[K * WStride];
+      X[K * XStride] = Xp;
+   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// array launchers (kernels/TriDiagKernels.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+
+/// One batched solve of NBatch systems of NRow rows (1 <= NRow <= TriDiagMaxRows).  Row I of each array starts at
+/// Ptr + I * Pitch.  General form: A = DL, B = D, C = DU; diffusion form: A = G, B = H, C unused.
+struct TriDiagArgs {
+   int NBatch = 0, NRow = 0;
+   const Real *A = nullptr, *B = nullptr, *C = nullptr;
+   int PitchA = 0, PitchB = 0, PitchC = 0;
+   Real *X    = nullptr;
+   int PitchX = 0;
+};
+
+enum class TriDiagAlgo { Thomas, PCR, ThomasDiffusion, PCRDiffusion };
+
+/// Asynchronous on stream S; writes X[0:NBatch][0:NRow] only and allocates nothing.
+void launchTriDiag(TriDiagAlgo Algo, const TriDiagArgs &A, hipStream_t S);
+
+} // namespace OMEGA
+#endif

@@ -1,0 +1,208 @@
+"""The batched tridiagonal solvers on the GPU (omega_amd/csrc/TriDiagSolvers.h): all four equal the NumPy restatement
+(tests/tridiag_reference.py) bit for bit, write exactly X[0:NBatch][0:NRow] of NaN-filled pitched arrays and leave
+the coefficients unchanged, refuse sizes outside 1 <= NRow <= 1024, allocate nothing per call, agree across streams,
+and pass the reference's own unit test (TriDiagSolversTest.cpp) with every solve on the device."""
+import math
+
+import numpy as np
+import pytest
+
+import omega_amd as oa
+from tests import tridiag_reference as R
+
+pytestmark = pytest.mark.gpu
+
+SOLVERS = [("general", "pcr"), ("general", "thomas"), ("diffusion", "pcr"), ("diffusion", "thomas")]
+NROWS = (1, 2, 3, 4, 5, 16, 17, 60, 63, 64, 65, 80, 100, 128, 129, 200, 1024)
+NBATCHES = (1, 3, 130)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _device():
+    oa.device_init(0)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _system(form, nb, n, seed, edges):
+    """A random well-posed system; edges=True puts non-zero values in DL[:,0], DU[:,-1] (general) or G[:,-1]
+    (diffusion), where the reference assumes zeros"""
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-1.0, 1.0, (nb, n))
+    if form == "general":
+        dl, du = rng.uniform(-1.0, 1.0, (nb, n)), rng.uniform(-1.0, 1.0, (nb, n))
+        if not edges:
+            dl[:, 0], du[:, -1] = 0.0, 0.0
+        d = rng.uniform(3.0, 4.0, (nb, n)) * np.where(rng.random((nb, n)) < 0.5, -1.0, 1.0)
+        return (dl, d, du), x
+    g, h = rng.uniform(0.0, 2.0, (nb, n)), rng.uniform(0.5, 1.5, (nb, n))
+    g[:, 0] *= 1.0e3  # a strongly mixed interface
+    if not edges:
+        g[:, -1] = 0.0
+    return (g, h), x
+
+
+def _restated(form, algo, coeffs, x):
+    return (R.GENERAL if form == "general" else R.DIFFUSION)[algo](*coeffs, x)
+
+
+def _solve(form, algo, coeffs, x, **kw):
+    f = oa.tridiag_solve if form == "general" else oa.tridiag_diff_solve
+    return f(*coeffs, x, algorithm=algo, **kw)
+
+
+@pytest.mark.parametrize("form,algo", SOLVERS)
+@pytest.mark.parametrize("n", NROWS)
+def test_bit_for_bit_against_the_restatement(form, algo, n):
+    for nb in NBATCHES:
+        for edges in (False, True):
+            coeffs, x = _system(form, nb, n, seed=1000 * n + nb + (7 if edges else 0), edges=edges)
+            got = _solve(form, algo, coeffs, x)
+            want = _restated(form, algo, coeffs, x)
+            assert np.array_equal(_bits(got), _bits(want)), (form, algo, n, nb, edges)
+
+
+class Pitched:
+    """[nb + 1][pitch] device copies of [nb][n] arrays; the pad columns and the extra trailing row hold NaN"""
+
+    def __init__(self, arrays, nb, n, pitch):
+        self.nb, self.n, self.pitch = nb, n, pitch
+        self.host, self.bufs = [], []
+        for a in arrays:
+            p = np.full((nb + 1, pitch), np.nan)
+            p[:nb, :n] = a
+            self.host.append(p)
+            self.bufs.append(oa.DeviceBuffer(p))
+
+    def ptrs(self):
+        return [b.ptr for b in self.bufs]
+
+
+@pytest.mark.parametrize("form,algo", SOLVERS)
+@pytest.mark.parametrize("n,pitch", [(1, 3), (17, 20), (60, 64), (80, 81), (200, 208), (1024, 1030)])
+def test_writes_exactly_the_contract(form, algo, n, pitch):
+    nb = 37
+    coeffs, x = _system(form, nb, n, seed=n, edges=True)
+    P = Pitched([*coeffs, x], nb, n, pitch)
+    *cp, xp = P.ptrs()
+    _solve(form, algo, cp, xp, nbatch=nb, nrow=n, row_pitch=pitch)
+    oa.device_synchronize()
+    out = [b.to_host() for b in P.bufs]
+    for before, after in zip(P.host[:-1], out[:-1]):  # coefficients bit for bit unchanged, pads included
+        assert np.array_equal(_bits(before), _bits(after))
+    xo = out[-1]
+    assert np.isnan(xo[:nb, n:]).all() and np.isnan(xo[nb]).all()
+    assert np.array_equal(_bits(xo[:nb, :n]), _bits(_restated(form, algo, coeffs, x)))
+
+
+@pytest.mark.parametrize("form,algo", SOLVERS)
+def test_limits(form, algo):
+    coeffs, x = _system(form, 2, 1025, seed=1, edges=False)
+    with pytest.raises(oa.OmegaAmdError, match="1024"):
+        _solve(form, algo, coeffs, x)
+    buf = oa.DeviceBuffer(np.zeros(4 * 2048))
+    ptrs = [buf.ptr] * (3 if form == "general" else 2)
+    for bad in (0, -1, 1025):
+        with pytest.raises(oa.OmegaAmdError, match="1 <= NRow <= 1024"):
+            _solve(form, algo, ptrs, buf.ptr, nbatch=1, nrow=bad)
+    with pytest.raises(oa.OmegaAmdError, match="pitch"):
+        _solve(form, algo, ptrs, buf.ptr, nbatch=2, nrow=8, row_pitch=4)
+    coeffs, x = _system(form, 3, 8, seed=2, edges=False)
+    with pytest.raises(oa.OmegaAmdError, match="shape"):
+        _solve(form, algo, coeffs, x[:, :7])
+    with pytest.raises(ValueError):
+        _solve(form, "lu", coeffs, x)
+
+
+@pytest.mark.parametrize("form,algo", SOLVERS)
+def test_no_allocation_and_streams(form, algo):
+    nb, n, pitch = 300, 60, 64
+    coeffs, x = _system(form, nb, n, seed=5, edges=False)
+    stream = oa.Stream()
+    A = Pitched([*coeffs, x], nb, n, pitch)
+    B = Pitched([*coeffs, x], nb, n, pitch)
+    *ca, xa = A.ptrs()
+    *cb, xb = B.ptrs()
+    before = oa.device_resource_count()
+    for _ in range(3):  # repeated solves iterate the same arrays: every call launches, none allocates
+        _solve(form, algo, ca, xa, nbatch=nb, nrow=n, row_pitch=pitch)
+        _solve(form, algo, cb, xb, nbatch=nb, nrow=n, row_pitch=pitch, stream=stream)
+    stream.synchronize()
+    oa.device_synchronize()
+    assert oa.device_resource_count() == before
+    ra, rb = A.bufs[-1].to_host(), B.bufs[-1].to_host()
+    assert np.array_equal(_bits(ra), _bits(rb))
+    want = x
+    for _ in range(3):
+        want = _restated(form, algo, coeffs, want)
+    assert np.array_equal(_bits(ra[:nb, :n]), _bits(want))
+
+
+@pytest.mark.parametrize("algo", ["pcr", "thomas"])
+def test_qu30_size_diffusion_bit_exact(algo):
+    """462 400 systems x K = 60 in level arrays of pitch 64, the diffusion form"""
+    nb, n, pitch = 462400, 60, 64
+    (g, h), x = _system("diffusion", nb, n, seed=30, edges=False)
+    P = Pitched([g, h, x], nb, n, pitch)
+    gp, hp, xp = P.ptrs()
+    oa.tridiag_diff_solve(gp, hp, xp, algorithm=algo, nbatch=nb, nrow=n, row_pitch=pitch)
+    oa.device_synchronize()
+    xo = P.bufs[-1].to_host()
+    assert np.isnan(xo[:nb, n:]).all() and np.isnan(xo[nb]).all()
+    assert np.array_equal(_bits(xo[:nb, :n]), _bits(_restated("diffusion", algo, (g, h), x)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reference's unit test (TriDiagSolversTest.cpp), assembled on the host, every solve on the device
+# ---------------------------------------------------------------------------------------------------------------------
+
+class DeviceRows:
+    """A solve on [1][n] systems through fixed device buffers: one copy in, one solve, one copy out per call"""
+
+    def __init__(self, form, algo, ncoef, n):
+        self.form, self.algo, self.n = form, algo, n
+        self.bufs = [oa.DeviceBuffer(np.zeros((1, n))) for _ in range(ncoef + 1)]
+
+    def __call__(self, *arrays):
+        for b, a in zip(self.bufs, arrays):
+            oa.copy_to_device(b.ptr, a)
+        *c, x = [b.ptr for b in self.bufs]
+        _solve(self.form, self.algo, c, x, nbatch=1, nrow=self.n)
+        return self.bufs[-1].to_host()
+
+
+@pytest.mark.parametrize("algo", ["pcr", "thomas"])
+def test_reference_correctness_sweep_on_device(algo):
+    for nb in (1, 2, 4, 5, 11, 33, 102):
+        for n in (3, 4, 5, 6, 11, 17, 64, 100):
+            dl, d, du, x, ax = R.correctness_system(nb, n)
+            y = oa.tridiag_solve(dl, d, du, ax, algorithm=algo)
+            assert np.max(np.abs(y - x)) <= 1e-12, (nb, n)
+            assert np.array_equal(_bits(y), _bits(R.GENERAL[algo](dl, d, du, ax)))
+            g, h, x, ax = R.diffusion_correctness_system(nb, n)
+            y = oa.tridiag_diff_solve(g, h, ax, algorithm=algo)
+            assert np.max(np.abs(y - x)) <= 1e-12, (nb, n)
+            assert np.array_equal(_bits(y), _bits(R.DIFFUSION[algo](g, h, ax)))
+
+
+@pytest.mark.parametrize("algo", ["pcr", "thomas"])
+def test_reference_manufactured_solution_on_device(algo):
+    e = {}
+    for n in (100, 200):
+        e[n] = R.diff_manufactured(n, DeviceRows("diffusion", algo, 2, n))
+        assert e[n] == R.diff_manufactured(n, R.DIFFUSION[algo])  # bit for bit through every step
+    rate = math.log2(e[100] / e[200])
+    assert abs(rate - 2) <= 0.1, rate
+    assert e[200] <= 2e-5, e[200]
+
+
+@pytest.mark.parametrize("algo", ["pcr", "thomas"])
+def test_reference_stability_on_device(algo):
+    gen, dif = DeviceRows("general", algo, 3, 100), DeviceRows("diffusion", algo, 2, 100)
+    small_g = R.diffusion_stability(True, 1e2, gen)
+    small_d = R.diffusion_stability(False, 1e2, dif)
+    assert R.is_approx(small_g, small_d, 1e-3), (small_g, small_d)
+    assert math.isnan(R.diffusion_stability(True, 1e14, gen))
+    assert not math.isnan(R.diffusion_stability(False, 1e14, dif))
