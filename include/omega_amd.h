@@ -37,6 +37,7 @@ typedef struct omg_tend omg_tend;       /* O/src/ocn/Tendencies.h               
 typedef struct omg_stepper omg_stepper; /* O/src/timeStepping/TimeStepper.h          */
 typedef struct omg_vcoord omg_vcoord;   /* O/src/ocn/VertCoord.h class VertCoord     */
 typedef struct omg_eos omg_eos;         /* O/src/ocn/Eos.h       class Eos           */
+typedef struct omg_vertmix omg_vertmix; /* O/doc/design/VerticalMixingCoeff.md (design only) */
 
 enum { OMG_ON_CELL = 0, OMG_ON_EDGE = 1, OMG_ON_VERTEX = 2 }; /* O/src/base/Halo.h:45 MeshElement */
 
@@ -508,6 +509,46 @@ int omg_eos_compute_spec_vol_disp(omg_eos *e, const double *conserv_temp_dev, co
 int omg_eos_copy_to_host(const omg_eos *e, const char *name, double *host, size_t n);
 int omg_eos_copy_to_device(omg_eos *e, const char *name, const double *host, size_t n);
 int omg_eos_device_ptr(const omg_eos *e, const char *name, double **dev, size_t *n);
+
+/* ---- VertMix: vertical mixing coefficients and implicit vertical diffusion.  The reference specifies it in
+ * O/doc/design/VerticalMixingCoeff.md only (no code yet).  Numerical contract and the stated deviations (N2 form,
+ * Ri >= 0 clamp, integer exponents): omega_amd/csrc/VertMix.h.  Arrays are level-indexed device arrays as above;
+ * edge arrays are [NEdgesSize][omg_level_pitch(K)].  Every call is asynchronous on stream and allocates nothing. ---- */
+/* VerticalMixingCoeff.md section 4.1.1: the configuration, with its defaults */
+typedef struct omg_vertmix_config {
+   double BackgroundViscosity;   /* 1.0e-4 */
+   double BackgroundDiffusivity; /* 1.0e-5 */
+   int32_t EnableShearMix;       /* 1 */
+   double ShearNuZero;           /* 0.005 */
+   double ShearAlpha;            /* 5 */
+   double ShearExponent;         /* 2 */
+   int32_t EnableConvectiveMix;  /* 1 */
+   double ConvectiveDiffusivity; /* 1.0 */
+   double ConvectiveTriggerBVF;  /* 0.0 */
+} omg_vertmix_config;
+int omg_vertmix_config_default(omg_vertmix_config *c);
+/* VerticalMixingCoeff.md section 4.1 (construction): fails for negative viscosities or diffusivities, more than 1024
+ * layers (the tridiagonal limit), a host-only mesh, or a VertCoord of another mesh.  c NULL: the defaults. */
+int omg_vertmix_create(const omg_mesh *m, const omg_vcoord *v, const omg_vertmix_config *c, omg_vertmix **out);
+int omg_vertmix_destroy(omg_vertmix *x);
+/* VerticalMixingCoeff.md section 4.2 (Brunt-Vaisala frequency, here on VertMix): BruntVaisalaFreqSq from e's SpecVol
+ * and SpecVolDisplaced (after omg_vcoord_compute_column with displaced = 1, kdisp = 1) and the VertCoord's ZMid */
+int omg_vertmix_compute_bvf(omg_vertmix *x, const omg_eos *e, void *stream);
+/* VerticalMixingCoeff.md section 4.2 (background, shear and convective coefficients): VertVisc and VertDiff from the
+ * edge velocities and bvf_dev (NULL: the object's own BruntVaisalaFreqSq) */
+int omg_vertmix_compute(omg_vertmix *x, const double *normal_velocity_dev, const double *tangential_velocity_dev,
+                        const double *bvf_dev, void *stream);
+/* VerticalMixingCoeff.md section 4.3 (coefficients feeding TriDiagDiffSolver, no-flux boundaries): backward-Euler
+ * diffusion with VertDiff of tracers_dev [ntracers][NCellsSize][pitch] in place, all tracers in one pass */
+int omg_vertmix_apply_tracers(omg_vertmix *x, const double *layer_thickness_dev, double *tracers_dev, int ntracers,
+                              double dt, void *stream);
+/* VerticalMixingCoeff.md section 4.3: backward-Euler diffusion with VertVisc of the normal velocity in place */
+int omg_vertmix_apply_velocity(omg_vertmix *x, const double *layer_thickness_dev, double *normal_velocity_dev,
+                               double dt, void *stream);
+/* "VertDiff", "VertVisc", "BruntVaisalaFreqSq" ([NCellsSize][K]) */
+int omg_vertmix_copy_to_host(const omg_vertmix *x, const char *name, double *host, size_t n);
+int omg_vertmix_copy_to_device(omg_vertmix *x, const char *name, const double *host, size_t n);
+int omg_vertmix_device_ptr(const omg_vertmix *x, const char *name, double **dev, size_t *n);
 
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at

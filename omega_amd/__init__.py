@@ -1116,6 +1116,109 @@ class VertCoord:
             pass
 
 
+class VertMixConfig(C.Structure):
+    """omg_vertmix_config (VerticalMixingCoeff.md section 4.1.1)"""
+    _fields_ = [("BackgroundViscosity", C.c_double), ("BackgroundDiffusivity", C.c_double),
+                ("EnableShearMix", C.c_int32), ("ShearNuZero", C.c_double), ("ShearAlpha", C.c_double),
+                ("ShearExponent", C.c_double), ("EnableConvectiveMix", C.c_int32),
+                ("ConvectiveDiffusivity", C.c_double), ("ConvectiveTriggerBVF", C.c_double)]
+
+
+def vertmix_config(**over) -> VertMixConfig:
+    """The defaults (omg_vertmix_config_default) with the given fields replaced; an unknown field raises KeyError."""
+    c = VertMixConfig()
+    _chk(lib().omg_vertmix_config_default(C.byref(c)))
+    names = {f[0] for f in VertMixConfig._fields_}
+    for k, v in over.items():
+        if k not in names:
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
+class VertMix:
+    """VertMix (omega_amd/csrc/VertMix.h): N^2, mixing coefficients and the implicit vertical diffusion of tracers and
+    normal velocity.  `config` fields as in VertMixConfig (e.g. ShearExponent=3.0, EnableConvectiveMix=False).
+    Level-indexed inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles; the in-place
+    solves take a device address (solved asynchronously on `stream`) or a numpy array (staged, solved, returned)."""
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", **config):
+        self.mesh, self.vcoord = mesh, vcoord
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self.config = vertmix_config(**config)
+        h = C.c_void_p()
+        _chk(lib().omg_vertmix_create(mesh.h, vcoord.h if vcoord is not None else None, C.byref(self.config),
+                                      C.byref(h)))
+        self.h = h
+
+    def compute_bvf(self, eos: Eos, stream=None):
+        _chk(lib().omg_vertmix_compute_bvf(self.h, eos.h, _sh(stream)))
+
+    def compute(self, normal_velocity, tangential_velocity, bvf=None, stream=None):
+        """VertVisc, VertDiff from the edge velocities and N^2 (bvf None: this object's BruntVaisalaFreqSq)"""
+        keep, ne, nc = [], self.mesh.NEdgesSize, self.mesh.NCellsSize
+        _chk(lib().omg_vertmix_compute(self.h, _level_dev(normal_velocity, ne, self.K, keep),
+                                       _level_dev(tangential_velocity, ne, self.K, keep),
+                                       None if bvf is None else _level_dev(bvf, nc, self.K, keep), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def _in_place(self, x, rows_shape):
+        """(device pointer, staged buffer or None) for an in-place array"""
+        if isinstance(x, (int, np.integer)):
+            return C.c_void_p(int(x)), None
+        a = np.asarray(x, dtype=np.float64)
+        assert a.shape == rows_shape + (self.K,), f"expected shape {rows_shape + (self.K,)}, got {a.shape}"
+        pad = np.zeros(rows_shape + (level_pitch(self.K),))
+        pad[..., : self.K] = a
+        b = DeviceBuffer(pad)
+        return C.c_void_p(b.ptr), b
+
+    def _back(self, buf, stream):
+        if buf is None:
+            return None
+        if stream is not None:
+            stream.synchronize()
+        device_synchronize()
+        return buf.to_host()[..., : self.K]
+
+    def apply_tracers(self, layer_thickness, tracers, ntracers: int, dt: float, stream=None):
+        """Backward-Euler diffusion of tracers [ntracers][NCellsSize][K] with VertDiff, all in one pass"""
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        p, buf = self._in_place(tracers, (int(ntracers), n))
+        _chk(lib().omg_vertmix_apply_tracers(self.h, h, p, int(ntracers), C.c_double(dt), _sh(stream)))
+        return self._back(buf, stream)
+
+    def apply_velocity(self, layer_thickness, normal_velocity, dt: float, stream=None):
+        """Backward-Euler diffusion of the normal velocity [NEdgesSize][K] with VertVisc averaged to the edges"""
+        keep = []
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        p, buf = self._in_place(normal_velocity, (self.mesh.NEdgesSize,))
+        _chk(lib().omg_vertmix_apply_velocity(self.h, h, p, C.c_double(dt), _sh(stream)))
+        return self._back(buf, stream)
+
+    def get(self, name: str) -> np.ndarray:
+        out = np.zeros((self.mesh.NCellsSize, self.K))
+        _chk(lib().omg_vertmix_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
+        return out
+
+    def set(self, name: str, values: np.ndarray):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        _chk(lib().omg_vertmix_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
+
+    def device_ptr(self, name: str) -> int:
+        p = PD()
+        _chk(lib().omg_vertmix_device_ptr(self.h, name.encode(), C.byref(p), None))
+        return C.cast(p, C.c_void_p).value
+
+    def __del__(self):
+        try:
+            lib().omg_vertmix_destroy(self.h)
+        except Exception:
+            pass
+
+
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""

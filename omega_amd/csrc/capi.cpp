@@ -20,6 +20,7 @@
 #include "VertCoord.h"
 #include "Eos.h"
 #include "TriDiagSolvers.h"
+#include "VertMix.h"
 
 #include <cstring>
 #include <map>
@@ -66,6 +67,9 @@ struct omg_vcoord {
 };
 struct omg_eos {
    std::unique_ptr<Eos> E;
+};
+struct omg_vertmix {
+   std::unique_ptr<VertMix> X;
 };
 
 static thread_local std::string LastError;
@@ -1637,6 +1641,123 @@ int omg_eos_device_ptr(const omg_eos *e, const char *name, double **dev, size_t 
    OMG_TRY
    OMG_ARG(e && name && dev);
    const ArrRef R = eosLookup(*e->E, name);
+   *dev = R.Ptr;
+   if (n)
+      *n = R.size();
+   OMG_CATCH
+}
+
+// ---- VertMix (VertMix.h)
+static VertMixConfig toVertMixConfig(const omg_vertmix_config &c) {
+   VertMixConfig V;
+   V.BackgroundViscosity   = c.BackgroundViscosity;
+   V.BackgroundDiffusivity = c.BackgroundDiffusivity;
+   V.EnableShearMix        = c.EnableShearMix != 0;
+   V.ShearNuZero           = c.ShearNuZero;
+   V.ShearAlpha            = c.ShearAlpha;
+   V.ShearExponent         = c.ShearExponent;
+   V.EnableConvectiveMix   = c.EnableConvectiveMix != 0;
+   V.ConvectiveDiffusivity = c.ConvectiveDiffusivity;
+   V.ConvectiveTriggerBVF  = c.ConvectiveTriggerBVF;
+   return V;
+}
+int omg_vertmix_config_default(omg_vertmix_config *c) {
+   OMG_TRY
+   OMG_ARG(c);
+   const VertMixConfig V;
+   c->BackgroundViscosity   = V.BackgroundViscosity;
+   c->BackgroundDiffusivity = V.BackgroundDiffusivity;
+   c->EnableShearMix        = V.EnableShearMix;
+   c->ShearNuZero           = V.ShearNuZero;
+   c->ShearAlpha            = V.ShearAlpha;
+   c->ShearExponent         = V.ShearExponent;
+   c->EnableConvectiveMix   = V.EnableConvectiveMix;
+   c->ConvectiveDiffusivity = V.ConvectiveDiffusivity;
+   c->ConvectiveTriggerBVF  = V.ConvectiveTriggerBVF;
+   OMG_CATCH
+}
+int omg_vertmix_create(const omg_mesh *m, const omg_vcoord *v, const omg_vertmix_config *c, omg_vertmix **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   const VertMixConfig Cfg = c ? toVertMixConfig(*c) : VertMixConfig();
+   auto *R = new omg_vertmix;
+   try {
+      R->X.reset(new VertMix("Default", m->M.get(), v ? v->V.get() : nullptr, Cfg));
+   } catch (...) {
+      delete R;
+      throw;
+   }
+   *out = R;
+   OMG_CATCH
+}
+int omg_vertmix_destroy(omg_vertmix *x) {
+   delete x;
+   return 0;
+}
+int omg_vertmix_compute_bvf(omg_vertmix *x, const omg_eos *e, void *stream) {
+   OMG_TRY
+   OMG_ARG(x && e);
+   x->X->computeBruntVaisalaFreqSq(*e->E, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertmix_compute(omg_vertmix *x, const double *normal_velocity, const double *tangential_velocity,
+                        const double *bvf, void *stream) {
+   OMG_TRY
+   OMG_ARG(x && normal_velocity && tangential_velocity);
+   const HorzMesh *M = x->X->Mesh;
+   const int K       = x->X->NVertLayers;
+   x->X->computeVertMix(levelView(normal_velocity, M->NEdgesSize, K), levelView(tangential_velocity, M->NEdgesSize, K),
+                        bvf ? levelView(bvf, M->NCellsSize, K) : x->X->BruntVaisalaFreqSq, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertmix_apply_tracers(omg_vertmix *x, const double *layer_thickness, double *tracers, int ntracers, double dt,
+                              void *stream) {
+   OMG_TRY
+   OMG_ARG(x && layer_thickness && ntracers >= 0 && (tracers || ntracers == 0));
+   const HorzMesh *M = x->X->Mesh;
+   const int K       = x->X->NVertLayers;
+   Array3DReal Tr;
+   Tr.Ptr    = tracers;
+   Tr.Ext[0] = ntracers, Tr.Ext[1] = M->NCellsSize, Tr.Ext[2] = K;
+   Tr.Pitch  = levelPitch(K);
+   x->X->applyTracerVertMix(levelView(layer_thickness, M->NCellsSize, K), Tr, ntracers, dt, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertmix_apply_velocity(omg_vertmix *x, const double *layer_thickness, double *normal_velocity, double dt,
+                               void *stream) {
+   OMG_TRY
+   OMG_ARG(x && layer_thickness && normal_velocity);
+   const HorzMesh *M = x->X->Mesh;
+   const int K       = x->X->NVertLayers;
+   x->X->applyVelocityVertMix(levelView(layer_thickness, M->NCellsSize, K), levelView(normal_velocity, M->NEdgesSize, K),
+                              dt, (hipStream_t)stream);
+   OMG_CATCH
+}
+static ArrRef vertMixLookup(const VertMix &X, const std::string &Name) {
+   if (Name == "VertDiff")
+      return arrRef(X.VertDiff);
+   if (Name == "VertVisc")
+      return arrRef(X.VertVisc);
+   if (Name == "BruntVaisalaFreqSq")
+      return arrRef(X.BruntVaisalaFreqSq);
+   OMEGA_ABORT("VertMix: no array named " + Name);
+}
+int omg_vertmix_copy_to_host(const omg_vertmix *x, const char *name, double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(x && name && host);
+   refCopyToHost(vertMixLookup(*x->X, name), name, host, n);
+   OMG_CATCH
+}
+int omg_vertmix_copy_to_device(omg_vertmix *x, const char *name, const double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(x && name && host);
+   refCopyToDevice(vertMixLookup(*x->X, name), name, host, n);
+   OMG_CATCH
+}
+int omg_vertmix_device_ptr(const omg_vertmix *x, const char *name, double **dev, size_t *n) {
+   OMG_TRY
+   OMG_ARG(x && name && dev);
+   const ArrRef R = vertMixLookup(*x->X, name);
    *dev = R.Ptr;
    if (n)
       *n = R.size();

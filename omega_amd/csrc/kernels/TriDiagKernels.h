@@ -170,6 +170,151 @@ __device__ inline Real pcrDiffSolveRow(bool Active, int K, int NRow, Real G, Rea
    return X / (H + Gkms + G);
 }
 
+/// Largest PCR level count (pcrLevels(TriDiagMaxRows)): the multi-right-hand-side body keeps one Alpha / Beta per level
+/// in registers, so its level loops have this compile-time bound
+constexpr int TriDiagMaxLevels = 10;
+
+/// pcrDiffSolveRow for NRhs right-hand sides that share G and H (e.g. every tracer of a column): the result for each
+/// right-hand side is bit for bit that of pcrDiffSolveRow on (G, H, X_t).  Everything that depends only on G and H --
+/// Alpha, Beta, NewG, NewH of every level and the final Dk / Dkps / Det -- is computed once; each X_t then goes
+/// through the same levels with the stored Alpha / Beta, Chunk right-hand sides at a time.  LoadX(T) returns X of
+/// right-hand side T of this row and StoreX(T, V) takes its solution (called only when Active).
+///
+/// The systems of one workgroup may have different NRow (columns of different depth): NLevWg is the workgroup-uniform
+/// number of barrier steps, at least pcrLevels(NRow) of every system in it.  A system that has finished its own levels
+/// keeps joining the barriers without touching the workspace.  `Sys` points to row 0 of the thread's system in a
+/// workspace of 2 x 2 arrays (G, H) followed by 2 x Chunk arrays (X) of `Span` doubles each, in LDS.
+template <int Chunk, class LoadX, class StoreX>
+__device__ inline void pcrDiffSolveRowMulti(bool Active, int K, int NRow, int NLevWg, Real G, Real H, int NRhs,
+                                            LoadX Load, StoreX Store, Real *Sys, int Span) {
+   const int NLev = Active ? pcrLevels(NRow) : 0;
+   Real Alpha[TriDiagMaxLevels], Beta[TriDiagMaxLevels];
+   Real *GH = Sys, *XW = Sys + 4 * Span;
+   // ---- G and H: the levels of pcrDiffSolveRow, keeping Alpha and Beta; the last step writes the reduced G, H
+   int B = 0;
+#pragma unroll
+   for (int Lev = 1; Lev <= TriDiagMaxLevels; ++Lev) {
+      if (Lev > NLevWg) // workgroup-uniform: a condition, not a break, so that the loop unrolls
+         continue;
+      Real *W = GH + B * 2 * Span;
+      if (Lev <= NLev) {
+         W[0 * Span + K] = G, W[1 * Span + K] = H;
+      }
+      __syncthreads();
+      if (Lev < NLev) {
+         const int Stride     = 1 << Lev;
+         const int HalfStride = 1 << (Lev - 1);
+
+         int Kmh         = K - HalfStride;
+         const Real Gkmh = Kmh < 0 ? 0 : W[0 * Span + Kmh];
+         Kmh             = Kmh < 0 ? 0 : Kmh;
+
+         const int Kms   = K - Stride;
+         const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
+
+         int Kph = K + HalfStride;
+         Kph     = Kph >= NRow ? NRow - 1 : Kph;
+
+         const Real A  = Gkmh / (W[1 * Span + Kmh] + Gkms + Gkmh);
+         const Real Bt = G / (W[1 * Span + Kph] + G + W[0 * Span + Kph]);
+
+         const Real NewG = W[0 * Span + Kph] * Bt;
+         const Real NewH = H + A * W[1 * Span + Kmh] + Bt * W[1 * Span + Kph];
+         G = NewG, H = NewH;
+         Alpha[Lev - 1] = A, Beta[Lev - 1] = Bt;
+         B ^= 1;
+      }
+   }
+   // ---- the final 2x2 / 1x1 systems: X = (Ca * X - Cb * Xpartner) / Det, or X / Det without a partner (Cb unused)
+   int Partner = -1;
+   Real Ca = 1, Cb = 0, Det = 1;
+   if (Active) {
+      const Real *W = GH + B * 2 * Span;
+      if (NRow == 1) { // the reference's 1 << -1; defined as the 1x1 solve (TriDiagSolvers.h)
+         Det = H + G;
+      } else {
+         const int Stride = 1 << (NLev - 1);
+         if (K + Stride < NRow) { // 2x2 system (K, K + Stride), row K: (Dkps * Xk - DUk * Xkps) / Det
+            const int P      = K + Stride;
+            const int Kms    = K - Stride;
+            const Real Gkms  = Kms < 0 ? 0 : W[0 * Span + Kms];
+            const Real Dk    = H + Gkms + G;
+            const Real Dkps  = W[1 * Span + P] + G + W[0 * Span + P];
+            const Real DUk   = -G;
+            const Real DLkps = -G;
+            Det              = Dk * Dkps - DLkps * DUk;
+            Partner = P, Ca = Dkps, Cb = DUk;
+         } else if (K - Stride >= 0) { // 2x2 system (K - Stride, K), row K: (-DLkps * Xk + Dk * Xkps) / Det
+            const int P      = K - Stride;
+            const int Kms    = P - Stride;
+            const Real Gp    = W[0 * Span + P];
+            const Real Gkms  = Kms < 0 ? 0 : W[0 * Span + Kms];
+            const Real Dk    = W[1 * Span + P] + Gkms + Gp;
+            const Real Dkps  = H + Gp + G;
+            const Real DUk   = -Gp;
+            const Real DLkps = -Gp;
+            Det              = Dk * Dkps - DLkps * DUk;
+            Partner = P, Ca = -DLkps, Cb = Dk; // kept in the reference's order below: Ca * Xpartner + Cb * X
+         } else { // 1x1 system
+            const int Kms   = K - Stride;
+            const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
+            Det             = H + Gkms + G;
+         }
+      }
+   }
+   const bool Upper = Partner > K; // which of the two 2x2 expressions this row evaluates
+   // ---- every right-hand side through the stored levels
+   for (int T0 = 0; T0 < NRhs; T0 += Chunk) {
+      if (T0 > 0)
+         __syncthreads(); // the previous chunk's final step read the workspace
+      Real X[Chunk];
+#pragma unroll
+      for (int J = 0; J < Chunk; ++J)
+         X[J] = (Active && T0 + J < NRhs) ? Load(T0 + J) : 0;
+      int Bx = 0;
+#pragma unroll
+      for (int Lev = 1; Lev <= TriDiagMaxLevels; ++Lev) {
+         if (Lev > NLevWg)
+            continue;
+         Real *W = XW + Bx * Chunk * Span;
+         if (Lev <= NLev) {
+#pragma unroll
+            for (int J = 0; J < Chunk; ++J)
+               W[J * Span + K] = X[J];
+         }
+         __syncthreads();
+         if (Lev < NLev) {
+            const int HalfStride = 1 << (Lev - 1);
+            int Kmh              = K - HalfStride;
+            Kmh                  = Kmh < 0 ? 0 : Kmh;
+            int Kph              = K + HalfStride;
+            Kph                  = Kph >= NRow ? NRow - 1 : Kph;
+            const Real A = Alpha[Lev - 1], Bt = Beta[Lev - 1];
+#pragma unroll
+            for (int J = 0; J < Chunk; ++J)
+               X[J] = X[J] + A * W[J * Span + Kmh] + Bt * W[J * Span + Kph];
+            Bx ^= 1;
+         }
+      }
+      if (Active) {
+         const Real *W = XW + Bx * Chunk * Span;
+#pragma unroll
+         for (int J = 0; J < Chunk; ++J) {
+            if (T0 + J >= NRhs)
+               break;
+            Real V;
+            if (Partner < 0)
+               V = X[J] / Det;
+            else if (Upper)
+               V = (Ca * X[J] - Cb * W[J * Span + Partner]) / Det;
+            else
+               V = (Ca * W[J * Span + Partner] + Cb * X[J]) / Det;
+            Store(T0 + J, V);
+         }
+      }
+   }
+}
+
 /// ThomasSolver::solve(Member, Scratch) (TriDiagSolvers.h:69-93) for one column of NRow rows, by one thread.  Row K of
 /// DL / D / DU is at [K * InStride], of X at [K * XStride] (overwritten with the solution), and `Dw` is a workspace of
 /// NRow doubles at [K * WStride] that takes the eliminated diagonal (the reference's scratch copy of D).
