@@ -1,0 +1,345 @@
+"""The NumPy restatements the GPU is compared with (tests/column_reference.py, tests/vert_mix_reference.py,
+tests/tridiag_reference.py) anchored on something they were not written from: the TEOS-10 polynomial as the expanded
+sum of monomials in 50-digit arithmetic, its coefficients read by name from the kernel source and (where a checkout of
+the reference model lies beside this repository, or OMEGA_REFERENCE_ROOT names one) from the reference's Eos.h, the
+column formulas as exact rational sums, and the diffusion solves against a 50-digit Thomas elimination.
+
+u = 2^-53 is the unit roundoff, so one FP64 operation has a relative error of at most u."""
+import os
+import re
+from fractions import Fraction as Fr
+
+import mpmath
+import numpy as np
+import pytest
+
+from tests import column_reference as CR
+from tests import tridiag_reference as TR
+from tests import vert_mix_reference as MR
+
+U = 2.0 ** -53
+RHO0 = 1026.0
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REFERENCE = os.environ.get("OMEGA_REFERENCE_ROOT", os.path.join(os.path.dirname(ROOT), "reference"))
+REFERENCE_EOS = os.path.join(REFERENCE, "components", "omega", "src", "ocn", "Eos.h")
+KERNEL = os.path.join(ROOT, "omega_amd", "csrc", "kernels", "ColumnKernels.hip")
+K_NEW = [1, 2, 3, 5, 17, 257, 1024]
+
+
+# ---- TEOS-10
+def _teos10_expanded(ct, sa, p):
+    """sum V_ijk ss^i tt^j pp^k + sum V0_k pp^(k+1), every monomial on its own, in 50 digits"""
+    mp = mpmath.mp
+    sau = mp.mpf(40) * mp.mpf("35.16504") / mp.mpf(35)
+    ss = mp.sqrt((mp.mpf(float(sa)) + 24) / sau)
+    tt = mp.mpf(float(ct)) / 40
+    pp = mp.mpf(float(p)) / 10000
+    v = mp.mpf(0)
+    for (i, j, k), c in CR._V.items():
+        v += mp.mpf(c) * ss ** i * tt ** j * pp ** k
+    for k, c in enumerate(CR._V0):
+        v += mp.mpf(c) * pp ** (k + 1)
+    return v
+
+
+def test_teos10_nested_form_equals_the_expanded_polynomial():
+    """The nested form of spec_vol_teos10 against the expanded sum: 1e-15 relative (the polynomial is dominated by
+    V000, so the nested evaluation is a few u off; measured 3.4e-16 over this grid).  A coefficient in the wrong place
+    of the nesting moves the value by its own size, 1e-9 relative and more."""
+    rng = np.random.default_rng(2015)
+    pts = [(ct, sa, p) for ct in (-2.0, 40.0) for sa in (0.0, 42.0) for p in (0.0, 11000.0)]
+    pts += [(10.0, 30.0, 1000.0)]
+    pts += list(zip(rng.uniform(-2.0, 40.0, 400), rng.uniform(0.0, 42.0, 400), rng.uniform(0.0, 11000.0, 400)))
+    worst = 0.0
+    with mpmath.workdps(50):
+        for ct, sa, p in pts:
+            got = CR.spec_vol_teos10(np.float64(ct), np.float64(sa), np.float64(p))
+            want = _teos10_expanded(ct, sa, p)
+            worst = max(worst, float(abs(mpmath.mpf(float(got)) - want) / abs(want)))
+    print(f"TEOS-10 nested vs expanded: worst relative difference {worst:.3e}")
+    assert worst <= 1.0e-15
+    assert len(CR._V) + len(CR._V0) == 80
+
+
+_LITERAL = re.compile(r"\b(V\d{2,3})\s*=\s*([-+]?\d+\.\d+e[-+]?\d+)\s*[,;]")
+
+
+def _named_literals(path):
+    with open(path) as f:
+        text = f.read()
+    found = {}
+    for name, lit in _LITERAL.findall(text):
+        assert found.setdefault(name, float(lit)) == float(lit), f"{name} is defined twice with different values"
+    return found
+
+
+def _table():
+    t = {f"V{i}{j}{k}": v for (i, j, k), v in CR._V.items()}
+    t.update({f"V0{k}": v for k, v in enumerate(CR._V0)})
+    return t
+
+
+def _compare_with_table(found, where):
+    table = _table()
+    assert sorted(set(table) - set(found)) == [], f"names missing in {where}"
+    assert sorted(set(found) - set(table)) == [], f"names of {where} missing in column_reference"
+    wrong = {n: (found[n], table[n]) for n in table if found[n] != table[n]}
+    assert not wrong, f"{where} differs from column_reference: {wrong}"
+
+
+def test_teos10_coefficients_equal_the_kernel_literals():
+    _compare_with_table(_named_literals(KERNEL), "ColumnKernels.hip")
+
+
+def test_teos10_coefficients_equal_the_reference_header():
+    """reads the numeric literals of the reference's Eos.h by name; nothing of the header is kept here"""
+    if not os.path.exists(REFERENCE_EOS):
+        pytest.skip(f"no reference checkout at {REFERENCE} (set OMEGA_REFERENCE_ROOT)")
+    _compare_with_table(_named_literals(REFERENCE_EOS), "the reference's Eos.h")
+
+
+# ---- the column formulas as exact rational sums
+def _column(K, seed):
+    rng = np.random.default_rng(seed)
+    n = 5
+    lo = np.array([0, 0, K // 2, K - 1, min(1, K - 1), -1], np.int32)
+    hi = np.array([K - 1, min(2, K - 1), K - 1, K - 1, min(3, K - 1), -1], np.int32)
+    return dict(n=n, lo=lo, hi=hi, h=rng.uniform(0.5, 40.0, (n + 1, K)), ps=rng.uniform(0.9e5, 1.1e5, n + 1),
+                sv=rng.uniform(9.6e-4, 9.9e-4, (n + 1, K)), bot=rng.uniform(100.0, 6000.0, n + 1),
+                tidal=rng.uniform(-1.0, 1.0, n + 1), sal=rng.uniform(-0.1, 0.1, n + 1))
+
+
+def _rel(got, want):
+    return abs(Fr(float(got)) - want) / abs(want)
+
+
+def test_linear_eos_against_the_exact_quotient():
+    """1 / (RhoT0S0 + (dRhodT Ct + dRhodS Sa)): five operations, the sum dominated by RhoT0S0 = 1000, so the quotient
+    is within 4 u of the exact one."""
+    rng = np.random.default_rng(1)
+    for ct, sa in zip(rng.uniform(-2.0, 40.0, 200), rng.uniform(0.0, 42.0, 200)):
+        want = 1 / (Fr(1000.0) + (Fr(-0.2) * Fr(ct) + Fr(0.8) * Fr(sa)))
+        assert _rel(CR.spec_vol_linear(ct, sa), want) <= 4 * U
+
+
+@pytest.mark.parametrize("K", K_NEW)
+def test_pressure_against_exact_prefix_sums(K):
+    """PInt[k+1] = Ps + g Rho0 sum_{j<=k} h_j: n + 3 operations on terms of one sign, relative error at most
+    (n + 3) u (1 + O(n u)); PMid = PInt[k+1] - g Rho0 h_k / 2 lies above PInt[k+1] / 2, which doubles the bound."""
+    c = _column(K, 20 + K)
+    pint, pmid = np.full((c["n"] + 1, K + 1), np.nan), np.full((c["n"] + 1, K), np.nan)
+    CR.pressure(c["h"], c["ps"], c["lo"], c["hi"], c["n"], RHO0, pint, pmid)
+    grho = Fr(CR.GRAVITY) * Fr(RHO0)
+    worst = 0.0
+    for i in range(c["n"]):
+        lo, hi = int(c["lo"][i]), int(c["hi"][i])
+        acc = Fr(float(c["ps"][i]))
+        assert pint[i, lo] == c["ps"][i]
+        for k in range(lo, hi + 1):
+            inc = grho * Fr(float(c["h"][i, k]))
+            acc += inc
+            n = k - lo + 1
+            e1, e2 = _rel(pint[i, k + 1], acc), _rel(pmid[i, k], acc - inc / 2)
+            worst = max(worst, float(e1) / ((n + 3) * U))
+            assert e1 <= (n + 3) * U * 1.001 and e2 <= (2 * (n + 3) + 1) * U * 1.001
+        assert np.all(np.isnan(pint[i, :lo])) and np.all(np.isnan(pint[i, hi + 2:]))
+    assert np.all(np.isnan(pint[c["n"]])) and np.all(np.isnan(pmid[c["n"]]))
+    print(f"pressure K={K}: worst error / bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("K", K_NEW)
+def test_zheight_and_geopotential_against_exact_suffix_sums(K):
+    """ZInt[k] = -Bot + Rho0 sum_{j>=k} SpecVol_j h_j: the sum (n + 2 operations, one sign) is added to a term of the
+    other sign, so the bound is absolute: (n + 3) u (Bot + sum); ZMid one operation more.  GeoMid = (g ZMid + Tidal)
+    + SAL: 3 u (|g ZMid| + |Tidal| + |SAL|), from the ZMid it is given."""
+    c = _column(K, 40 + K)
+    zint, zmid = np.full((c["n"] + 1, K + 1), np.nan), np.full((c["n"] + 1, K), np.nan)
+    CR.zheight(c["h"], c["sv"], c["bot"], c["lo"], c["hi"], c["n"], RHO0, zint, zmid)
+    geo = np.full((c["n"] + 1, K), np.nan)
+    CR.geopotential(zmid, c["tidal"], c["sal"], c["lo"], c["hi"], c["n"], geo)
+    for i in range(c["n"]):
+        lo, hi = int(c["lo"][i]), int(c["hi"][i])
+        bot = Fr(float(c["bot"][i]))
+        acc = Fr(0)
+        assert zint[i, hi + 1] == -c["bot"][i]
+        for k in range(hi, lo - 1, -1):
+            dz = Fr(RHO0) * Fr(float(c["sv"][i, k])) * Fr(float(c["h"][i, k]))
+            acc += dz
+            n = hi - k + 1
+            scale = bot + acc
+            assert abs(Fr(float(zint[i, k])) - (acc - bot)) <= (n + 3) * U * scale * 1.001
+            assert abs(Fr(float(zmid[i, k])) - (acc - bot - dz / 2)) <= (n + 4) * U * scale * 1.001
+            gz = Fr(CR.GRAVITY) * Fr(float(zmid[i, k]))
+            t, s = Fr(float(c["tidal"][i])), Fr(float(c["sal"][i]))
+            assert abs(Fr(float(geo[i, k])) - (gz + t + s)) <= 3 * U * (abs(gz) + abs(t) + abs(s)) * 1.001
+        assert np.all(np.isnan(zmid[i, :lo])) and np.all(np.isnan(geo[i, hi + 1:]))
+
+
+@pytest.mark.parametrize("K", K_NEW)
+def test_bvf_against_the_exact_quotient(K):
+    """N2[k] = (g / Rho0) (1 / v_k - 1 / vd_{k-1}) / (z_{k-1} - z_k) subtracts two nearly equal densities: each
+    reciprocal is u / v off, so the absolute error is at most 2 u (1 / v) (g / Rho0) / dz, plus 5 u |N2| for the other
+    five operations; asserted with the constants 4 and 8 (twice the derived ones)."""
+    rng = np.random.default_rng(60 + K)
+    n = 5
+    lo = np.array([0, 0, K // 2, K - 1, min(1, K - 1), -1], np.int32)
+    hi = np.array([K - 1, min(2, K - 1), K - 1, K - 1, min(3, K - 1), -1], np.int32)
+    v = rng.uniform(9.70e-4, 9.75e-4, (n + 1, K))
+    vd = v * (1.0 + rng.uniform(-1.0e-5, 1.0e-5, (n + 1, K)))
+    z = -np.cumsum(rng.uniform(0.5, 40.0, (n + 1, K)), axis=1)
+    got = MR.bvf(v, vd, z, lo, hi, n, RHO0)
+    count = 0
+    for i in range(n):
+        for k in range(K):
+            if not (lo[i] < k <= hi[i]):
+                assert got[i, k] == 0.0
+                continue
+            dz = Fr(float(z[i, k - 1])) - Fr(float(z[i, k]))
+            want = (Fr(MR.GRAVITY) / Fr(RHO0)) * (1 / Fr(float(v[i, k])) - 1 / Fr(float(vd[i, k - 1]))) / dz
+            bound = 4 * U * (1 / Fr(float(min(v[i, k], vd[i, k - 1])))) * (Fr(MR.GRAVITY) / Fr(RHO0)) / dz \
+                + 8 * U * abs(want)
+            assert abs(Fr(float(got[i, k])) - want) <= bound
+            count += 1
+    assert np.all(got[n] == 0.0)
+    assert count == sum(max(int(hi[i] - lo[i]), 0) for i in range(n))  # K = 1: none, K = 2: one per full column
+    if K == 1:
+        assert not got.any()
+
+
+@pytest.mark.parametrize("K", K_NEW)
+def test_coefficients_against_a_50_digit_evaluation(K):
+    """VertVisc / VertDiff (background + shear with Ri = max(N2 / max(S2, 1e-12), 0) + convective) against the same
+    formulas in 50 digits, the shear sum over a cell's edges as a plain sum.  The shear sum has 7 same-sign terms of
+    4 operations each, then D^2 and the quotients; no sharp constant is derived here.  Measured on these inputs: 9.6 u
+    at worst (K = 1024); asserted at four times that, 40 u."""
+    from omega_amd.meshgen import planar_hex
+    g = planar_hex(4, 4, 3.0e4)
+    nc, ne = int(g["nCells"]), int(g["nEdges"])
+    rng = np.random.default_rng(80 + K)
+    lo = np.zeros(nc + 1, np.int32)
+    hi = np.full(nc + 1, K - 1, np.int32)
+    lo[nc], hi[nc] = -1, -1
+    hi[1], lo[2] = min(2, K - 1), K // 2
+    un, ut = rng.uniform(-0.05, 0.05, (2, ne + 1, K))
+    n2 = rng.uniform(-1.0e-5, 1.0e-4, (nc + 1, K))
+    zmid = -np.cumsum(rng.uniform(0.5, 40.0, (nc + 1, K)), axis=1)
+    nec, eoc = np.asarray(g["nEdgesOnCell"]), np.asarray(g["edgesOnCell"])
+    dc, dv, area = (np.asarray(g[k], dtype=np.float64) for k in ("dcEdge", "dvEdge", "areaCell"))
+    cfg = MR.config()
+    visc, diff = MR.coefficients(un, ut, n2, zmid, lo, hi, nc, nec, eoc, dc, dv, area, cfg)
+    worst = 0.0
+    mpf = mpmath.mpf
+    with mpmath.workdps(50):
+        for c in range(0, nc, 3):
+            for k in range(K):
+                if not (lo[c] < k <= hi[c]):
+                    assert visc[c, k] == 0.0 and diff[c, k] == 0.0
+                    continue
+                s2 = mpf(0)
+                for j in range(int(nec[c])):
+                    e = int(eoc[c, j])
+                    du, dvv = mpf(un[e, k - 1]) - mpf(un[e, k]), mpf(ut[e, k - 1]) - mpf(ut[e, k])
+                    s2 += mpf(0.5) * mpf(dc[e]) * mpf(dv[e]) / mpf(area[c]) * (du * du + dvv * dvv)
+                dz = mpf(zmid[c, k - 1]) - mpf(zmid[c, k])
+                s2 = max(s2 / (dz * dz), mpf(1.0e-12))
+                ri = max(mpf(n2[c, k]) / s2, mpf(0))
+                d = 1 + mpf(cfg["ShearAlpha"]) * ri
+                v = mpf(cfg["BackgroundViscosity"]) + mpf(cfg["ShearNuZero"]) / d ** 2
+                dd = mpf(cfg["BackgroundDiffusivity"]) + v / d
+                if n2[c, k] < cfg["ConvectiveTriggerBVF"]:
+                    v, dd = v + mpf(cfg["ConvectiveDiffusivity"]), dd + mpf(cfg["ConvectiveDiffusivity"])
+                worst = max(worst, float(abs(mpf(visc[c, k]) - v) / v), float(abs(mpf(diff[c, k]) - dd) / dd))
+    print(f"coefficients K={K}: worst relative error {worst / U:.2f} u")
+    assert worst <= 40 * U
+    if K == 1:
+        assert not visc.any() and not diff.any()
+
+
+# ---- the diffusion solves
+def _thomas_mp(g, h, x):
+    """-g[i-1] y[i-1] + (h[i] + g[i-1] + g[i]) y[i] - g[i] y[i+1] = x[i] by elimination in 50 digits"""
+    mpf = mpmath.mpf
+    n = len(x)
+    gg, hh, xx = [mpf(float(a)) for a in g], [mpf(float(a)) for a in h], [mpf(float(a)) for a in x]
+    d = [hh[i] + (gg[i - 1] if i else 0) + (gg[i] if i < n - 1 else 0) for i in range(n)]
+    for i in range(1, n):
+        w = -gg[i - 1] / d[i - 1]
+        d[i] -= w * -gg[i - 1]
+        xx[i] -= w * xx[i - 1]
+    y = [mpf(0)] * n
+    y[n - 1] = xx[n - 1] / d[n - 1]
+    for i in range(n - 2, -1, -1):
+        y[i] = (xx[i] + gg[i] * y[i + 1]) / d[i]
+    return y
+
+
+def _physical_system(n, seed, nb=4):
+    """layers of 0.5 .. 40 m (half of them 0.5 m), dt 1800 s; per interface the coefficient is 0, the convective
+    1.0 m2/s or the background 1e-5 m2/s: G / H from 0 to 7200, and a zero G splits the column"""
+    rng = np.random.default_rng(seed)
+    h = np.where(rng.random((nb, n)) < 0.5, 0.5, rng.uniform(0.5, 40.0, (nb, n)))
+    pick = rng.integers(0, 3, (nb, n))
+    coef = np.where(pick == 0, 0.0, np.where(pick == 1, 1.0, 1.0e-5))
+    phi = rng.uniform(-2.0, 30.0, (nb, n))
+    phi[0] = 17.25  # a uniform column
+    return h, coef, phi
+
+
+N_SOLVE = [1, 2, 3, 5, 15, 17, 129, 257, 512, 1024]
+
+
+@pytest.mark.parametrize("n", N_SOLVE)
+def test_diffusion_solves_against_a_50_digit_elimination(n):
+    """pcr_diff (the restated PCRDiffusionSolver) on the physical coefficient range of the GPU sweep (G / H from 0 to
+    7200, zero G inside the column) against a 50-digit elimination.  The tolerance is not a fixed number: the forward
+    error max|x^ - x| / max|x| of thomas_diff (the reference's serial algorithm) on the same systems is measured, and
+    PCR is allowed 16 times that (never less than 16 u).  Measured here over n = 1 .. 1024: thomas_diff up to 5.6 u,
+    pcr_diff up to 5.2 u (pcr_diff / thomas_diff at most 2.3 on any one system).  Also: sum h phi is conserved -- the sum of the residuals of a solve
+    that is backward stable row by row (Higham, Accuracy and Stability, 9.6: |dA| <= 13 u |A| for diagonally dominant
+    tridiagonal elimination) -- within 16 n u (||A|| max|x^| + max|b|); a uniform column stays uniform within the
+    same forward bound."""
+    h, coef, phi = _physical_system(n, 300 + n)
+    g, hh, b = MR.assemble(h, coef, phi, 1800.0)
+    assert n < 15 or g.max() / 0.5 > 1.0e3  # the convective value over a thin layer occurs
+    xp, xt = TR.pcr_diff(g, hh, b), TR.thomas_diff(g, hh, b)
+    for s in range(h.shape[0]):
+        with mpmath.workdps(50):
+            y = _thomas_mp(g[s], hh[s], b[s])
+            scale = max(abs(v) for v in y)
+            ep = float(max(abs(mpmath.mpf(float(a)) - v) for a, v in zip(xp[s], y)) / scale)
+            et = float(max(abs(mpmath.mpf(float(a)) - v) for a, v in zip(xt[s], y)) / scale)
+            # the uniform column: the exact solution is the constant, up to the rounding of X = h * phi
+            off = float(max(abs(v - mpmath.mpf(17.25)) for v in y)) / 17.25 if s == 0 else 0.0
+        print(f"n={n} system {s}: forward error thomas_diff {et / U:.2f} u, pcr_diff {ep / U:.2f} u")
+        assert ep <= 16 * max(et, U)
+        if s == 0:
+            assert off <= 2 * U and np.max(np.abs(xp[s] - 17.25)) / 17.25 <= 16 * max(et, U) + off
+        gm = np.concatenate([[0.0], g[s, :-1]])
+        norm_a = np.max(hh[s] + 2 * gm + 2 * g[s])
+        for xs in (xp[s], xt[s]):
+            drift = abs(sum(Fr(float(a)) * Fr(float(v)) for a, v in zip(h[s], xs)) - sum(Fr(float(v)) for v in b[s]))
+            assert drift <= 16 * n * U * (norm_a * np.max(np.abs(xs)) + np.max(np.abs(b[s])))
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 17, 129, 1024])
+def test_tracer_mix_against_a_50_digit_elimination(n):
+    """tracer_mix (ranges, assembly and pcr_diff together) on columns inside a deeper array, with the bound of the
+    test above; levels outside the range and unowned columns keep their values."""
+    K, nb = n + 3, 4
+    h, coef, phi = _physical_system(K, 500 + n, nb)
+    lo = np.array([0, 1, 3, 2], np.int32)
+    hi = lo + n - 1
+    tr = np.stack([phi, phi * 0.5 - 1.0])
+    out = MR.tracer_mix(h, coef, tr, 2, 1800.0, lo, hi, 3)
+    assert np.array_equal(out[:, 3], tr[:, 3])  # not owned
+    for c in range(3):
+        a, z = int(lo[c]), int(hi[c]) + 1
+        assert np.array_equal(out[:, c, :a], tr[:, c, :a]) and np.array_equal(out[:, c, z:], tr[:, c, z:])
+        g, hh, b = MR.assemble(h[c: c + 1, a:z], coef[c: c + 1, a:z], tr[1][c: c + 1, a:z], 1800.0)
+        xt = TR.thomas_diff(g, hh, b)[0]
+        with mpmath.workdps(50):
+            y = _thomas_mp(g[0], hh[0], b[0])
+            scale = max(abs(v) for v in y)
+            ep = float(max(abs(mpmath.mpf(float(q)) - v) for q, v in zip(out[1, c, a:z], y)) / scale)
+            et = float(max(abs(mpmath.mpf(float(q)) - v) for q, v in zip(xt, y)) / scale)
+        assert ep <= 16 * max(et, U)

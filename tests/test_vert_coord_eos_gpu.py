@@ -8,125 +8,13 @@ import pytest
 import omega_amd as oa
 from tests import column_reference as R
 from tests.meshes import named_mesh
+from tests.vert_fixtures import EOS_OUT, RHO0, Col, same as _assert_same
 
 pytestmark = pytest.mark.gpu
-
-RHO0 = 1026.0
-NT = 3  # tracers: T and S are picked by index (1 and 2 in some cases: not only the default 0 / 1)
-VC_OUT = ("PressureInterface", "PressureMid", "ZInterface", "ZMid", "GeopotentialMid", "LayerThicknessTarget")
-EOS_OUT = ("SpecVol", "SpecVolDisplaced")
-
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
     oa.device_init(0)
-
-
-def _global_inputs(g, K, seed):
-    """Global per-cell inputs: 1-based layer ranges (full columns, KMin > 0, short and single-layer columns),
-    thickness, tracers, surface pressure, tidal potential, SAL, bottom depth, reference thickness."""
-    n = int(g["nCells"])
-    rng = np.random.default_rng(seed)
-    kind = rng.integers(0, 5, n)
-    mn = np.ones(n, np.int32)
-    mx = np.full(n, K, np.int32)
-    a = rng.integers(2, max(3, K // 3), n)
-    mn[kind == 1] = a[kind == 1]                                   # KMin > 0, to the bottom
-    mx[kind == 2] = rng.integers(1, 4, n)[kind == 2]               # short columns
-    s = rng.integers(1, K + 1, n)
-    mn[kind == 3], mx[kind == 3] = s[kind == 3], s[kind == 3]      # single layer
-    lo = rng.integers(1, K + 1, n)
-    hi = np.minimum(K, lo + rng.integers(0, K, n))
-    mn[kind == 4], mx[kind == 4] = lo[kind == 4], hi[kind == 4]    # random
-    return dict(
-        min_level=mn, max_level=mx,
-        h=rng.uniform(0.5, 40.0, (n, K)),
-        tr=np.stack([rng.uniform(-1.0, 1.0, (n, K)), rng.uniform(-2.0, 30.0, (n, K)), rng.uniform(30.0, 38.0, (n, K))]),
-        ps=rng.uniform(0.9e5, 1.1e5, n), tidal=rng.uniform(-1.0, 1.0, n), sal=rng.uniform(-0.1, 0.1, n),
-        bot=rng.uniform(100.0, 6000.0, n), ref=rng.uniform(1.0, 30.0, (n, K)))
-
-
-class Col:
-    """One rank's objects (VertCoord, Eos, OceanState, Tracers) with the global inputs in local order."""
-
-    def __init__(self, g, K, eos_kind, nparts=1, rank=0, seed=7, weights="Uniform"):
-        self.K, self.eos_kind = K, eos_kind
-        self.gm = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm, nparts, rank, 3)
-        self.mesh = oa.HorzMesh(self.decomp, K)
-        m = self.mesh
-        self.n_all, self.n_size = m.NCellsAll, m.NCellsSize
-        self.cid = self.decomp.get_array("CellID")
-        G = _global_inputs(g, K, seed)
-        self.G = G
-        rows = self.cid[: self.n_all] - 1
-
-        def loc(x):
-            out = np.zeros((self.n_size,) + x.shape[1:])
-            out[: self.n_all] = x[rows]
-            return out
-
-        self.h = loc(G["h"])
-        self.tr = np.stack([loc(t) for t in G["tr"]])
-        self.ps, self.tidal, self.sal, self.bot, self.ref = (loc(G[k]) for k in ("ps", "tidal", "sal", "bot", "ref"))
-        self.vc = oa.VertCoord(m, K, RHO0, weights, G["min_level"], G["max_level"], decomp=self.decomp)
-        self.eos = oa.Eos(m, K, eos_kind)
-        self.state = oa.OceanState(m, None, K, 2)
-        self.tracers = oa.Tracers(m, None, K, NT, 2)
-        self.state.copy_to_device(self.h, np.zeros((m.NEdgesSize, K)), 0)
-        self.tracers.copy_to_device(self.tr, 0)
-        self.vc.set("BottomDepth", self.bot)
-        self.vc.set("RefLayerThickness", self.ref)
-        self.lo, self.hi = R.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
-        self.poison()
-
-    def poison(self):
-        for name in VC_OUT:
-            self.vc.set(name, np.full(self.vc.get(name).shape, np.nan))
-        for name in EOS_OUT:
-            self.eos.set(name, np.full((self.n_size, self.K), np.nan))
-
-    def nan_state(self):
-        K, n = self.K, self.n_size
-        return {"PressureInterface": np.full((n, K + 1), np.nan), "PressureMid": np.full((n, K), np.nan),
-                "ZInterface": np.full((n, K + 1), np.nan), "ZMid": np.full((n, K), np.nan),
-                "GeopotentialMid": np.full((n, K), np.nan), "SpecVol": np.full((n, K), np.nan),
-                "SpecVolDisplaced": np.full((n, K), np.nan), "LayerThicknessTarget": np.full((n, K), np.nan)}
-
-    def outputs(self):
-        out = {name: self.vc.get(name) for name in VC_OUT}
-        out.update({name: self.eos.get(name) for name in EOS_OUT})
-        return out
-
-    def run_fused(self, kdisp, ti, si):
-        self.vc.compute_column(self.state, self.tracers, self.eos, self.ps, self.tidal, self.sal, kdisp=kdisp,
-                               temp_index=ti, salt_index=si)
-        oa.device_synchronize()
-
-    def run_sequence(self, kdisp, ti, si):
-        """the four launches the fused pass replaces, on the device"""
-        vc, eos = self.vc, self.eos
-        hp = self.state.device_ptr(0)
-        tp, sp = oa.tracer_rows_ptr(self.tracers, ti), oa.tracer_rows_ptr(self.tracers, si)
-        vc.compute_pressure(hp, self.ps)
-        eos.compute_spec_vol(tp, sp, vc.device_ptr("PressureMid"), p_scale=1.0e-4)
-        if kdisp is not None:
-            eos.compute_spec_vol_disp(tp, sp, vc.device_ptr("PressureMid"), kdisp, p_scale=1.0e-4)
-        vc.compute_zheight(hp, eos.device_ptr("SpecVol"))
-        vc.compute_geopotential(self.tidal, self.sal)
-        oa.device_synchronize()
-
-    def expected(self, kdisp, ti, si):
-        st = self.nan_state()
-        R.column_sequence(self.h, self.tr[ti], self.tr[si], self.ps, self.tidal, self.sal, self.bot, self.lo, self.hi,
-                          self.n_all, RHO0, self.eos_kind, st, kdisp)
-        return st
-
-
-def _assert_same(got, want, name):
-    assert got.shape == want.shape, name
-    bad = ~((got == want) | (np.isnan(got) & np.isnan(want)))
-    assert not bad.any(), f"{name}: {bad.sum()} elements differ, first at {np.argwhere(bad)[0]}"
 
 
 CASES = [("hex24x20", 80, "teos10", 3, 0, 1), ("hex24x20", 60, "linear", None, 1, 2),

@@ -10,130 +10,18 @@ from tests import column_reference as CR
 from tests import tridiag_reference as TR
 from tests import vert_mix_reference as R
 from tests.meshes import named_mesh
+from tests.vert_fixtures import MIX_NT, MIX_OUT, Mix, same as _same
 
 pytestmark = pytest.mark.gpu
 
-RHO0 = 1026.0
-NT = 6
+NT = MIX_NT
 DT = 1800.0
-OUT = ("VertDiff", "VertVisc", "BruntVaisalaFreqSq")
+OUT = MIX_OUT
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
     oa.device_init(0)
-
-
-def _global_inputs(g, K, seed, full=False, nt=NT):
-    """Global per-cell / per-edge inputs: 1-based layer ranges (full columns, KMin > 0, short, single-layer, random,
-    land), thickness, tracers (T, S first), edge velocities."""
-    n, ne = int(g["nCells"]), int(g["nEdges"])
-    rng = np.random.default_rng(seed)
-    kind = rng.integers(0, 6, n)
-    mn, mx = np.ones(n, np.int32), np.full(n, K, np.int32)
-    if not full:
-        a = rng.integers(2, max(3, K // 3), n)
-        mn[kind == 1] = a[kind == 1]                                   # KMin > 0, to the bottom
-        mx[kind == 2] = rng.integers(1, 4, n)[kind == 2]               # short columns
-        s = rng.integers(1, K + 1, n)
-        mn[kind == 3], mx[kind == 3] = s[kind == 3], s[kind == 3]      # single layer
-        lo = rng.integers(1, K + 1, n)
-        hi = np.minimum(K, lo + rng.integers(0, K, n))
-        mn[kind == 4], mx[kind == 4] = lo[kind == 4], hi[kind == 4]    # random
-        mx[kind == 5] = 0                                              # land: MaxLayerCell -1
-    tr = np.concatenate([rng.uniform(-2.0, 30.0, (1, n, K)), rng.uniform(30.0, 38.0, (1, n, K)),
-                         rng.uniform(-1.0, 1.0, (nt - 2, n, K))])
-    return dict(min_level=mn, max_level=mx, h=rng.uniform(0.5, 40.0, (n, K)), tr=tr,
-                un=rng.uniform(-0.05, 0.05, (ne, K)), ut=rng.uniform(-0.05, 0.05, (ne, K)))
-
-
-class Mix:
-    """One rank's VertCoord, Eos, OceanState, Tracers and VertMix, with the global inputs in local order and the
-    column pass (with SpecVolDisplaced at KDisp = 1) already run."""
-
-    def __init__(self, g, K, eos_kind="teos10", nparts=1, rank=0, seed=7, full=False, ntracers=NT, **cfg):
-        self.K, self.nt = K, ntracers
-        self.gm = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm, nparts, rank, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K)
-        self.n_own, self.n_all, self.n_size = m.NCellsOwned, m.NCellsAll, m.NCellsSize
-        self.e_own, self.e_all, self.e_size = m.NEdgesOwned, m.NEdgesAll, m.NEdgesSize
-        self.cid = self.decomp.get_array("CellID")
-        self.eid = self.decomp.get_array("EdgeID")
-        G = self.G = _global_inputs(g, K, seed, full, ntracers)
-        crow, erow = self.cid[: self.n_all] - 1, self.eid[: self.e_all] - 1
-
-        def loc(x, rows, n_size, fill=0.0):
-            out = np.full((n_size,) + x.shape[1:], fill)
-            out[: len(rows)] = x[rows]
-            return out
-
-        self.h = loc(G["h"], crow, self.n_size)
-        self.tr = np.stack([loc(t, crow, self.n_size) for t in G["tr"]])
-        self.un = loc(G["un"], erow, self.e_size)
-        self.ut = loc(G["ut"], erow, self.e_size)
-        self.vc = oa.VertCoord(m, K, RHO0, "Uniform", G["min_level"], G["max_level"], decomp=self.decomp)
-        self.lo, self.hi = CR.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
-        self.eos = oa.Eos(m, K, eos_kind)
-        self.state = oa.OceanState(m, None, K, 2)
-        self.tracers = oa.Tracers(m, None, K, ntracers, 2)
-        self.state.copy_to_device(self.h, self.un, 0)
-        self.tracers.copy_to_device(self.tr, 0)
-        self.vc.compute_column(self.state, self.tracers, self.eos, kdisp=1)
-        oa.device_synchronize()
-        self.vm = oa.VertMix(m, self.vc, **cfg)
-        self.cfg = R.config(**cfg)
-        for name in OUT:
-            self.vm.set(name, np.full((self.n_size, K), np.nan))
-
-    def mesh_arrays(self):
-        m = self.mesh
-        return (m.get_array("NEdgesOnCell"), m.get_array("EdgesOnCell"), m.get_array("DcEdge"),
-                m.get_array("DvEdge"), m.get_array("AreaCell"))
-
-    def expected_coefficients(self, un, ut, n2):
-        return R.coefficients(un, ut, n2, self.vc.get("ZMid"), self.lo, self.hi, self.n_all, *self.mesh_arrays(),
-                              self.cfg)
-
-    def expected_bvf(self):
-        return R.bvf(self.eos.get("SpecVol"), self.eos.get("SpecVolDisplaced"), self.vc.get("ZMid"), self.lo,
-                     self.hi, self.n_all, RHO0)
-
-    def compute(self, ut=None, stream=None):
-        self.vm.compute_bvf(self.eos, stream=stream)
-        self.vm.compute(self.un, self.ut if ut is None else ut, stream=stream)
-        oa.device_synchronize()
-
-    def seeded_tracers(self):
-        """time level 0: the tracers, NaN outside each owned column's range, on halo and sentinel rows and in the
-        pad of land; time level 1: distinct values"""
-        t0 = np.full_like(self.tr, np.nan)
-        for c in range(self.n_own):
-            lo, hi = self.lo[c], self.hi[c]
-            if 0 <= lo <= hi < self.K:
-                t0[:, c, lo: hi + 1] = self.tr[:, c, lo: hi + 1]
-        t1 = np.arange(self.tr.size, dtype=np.float64).reshape(self.tr.shape) * 0.5 + 0.25
-        self.tracers.copy_to_device(t0, 0)
-        self.tracers.copy_to_device(t1, 1)
-        return t0, t1
-
-    def seeded_velocity(self):
-        """u at level 0 with NaN outside each owned edge's range and on halo / sentinel rows; level 1 distinct"""
-        lo, hi = self.vc.get("MinLayerEdgeBot"), self.vc.get("MaxLayerEdgeTop")
-        u0 = np.full_like(self.un, np.nan)
-        for e in range(self.e_own):
-            if 0 <= lo[e] <= hi[e] < self.K:
-                u0[e, lo[e]: hi[e] + 1] = self.un[e, lo[e]: hi[e] + 1]
-        u1 = np.arange(self.un.size, dtype=np.float64).reshape(self.un.shape) * 0.25 - 3.0
-        self.state.copy_to_device(self.h, u0, 0)
-        self.state.copy_to_device(self.h, u1, 1)
-        return u0, u1, lo, hi
-
-
-def _same(got, want, name):
-    assert got.shape == want.shape, name
-    bad = ~((got == want) | (np.isnan(got) & np.isnan(want)))
-    assert not bad.any(), f"{name}: {bad.sum()} elements differ, first at {np.argwhere(bad)[0]}"
 
 
 CASES = [("hex24x20", 80, "teos10"), ("hex24x20", 60, "linear"), ("fib700_coast_ragged", 37, "teos10"),
