@@ -38,6 +38,7 @@ typedef struct omg_stepper omg_stepper; /* O/src/timeStepping/TimeStepper.h     
 typedef struct omg_vcoord omg_vcoord;   /* O/src/ocn/VertCoord.h class VertCoord     */
 typedef struct omg_eos omg_eos;         /* O/src/ocn/Eos.h       class Eos           */
 typedef struct omg_vertmix omg_vertmix; /* O/doc/design/VerticalMixingCoeff.md (design only) */
+typedef struct omg_pgrad omg_pgrad;     /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
 
 enum { OMG_ON_CELL = 0, OMG_ON_EDGE = 1, OMG_ON_VERTEX = 2 }; /* O/src/base/Halo.h:45 MeshElement */
 
@@ -549,6 +550,34 @@ int omg_vertmix_apply_velocity(omg_vertmix *x, const double *layer_thickness_dev
 int omg_vertmix_copy_to_host(const omg_vertmix *x, const char *name, double *host, size_t n);
 int omg_vertmix_copy_to_device(omg_vertmix *x, const char *name, const double *host, size_t n);
 int omg_vertmix_device_ptr(const omg_vertmix *x, const char *name, double **dev, size_t *n);
+
+/* ---- PressureGrad: the layered-ocean pressure-gradient force on edges, -(grad Phi) - alpha grad p along the layers
+ * (O/doc/design/OmegaV1GoverningEqns.md, discrete momentum equation; the reference has no code for it).  Numerical
+ * contract: omega_amd/csrc/PressureGrad.h.  Arrays are level-indexed device arrays as above.  Every call is
+ * asynchronous on stream and allocates nothing.  The object keeps pointers to v and e: destroy it before them. ---- */
+/* fails for a host-only mesh and for a VertCoord or Eos of another mesh or layer count */
+int omg_pgrad_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, omg_pgrad **out);
+int omg_pgrad_destroy(omg_pgrad *p);
+/* the fused column pass (omg_vcoord_compute_column) from raw arrays: layer_thickness_dev [NCellsSize][pitch],
+ * tracers_dev [ntracers >= 2][NCellsSize][pitch] with temperature at index 0 and salinity at 1, no displaced volume,
+ * and the object's SurfacePressure / TidalPotential / SelfAttractionLoading */
+int omg_pgrad_update_column(omg_pgrad *p, const double *layer_thickness_dev, const double *tracers_dev, int ntracers,
+                            void *stream);
+/* tend_dev [NEdgesSize][pitch] -= the term, from the VertCoord's PressureMid / GeopotentialMid and the Eos's SpecVol as
+ * they stand */
+int omg_pgrad_compute(omg_pgrad *p, double *tend_dev, void *stream);
+/* the same from the caller's [NCellsSize][pitch] arrays (PressureMid in Pa) */
+int omg_pgrad_compute_arrays(omg_pgrad *p, double *tend_dev, const double *pressure_mid_dev,
+                             const double *geopotential_mid_dev, const double *spec_vol_dev, void *stream);
+/* "SurfacePressure", "TidalPotential", "SelfAttractionLoading" ([NCellsSize], zero at creation) */
+int omg_pgrad_device_ptr(const omg_pgrad *p, const char *name, double **dev, size_t *n);
+int omg_pgrad_copy_to_device(omg_pgrad *p, const char *name, const double *host, size_t n);
+int omg_pgrad_copy_to_host(const omg_pgrad *p, const char *name, double *host, size_t n);
+/* Tendencies::attachPressureGrad: the term becomes an opt-in velocity term of t (p NULL: detach).  Fails while
+ * SSHTendencyEnable is on.  While attached omg_tend_compute_all runs the column pass on the stage's thickness and
+ * tracers first; the velocity-only calls use the column fields as they stand; the Runge-Kutta stage updates run as
+ * separate kernels and nothing is replayed as a graph.  Detach before destroying p. */
+int omg_tend_attach_pressure_grad(omg_tend *t, omg_pgrad *p);
 
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at

@@ -2,7 +2,7 @@
 
 Thin ctypes plumbing used by tests/, bench.py and __graft_entry__.py: the product is the
 C++/HIP library under omega_amd/csrc (classes named after Omega's own: Decomp, Halo,
-HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, Tendencies, TimeStepper).  There is no
+HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, PressureGrad, Tendencies, TimeStepper).  There is no
 Python or CPU implementation of the hot path here: if the shared library is missing,
 importing the binding raises, and without a HIP device every device call fails.
 """
@@ -1219,6 +1219,99 @@ class VertMix:
             pass
 
 
+PGRAD_ARRAYS = ("SurfacePressure", "TidalPotential", "SelfAttractionLoading")
+
+
+class PressureGrad:
+    """PressureGrad (omega_amd/csrc/PressureGrad.h): the layered-ocean pressure-gradient force on edges,
+    Tend -= EdgeMask * (grad GeopotentialMid + 0.5 (SpecVol0 + SpecVol1) grad PressureMid), from the column fields of
+    `vcoord` and `eos`.  Level-indexed inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)]
+    doubles; `tend` is accumulated in place: a device address (asynchronous on `stream`) or a numpy array (staged,
+    computed, returned)."""
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None"):
+        self.mesh, self.vcoord, self.eos = mesh, vcoord, eos
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        h = C.c_void_p()
+        _chk(lib().omg_pgrad_create(mesh.h, vcoord.h if vcoord is not None else None,
+                                    eos.h if eos is not None else None, C.byref(h)))
+        self.h = h
+
+    def _tend(self, tend):
+        if isinstance(tend, (int, np.integer)):
+            return C.c_void_p(int(tend)), None
+        a = np.asarray(tend, dtype=np.float64)
+        shape = (self.mesh.NEdgesSize, self.K)
+        assert a.shape == shape, f"expected shape {shape}, got {a.shape}"
+        pad = np.zeros((shape[0], level_pitch(self.K)))
+        pad[:, : self.K] = a
+        b = DeviceBuffer(pad)
+        return C.c_void_p(b.ptr), b
+
+    def _back(self, buf, stream):
+        if buf is None:
+            return None
+        if stream is not None:
+            stream.synchronize()
+        device_synchronize()
+        return buf.to_host()[:, : self.K]
+
+    def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
+        """The fused column pass from raw arrays: thickness [NCellsSize][K], tracers [ntracers][NCellsSize][K]
+        (temperature 0, salinity 1), with this object's SurfacePressure / TidalPotential / SelfAttractionLoading."""
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        if isinstance(tracers, (int, np.integer)):
+            t = C.c_void_p(int(tracers))
+        else:
+            a = np.asarray(tracers, dtype=np.float64)
+            assert a.shape == (int(ntracers), n, self.K), f"expected shape {(int(ntracers), n, self.K)}, got {a.shape}"
+            pad = np.zeros((int(ntracers), n, level_pitch(self.K)))
+            pad[..., : self.K] = a
+            keep.append(DeviceBuffer(pad))
+            t = C.c_void_p(keep[-1].ptr)
+        _chk(lib().omg_pgrad_update_column(self.h, h, t, int(ntracers), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def compute(self, tend, pressure_mid=None, geopotential_mid=None, spec_vol=None, stream=None):
+        """tend -= the term: from the three given cell arrays (the array form; all three or none), or from the
+        VertCoord's and the Eos's arrays as they stand."""
+        given = [x is not None for x in (pressure_mid, geopotential_mid, spec_vol)]
+        assert all(given) or not any(given), "give PressureMid, GeopotentialMid and SpecVol, or none of them"
+        p, buf = self._tend(tend)
+        keep, n = [], self.mesh.NCellsSize
+        if all(given):
+            _chk(lib().omg_pgrad_compute_arrays(self.h, p, _level_dev(pressure_mid, n, self.K, keep),
+                                                _level_dev(geopotential_mid, n, self.K, keep),
+                                                _level_dev(spec_vol, n, self.K, keep), _sh(stream)))
+        else:
+            _chk(lib().omg_pgrad_compute(self.h, p, _sh(stream)))
+        if keep:
+            device_synchronize()
+        return self._back(buf, stream)
+
+    def get(self, name: str) -> np.ndarray:
+        out = np.zeros(self.mesh.NCellsSize)
+        _chk(lib().omg_pgrad_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
+        return out
+
+    def set(self, name: str, values: np.ndarray):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        _chk(lib().omg_pgrad_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
+
+    def device_ptr(self, name: str) -> int:
+        p = PD()
+        _chk(lib().omg_pgrad_device_ptr(self.h, name.encode(), C.byref(p), None))
+        return C.cast(p, C.c_void_p).value
+
+    def __del__(self):
+        try:
+            lib().omg_pgrad_destroy(self.h)
+        except Exception:
+            pass
+
+
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""
@@ -1242,6 +1335,12 @@ class Tendencies:
 
     def set_fused(self, on: bool):
         _chk(lib().omg_tend_set_fused(self.h, int(on)))
+
+    def attach_pressure_grad(self, pgrad: "PressureGrad | None"):
+        """Tendencies::attachPressureGrad: the layered pressure gradient as an opt-in velocity term (None detaches);
+        raises while SSHTendencyEnable is on."""
+        _chk(lib().omg_tend_attach_pressure_grad(self.h, pgrad.h if pgrad is not None else None))
+        self._pgrad = pgrad  # the library keeps a pointer to it
 
     def set_graphs(self, on: bool):
         _chk(lib().omg_tend_set_graphs(self.h, int(on)))

@@ -1,6 +1,7 @@
 // Tendencies.cpp -- see Tendencies.h.
 #include "Tendencies.h"
 #include "Pacer.h"
+#include "PressureGrad.h"
 #include "kernels/KernelCommon.h"
 
 namespace OMEGA {
@@ -72,6 +73,24 @@ TendParams Tendencies::paramsFor(const AuxiliaryState *Aux) const {
    return P;
 }
 
+void Tendencies::attachPressureGrad(PressureGrad *P) {
+   if (P) {
+      OMEGA_REQUIRE(!Params.SSHTendencyEnable,
+                    "Tendencies::attachPressureGrad: SSHTendencyEnable is on: the SSH gradient and the layered pressure "
+                    "gradient are two pressure forces; disable the SSH gradient first");
+      OMEGA_REQUIRE(P->Mesh == Mesh && P->NVertLayers == NVertLayers,
+                    "Tendencies::attachPressureGrad: the PressureGrad was built for another mesh or layer count");
+   }
+   PGrad = P;
+}
+
+void Tendencies::addPressureGrad(hipStream_t S) {
+   OMEGA_REQUIRE(!Params.SSHTendencyEnable,
+                 "Tendencies: SSHTendencyEnable was turned on while a PressureGrad is attached: two pressure forces");
+   Pacer::Range Timer("Tend:pressureGrad", 2);
+   PGrad->computePressureGrad(NormalVelocityTend, S);
+}
+
 // Tendencies.cpp:257-297
 void Tendencies::computeThicknessTendenciesOnly(const OceanState *State, const AuxiliaryState *Aux, int ThickLvl, int VelLvl,
                                                 hipStream_t S) {
@@ -93,6 +112,8 @@ void Tendencies::computeVelocityTendenciesOnly(const OceanState *State, const Au
    OMEGA_REQUIRE(State->getNormalVelocity(NormalVelEdge, VelLvl) == 0, "Tendencies: bad velocity time level");
    launchVelocityTendOnly(Mesh->view(), NVertLayers, paramsFor(Aux), Aux->ptrs(), NormalVelocityTend.Ptr,
                           NormalVelEdge.Ptr, S);
+   if (PGrad)
+      addPressureGrad(S);
    if (CustomVelocityTend) { // Tendencies.cpp:416-419
       Pacer::Range T2("Tend:customVelocityTend", 2);
       CustomVelocityTend(NormalVelocityTend, State, Aux, ThickLvl, VelLvl, ModelTime, S);
@@ -153,6 +174,8 @@ bool Tendencies::computeAllTendenciesStage(const OceanState *State, const Auxili
       return false;
    if (CustomThicknessTend || CustomVelocityTend)
       return false; // the custom terms are added to the stored tendencies: needs the plain sequence
+   if (PGrad)
+      return false; // so is the attached pressure gradient
    Array2DReal LayerThick, NormVel;
    OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0 && State->getNormalVelocity(NormVel, VelLvl) == 0,
                  "Tendencies: bad time level");
@@ -178,6 +201,8 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
             HIP_CHECK(hipEventCreate(&E));
          Ev = TimingEvents.back().data();
       }
+      if (PGrad)
+         PGrad->updateColumn(LayerThick, TracerArray, S);
       const TendParams P = paramsFor(Aux);
       auto Launch        = [&]() {
          launchFusedRHS(Mesh->view(), NVertLayers, NTracers, P, Aux->ptrs(), LayerThicknessTend.Ptr,
@@ -185,7 +210,7 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
                         EdgeScratch.Ptr, nullptr, Mesh->narrowView());
       };
       // wind forcing reads the stress arrays through a non-tile kernel too, still plain launches: capturable
-      if (graphsOn() && !Ev && !CustomThicknessTend && !CustomVelocityTend) {
+      if (graphsOn() && !Ev && !CustomThicknessTend && !CustomVelocityTend && !PGrad) {
          GraphCache::Key Key;
          GraphCache::add(Key, LayerThick.Ptr), GraphCache::add(Key, NormVel.Ptr), GraphCache::add(Key, TracerArray.Ptr);
          GraphCache::add(Key, Aux), GraphCache::add(Key, P), GraphCache::add(Key, S);
@@ -194,6 +219,8 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
       } else {
          Launch();
       }
+      if (PGrad)
+         addPressureGrad(S);
       if ((CustomThicknessTend || CustomVelocityTend) && MaterialiseAuxForCustom)
          Aux->computeAll(State, TracerArray, ThickLvl, VelLvl, S); // the hooks may read the AuxiliaryState
       if (CustomThicknessTend)
@@ -201,6 +228,11 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
       if (CustomVelocityTend)
          CustomVelocityTend(NormalVelocityTend, State, Aux, ThickLvl, VelLvl, ModelTime, S);
       return;
+   }
+   if (PGrad) {
+      Array2DReal LayerThick;
+      OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0, "Tendencies: bad time level");
+      PGrad->updateColumn(LayerThick, TracerArray, S); // computeVelocityTendenciesOnly adds the term from these fields
    }
    Aux->computeAll(State, TracerArray, ThickLvl, VelLvl, S);
    computeThicknessTendenciesOnly(State, Aux, ThickLvl, VelLvl, S);

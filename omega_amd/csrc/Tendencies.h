@@ -19,6 +19,8 @@
 
 namespace OMEGA {
 
+class PressureGrad;
+
 /// A custom tendency hook (Tendencies.h:51-53): holds a callable of EITHER form --
 ///   native:     void(const Array2DReal &Tend, const OceanState *, const AuxiliaryState *, int ThickLvl, int VelLvl,
 ///                    R8 ModelTimeSeconds, hipStream_t S)                  (launch on S)
@@ -91,6 +93,20 @@ class Tendencies : public Registry<Tendencies> {
    /// model time handed to the custom tendencies; the time steppers set it for every stage
    /// (RungeKutta4Stepper.cpp:87 StageTime, RungeKutta2Stepper.cpp:44,58, ForwardBackwardStepper.cpp:50,59,67)
    R8 ModelTime = 0.0;
+
+   /// The layered-ocean pressure-gradient force (PressureGrad.h) as an opt-in velocity term; nullptr detaches.  Refused
+   /// (OmegaError) while Params.SSHTendencyEnable is on -- two pressure forces must be a visible mistake -- and for an
+   /// object of another mesh or layer count.  While attached:
+   ///  - computeAllTendencies runs the column pass (PressureGrad::updateColumn) on the stage's layer thickness and the
+   ///    TracerArray argument (tracer 0 = temperature, 1 = salinity), then subtracts the term from NormalVelocityTend
+   ///    after the built-in velocity terms and before CustomVelocityTend, all on the same stream;
+   ///  - computeVelocityTendenciesOnly / computeVelocityTendencies take no tracers: they add the term from the column
+   ///    fields AS THEY STAND (the last updateColumn / VertCoord::computeColumn) -- the caller keeps them current;
+   ///  - computeAllTendenciesStage returns false, as with custom hooks (the Runge-Kutta stage updates then run as
+   ///    separate kernels), and the RHS is not replayed as a graph.
+   /// With nothing attached every code path, launch count and result is what it was.
+   void attachPressureGrad(PressureGrad *PGrad);
+   PressureGrad *pressureGrad() const { return PGrad; }
 
    void computeThicknessTendenciesOnly(const OceanState *State, const AuxiliaryState *AuxState, int ThickTimeLevel,
                                        int VelTimeLevel, hipStream_t S);
@@ -167,6 +183,8 @@ class Tendencies : public Registry<Tendencies> {
    bool MaterialiseAuxForCustom = true;
 
  private:
+   PressureGrad *PGrad = nullptr;
+   void addPressureGrad(hipStream_t S); ///< NormalVelocityTend -= the attached term, from the column fields as they stand
    Array2DReal EdgeScratch; ///< running PV sums of the fused RHS (allocated by the constructor)
    bool TimingOn = false;
    std::vector<std::vector<hipEvent_t>> TimingEvents;

@@ -492,7 +492,8 @@ bool RungeKutta4Stepper::doStepFused(OceanState *State, hipStream_t S) {
       }
    }
    };
-   if (!Exchanges && (UseGraphs || GraphCache::defaultOn()) && StageFusedKnownGood && !Tend->CustomThicknessTend && !Tend->CustomVelocityTend) {
+   if (!Exchanges && (UseGraphs || GraphCache::defaultOn()) && StageFusedKnownGood && !Tend->CustomThicknessTend && !Tend->CustomVelocityTend &&
+       !Tend->pressureGrad()) {
       // one rank: nothing but kernel launches on S -- replay them as a graph (keyed by everything that enters them)
       GraphCache::Key Key;
       GraphCache::add(Key, State), GraphCache::add(Key, CurH.Ptr), GraphCache::add(Key, NextH.Ptr);

@@ -177,6 +177,15 @@ void VertCoord::computeColumn(const OceanState *State, int ThickLevel, const Tra
    OMEGA_REQUIRE(State->getLayerThickness(H, ThickLevel) == 0, "VertCoord::computeColumn: bad thickness time level");
    Array3DReal Tr;
    OMEGA_REQUIRE(Tracers->getAll(Tr, TrLevel) == 0, "VertCoord::computeColumn: bad tracer time level");
+   computeColumn(H, Tr, EqState, Ps, Tidal, SAL, Displaced, KDisp, S, TIndex, SIndex);
+}
+
+void VertCoord::computeColumn(const Array2DReal &H, const Array3DReal &Tr, const Eos &EqState, const Array1DReal &Ps,
+                              const Array1DReal &Tidal, const Array1DReal &SAL, bool Displaced, I4 KDisp, hipStream_t S,
+                              I4 TIndex, I4 SIndex) {
+   OMEGA_REQUIRE(EqState.Mesh == Mesh && EqState.NVertLayers == NVertLayers,
+                 "VertCoord::computeColumn: the Eos was built for another mesh or layer count");
+   OMEGA_REQUIRE(Tr.Ptr != nullptr, "VertCoord::computeColumn: the tracer array is empty");
    const Array2DReal T = tracerRows(Tr, TIndex), Sa = tracerRows(Tr, SIndex);
    requireLevels(H, Mesh, NVertLayers, "LayerThickness");
    requireLevels(T, Mesh, NVertLayers, "tracer rows");

@@ -89,6 +89,12 @@ class VertCoord : public Registry<VertCoord> {
                       const Array1DReal &SurfacePressure, const Array1DReal &TidalPotential,
                       const Array1DReal &SelfAttractionLoading, bool Displaced, I4 KDisp, hipStream_t S, I4 TIndex = 0,
                       I4 SIndex = 1);
+   /// the same pass from raw arrays: LayerThickness [NCellsSize][levelPitch(K)], TracerArray
+   /// [NTracers][NCellsSize][levelPitch(K)] (what the overload above forwards to; same kernel, same results)
+   void computeColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, const Eos &EqState,
+                      const Array1DReal &SurfacePressure, const Array1DReal &TidalPotential,
+                      const Array1DReal &SelfAttractionLoading, bool Displaced, I4 KDisp, hipStream_t S, I4 TIndex = 0,
+                      I4 SIndex = 1);
 
    // ---- the reference's signatures (VertCoord.h:180-206): on this object's `Stream` (default: the null stream)
    hipStream_t Stream = nullptr;

@@ -21,6 +21,7 @@
 #include "Eos.h"
 #include "TriDiagSolvers.h"
 #include "VertMix.h"
+#include "PressureGrad.h"
 
 #include <cstring>
 #include <map>
@@ -70,6 +71,9 @@ struct omg_eos {
 };
 struct omg_vertmix {
    std::unique_ptr<VertMix> X;
+};
+struct omg_pgrad {
+   std::unique_ptr<PressureGrad> P;
 };
 
 static thread_local std::string LastError;
@@ -1761,6 +1765,91 @@ int omg_vertmix_device_ptr(const omg_vertmix *x, const char *name, double **dev,
    *dev = R.Ptr;
    if (n)
       *n = R.size();
+   OMG_CATCH
+}
+
+// ---- PressureGrad (PressureGrad.h)
+int omg_pgrad_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, omg_pgrad **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   auto *R = new omg_pgrad;
+   try {
+      R->P.reset(new PressureGrad("Default", m->M.get(), v ? v->V.get() : nullptr, e ? e->E.get() : nullptr));
+   } catch (...) {
+      delete R;
+      throw;
+   }
+   *out = R;
+   OMG_CATCH
+}
+int omg_pgrad_destroy(omg_pgrad *p) {
+   delete p;
+   return 0;
+}
+int omg_pgrad_update_column(omg_pgrad *p, const double *layer_thickness, const double *tracers, int ntracers,
+                            void *stream) {
+   OMG_TRY
+   OMG_ARG(p && layer_thickness && tracers && ntracers >= 2);
+   const HorzMesh *M = p->P->Mesh;
+   const int K       = p->P->NVertLayers;
+   Array3DReal Tr;
+   Tr.Ptr    = const_cast<Real *>(tracers);
+   Tr.Ext[0] = ntracers, Tr.Ext[1] = M->NCellsSize, Tr.Ext[2] = K;
+   Tr.Pitch  = levelPitch(K);
+   p->P->updateColumn(levelView(layer_thickness, M->NCellsSize, K), Tr, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_pgrad_compute(omg_pgrad *p, double *tend, void *stream) {
+   OMG_TRY
+   OMG_ARG(p && tend);
+   p->P->computePressureGrad(levelView(tend, p->P->Mesh->NEdgesSize, p->P->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_pgrad_compute_arrays(omg_pgrad *p, double *tend, const double *pressure_mid, const double *geopotential_mid,
+                             const double *spec_vol, void *stream) {
+   OMG_TRY
+   OMG_ARG(p && tend && pressure_mid && geopotential_mid && spec_vol);
+   const HorzMesh *M = p->P->Mesh;
+   const int K       = p->P->NVertLayers;
+   p->P->computePressureGrad(levelView(tend, M->NEdgesSize, K), levelView(pressure_mid, M->NCellsSize, K),
+                             levelView(geopotential_mid, M->NCellsSize, K), levelView(spec_vol, M->NCellsSize, K),
+                             (hipStream_t)stream);
+   OMG_CATCH
+}
+static ArrRef pgradLookup(const PressureGrad &P, const std::string &Name) {
+   if (Name == "SurfacePressure")
+      return arrRef(P.SurfacePressure);
+   if (Name == "TidalPotential")
+      return arrRef(P.TidalPotential);
+   if (Name == "SelfAttractionLoading")
+      return arrRef(P.SelfAttractionLoading);
+   OMEGA_ABORT("PressureGrad: no array named " + Name);
+}
+int omg_pgrad_device_ptr(const omg_pgrad *p, const char *name, double **dev, size_t *n) {
+   OMG_TRY
+   OMG_ARG(p && name && dev);
+   const ArrRef R = pgradLookup(*p->P, name);
+   *dev = R.Ptr;
+   if (n)
+      *n = R.size();
+   OMG_CATCH
+}
+int omg_pgrad_copy_to_device(omg_pgrad *p, const char *name, const double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(p && name && host);
+   refCopyToDevice(pgradLookup(*p->P, name), name, host, n);
+   OMG_CATCH
+}
+int omg_pgrad_copy_to_host(const omg_pgrad *p, const char *name, double *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(p && name && host);
+   refCopyToHost(pgradLookup(*p->P, name), name, host, n);
+   OMG_CATCH
+}
+int omg_tend_attach_pressure_grad(omg_tend *t, omg_pgrad *p) {
+   OMG_TRY
+   OMG_ARG(t);
+   t->T->attachPressureGrad(p ? p->P.get() : nullptr);
    OMG_CATCH
 }
 
