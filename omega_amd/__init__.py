@@ -116,6 +116,29 @@ def _pi(a):
     return a.ctypes.data_as(PI)
 
 
+class _Handle:
+    """Base of every class that owns a library handle: `self.h`, made by `_create`, freed once through the class's
+    `_destroy` symbol when the object goes (or by the `close()` of the classes that have one)."""
+    _destroy = None
+
+    def _create(self, symbol: str, *args):
+        """self.h from a create / open function whose last argument receives the handle"""
+        h = C.c_void_p()
+        _chk(getattr(lib(), symbol)(*args, C.byref(h)))
+        self.h = h
+
+    def _release(self):
+        if self.h:
+            getattr(lib(), self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
 def device_count() -> int:
     n = C.c_int(0)
     _chk(lib().omg_device_count(C.byref(n)))
@@ -150,11 +173,11 @@ class Stream:
             pass
 
 
-class Event:
+class Event(_Handle):
+    _destroy = "omg_event_destroy"
+
     def __init__(self):
-        h = C.c_void_p()
-        _chk(lib().omg_event_create(C.byref(h)))
-        self.h = h
+        self._create("omg_event_create")
 
     def record(self, stream: "Stream | None"):
         _chk(lib().omg_event_record(self.h, stream.h if stream else None))
@@ -163,12 +186,6 @@ class Event:
         ms = C.c_float()
         _chk(lib().omg_event_elapsed_ms(self.h, stop.h, C.byref(ms)))
         return ms.value
-
-    def __del__(self):
-        try:
-            lib().omg_event_destroy(self.h)
-        except Exception:
-            pass
 
 
 def _sh(s):
@@ -269,14 +286,13 @@ def read_restart(path, decomp, mesh, state, tracers, K, NT):
         lib().omg_restart_close(f)
 
 
-class MeshFile:
+class MeshFile(_Handle):
     """An MPAS mesh / initial-state file (NetCDF classic CDF-1/2/5) opened by the library's own reader;
     `.gm` is the GlobalMesh to build a Decomp from (the arrays live inside the file handle)."""
+    _destroy = "omg_mesh_file_close"
 
     def __init__(self, path: str, mesh: bool = True):
-        h = C.c_void_p()
-        _chk(lib().omg_mesh_file_open(os.fsencode(path), C.byref(h)))
-        self.h = h
+        self._create("omg_mesh_file_open", os.fsencode(path))
         self.gm = None
         if not mesh:   # a state-only file (initial conditions, forcing): variables through read()
             return
@@ -318,12 +334,6 @@ class MeshFile:
             shape = shp.get(n, (el,))
             out[n] = np.ctypeslib.as_array(p, shape=(int(np.prod(shape)),)).reshape(shape).copy()
         return out
-
-    def __del__(self):
-        try:
-            lib().omg_mesh_file_close(self.h)
-        except Exception:
-            pass
 
 
 class DeviceBuffer:
@@ -463,18 +473,18 @@ def partition_cells(gm: GlobalMesh, nparts: int, method: str = "graph"):
     return out, cut.value
 
 
-class Decomp:
+class Decomp(_Handle):
+    _destroy = "omg_decomp_destroy"
+
     def __init__(self, gm: GlobalMesh, nparts: int = 1, mytask: int = 0, halo_width: int = 3, cell_task=None,
                  local_order: str = "global"):
         """local_order: "global" (the reference's numbering by global id), "curve" (Morton curve through the cell
         centres: spatially compact local numbering whatever the file's order), "hilbert" (Hilbert curve) or "kd" (k-d
         order: compact tiles on the surface -- what spheres want)."""
         self.gm = gm
-        h = C.c_void_p()
         ct = None if cell_task is None else np.ascontiguousarray(cell_task, dtype=np.int32)
-        _chk(lib().omg_decomp_create_ordered(C.byref(gm.s), nparts, mytask, halo_width, _pi(ct),
-                                             {"global": 0, "curve": 1, "hilbert": 2, "kd": 3}[local_order], C.byref(h)))
-        self.h = h
+        self._create("omg_decomp_create_ordered", C.byref(gm.s), nparts, mytask, halo_width, _pi(ct),
+                     {"global": 0, "curve": 1, "hilbert": 2, "kd": 3}[local_order])
 
     def get_int(self, name: str) -> int:
         v = C.c_int32()
@@ -492,16 +502,11 @@ class Decomp:
         _chk(lib().omg_decomp_get_array(self.h, name.encode(), _pi(out), C.c_size_t(out.size)))
         return out
 
-    def __del__(self):
-        try:
-            lib().omg_decomp_destroy(self.h)
-        except Exception:
-            pass
 
-
-class RcclComm:
+class RcclComm(_Handle):
     """RCCL communicator owned by the library (omega_amd/csrc/Rccl.cpp).  `unique_id()` on rank 0, distribute the
     128 bytes by any side channel, then every rank constructs RcclComm(id, nranks, rank) after device_init."""
+    _destroy = "omg_rccl_destroy"
 
     ID_BYTES = 128
 
@@ -513,9 +518,7 @@ class RcclComm:
 
     def __init__(self, unique_id: bytes, nranks: int, rank: int):
         assert len(unique_id) == RcclComm.ID_BYTES
-        h = C.c_void_p()
-        _chk(lib().omg_rccl_create(C.create_string_buffer(unique_id, RcclComm.ID_BYTES), nranks, rank, C.byref(h)))
-        self.h = h
+        self._create("omg_rccl_create", C.create_string_buffer(unique_id, RcclComm.ID_BYTES), nranks, rank)
 
     def info(self) -> dict:
         n, r, v, e = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
@@ -534,28 +537,19 @@ class RcclComm:
     def close(self):
         """omg_rccl_destroy (ncclCommDestroy): explicitly, while the peers are still there -- not left to a destructor at
         interpreter exit"""
-        if self.h:
-            lib().omg_rccl_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._release()
 
 
-class PeerWire:
+class PeerWire(_Handle):
     """Direct peer-copy halo wire owned by the library (omega_amd/csrc/PeerWire.cpp): mailbox + flags exported with
     HIP IPC, exchanges fully stream-ordered.  Create after device_init, all_gather `handle()` over any side channel,
     `connect(list_of_handles_in_rank_order)`, then `Halo.use_peer(wire)`."""
+    _destroy = "omg_peer_destroy"
 
     HANDLE_BYTES = 160
 
     def __init__(self, nranks: int, rank: int, mailbox_bytes: int):
-        h = C.c_void_p()
-        _chk(lib().omg_peer_create(nranks, rank, C.c_size_t(mailbox_bytes), C.byref(h)))
-        self.h = h
+        self._create("omg_peer_create", nranks, rank, C.c_size_t(mailbox_bytes))
         self.nranks = nranks
 
     def handle(self) -> bytes:
@@ -577,23 +571,15 @@ class PeerWire:
         _chk(lib().omg_peer_set_timeout(self.h, C.c_double(seconds)))
 
     def close(self):
-        if self.h:
-            lib().omg_peer_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._release()
 
 
-class Halo:
+class Halo(_Handle):
+    _destroy = "omg_halo_destroy"
+
     def __init__(self, decomp: Decomp):
         self.decomp = decomp
-        h = C.c_void_p()
-        _chk(lib().omg_halo_create(decomp.h, C.byref(h)))
-        self.h = h
+        self._create("omg_halo_create", decomp.h)
         self._cb = None
         self._bufs = None
 
@@ -674,12 +660,6 @@ class Halo:
             _chk(lib().omg_halo_exchange_bytes(self.h, C.c_void_p(dev_ptr), elem_bytes, nt, rows_size, k, row_pitch, elem,
                                                _sh(stream)))
 
-    def __del__(self):
-        try:
-            lib().omg_halo_destroy(self.h)
-        except Exception:
-            pass
-
 
 _MESH_I4 = {"CellsOnCell": ("C", "ME"), "EdgesOnCell": ("C", "ME"), "NEdgesOnCell": ("C",),
             "VerticesOnCell": ("C", "ME"), "CellsOnEdge": ("E", 2), "EdgesOnEdge": ("E", "ME2"),
@@ -694,12 +674,12 @@ for _el, _d in (("Cell", "C"), ("Edge", "E"), ("Vertex", "V")):
         _MESH_R8[_p + _el] = (_d,)
 
 
-class HorzMesh:
+class HorzMesh(_Handle):
+    _destroy = "omg_mesh_destroy"
+
     def __init__(self, decomp: Decomp, nvertlayers: int, host_only: bool = False):
         self.decomp = decomp
-        h = C.c_void_p()
-        _chk(lib().omg_mesh_create(decomp.h, nvertlayers, int(host_only), C.byref(h)))
-        self.h = h
+        self._create("omg_mesh_create", decomp.h, nvertlayers, int(host_only))
         self._dims = None
 
     def get_int(self, name: str) -> int:
@@ -744,12 +724,6 @@ class HorzMesh:
 
     def set_fvertex(self, values: np.ndarray):
         _chk(lib().omg_mesh_set_fvertex(self.h, _pd(np.ascontiguousarray(values, dtype=np.float64))))
-
-    def __del__(self):
-        try:
-            lib().omg_mesh_destroy(self.h)
-        except Exception:
-            pass
 
 
 class HorzOperators:
@@ -799,12 +773,12 @@ def default_config(**over) -> TendConfig:
     return c
 
 
-class OceanState:
+class OceanState(_Handle):
+    _destroy = "omg_state_destroy"
+
     def __init__(self, mesh: HorzMesh, halo: Halo | None, nvertlayers: int, ntimelevels: int = 2):
         self.mesh, self.halo, self.K = mesh, halo, nvertlayers
-        h = C.c_void_p()
-        _chk(lib().omg_state_create(mesh.h, halo.h if halo else None, nvertlayers, ntimelevels, C.byref(h)))
-        self.h = h
+        self._create("omg_state_create", mesh.h, halo.h if halo else None, nvertlayers, ntimelevels)
 
     def copy_to_device(self, h=None, u=None, time_level: int = 0):
         _chk(lib().omg_state_copy_to_device(self.h, time_level, _pd(h), _pd(u)))
@@ -826,19 +800,13 @@ class OceanState:
     def update_time_levels(self, stream=None):
         _chk(lib().omg_state_update_time_levels(self.h, _sh(stream)))
 
-    def __del__(self):
-        try:
-            lib().omg_state_destroy(self.h)
-        except Exception:
-            pass
 
+class Tracers(_Handle):
+    _destroy = "omg_tracers_destroy"
 
-class Tracers:
     def __init__(self, mesh: HorzMesh, halo: Halo | None, nvertlayers: int, ntracers: int, ntimelevels: int = 2):
         self.mesh, self.K, self.NT = mesh, nvertlayers, ntracers
-        h = C.c_void_p()
-        _chk(lib().omg_tracers_create(mesh.h, halo.h if halo else None, nvertlayers, ntracers, ntimelevels, C.byref(h)))
-        self.h = h
+        self._create("omg_tracers_create", mesh.h, halo.h if halo else None, nvertlayers, ntracers, ntimelevels)
 
     def copy_to_device(self, tr, time_level: int = 0):
         _chk(lib().omg_tracers_copy_to_device(self.h, time_level, _pd(tr)))
@@ -860,11 +828,38 @@ class Tracers:
     def update_time_levels(self, stream=None):
         _chk(lib().omg_tracers_update_time_levels(self.h, _sh(stream)))
 
-    def __del__(self):
-        try:
-            lib().omg_tracers_destroy(self.h)
-        except Exception:
-            pass
+
+class _NamedArrays:
+    """get / set / device_ptr of a class whose library object has named device arrays: `_arrays` is the prefix of its
+    <prefix>_copy_to_host / _copy_to_device / _device_ptr symbols and `_shape(name)` the class's own shape rule for a
+    host copy.  A name in `_i4` (VertCoord) is an int32 array and goes through the <prefix>_copy_to_*_i4 symbols."""
+    _arrays = None
+    _i4 = ()
+
+    def _array_call(self, op: str, name: str, *args):
+        _chk(getattr(lib(), f"{self._arrays}_{op}")(self.h, name.encode(), *args))
+
+    def get(self, name: str) -> np.ndarray:
+        if name in self._i4:
+            out = np.zeros(self._shape(name), dtype=np.int32)
+            self._array_call("copy_to_host_i4", name, _pi(out), C.c_size_t(out.size))
+        else:
+            out = np.zeros(self._shape(name))
+            self._array_call("copy_to_host", name, _pd(out), C.c_size_t(out.size))
+        return out
+
+    def set(self, name: str, values: np.ndarray):
+        if name in self._i4:
+            v = np.ascontiguousarray(values, dtype=np.int32)
+            self._array_call("copy_to_device_i4", name, _pi(v), C.c_size_t(v.size))
+        else:
+            v = np.ascontiguousarray(values, dtype=np.float64)
+            self._array_call("copy_to_device", name, _pd(v), C.c_size_t(v.size))
+
+    def device_ptr(self, name: str) -> int:
+        p = PD()
+        self._array_call("device_ptr", name, C.byref(p), None)
+        return C.cast(p, C.c_void_p).value
 
 
 AUX_SHAPES = {"KineticEnergyCell": "C", "VelocityDivCell": "C", "FluxLayerThickEdge": "E", "MeanLayerThickEdge": "E",
@@ -874,12 +869,12 @@ AUX_SHAPES = {"KineticEnergyCell": "C", "VelocityDivCell": "C", "FluxLayerThickE
               "ZonalStressCell": "C1", "MeridStressCell": "C1"}
 
 
-class AuxiliaryState:
+class AuxiliaryState(_Handle, _NamedArrays):
+    _destroy, _arrays = "omg_aux_destroy", "omg_aux"
+
     def __init__(self, mesh: HorzMesh, halo: Halo | None, nvertlayers: int, ntracers: int):
         self.mesh, self.K, self.NT = mesh, nvertlayers, ntracers
-        h = C.c_void_p()
-        _chk(lib().omg_aux_create(mesh.h, halo.h if halo else None, nvertlayers, ntracers, C.byref(h)))
-        self.h = h
+        self._create("omg_aux_create", mesh.h, halo.h if halo else None, nvertlayers, ntracers)
 
     def set_options(self, flux_thickness_upwind=False, flux_tracer_upwind=False, wind_interp_isotropic=True):
         _chk(lib().omg_aux_set_options(self.h, int(flux_thickness_upwind), int(flux_tracer_upwind),
@@ -901,34 +896,38 @@ class AuxiliaryState:
             return (nt, rows[s[1]], K)
         return (rows[s[0]],)
 
-    def get(self, name: str) -> np.ndarray:
-        out = np.zeros(self._shape(name))
-        _chk(lib().omg_aux_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
-        return out
 
-    def set(self, name: str, values: np.ndarray):
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        _chk(lib().omg_aux_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
+def _stage_levels(x, lead: tuple, k: int, keep: "list | None" = None):
+    """A level-indexed array as (device pointer, staged buffer or None): an int is taken as the device address of
+    [*lead][level_pitch(k)] doubles and passed through; a numpy array [*lead][k] is staged into a padded device copy
+    (also appended to `keep`, if given, to stay alive there)."""
+    if isinstance(x, (int, np.integer)):
+        return C.c_void_p(int(x)), None
+    a = np.asarray(x, dtype=np.float64)
+    assert a.shape == lead + (k,), f"expected shape {lead + (k,)}, got {a.shape}"
+    pad = np.zeros(lead + (level_pitch(k),))
+    pad[..., :k] = a
+    b = DeviceBuffer(pad)
+    if keep is not None:
+        keep.append(b)
+    return C.c_void_p(b.ptr), b
 
-    def __del__(self):
-        try:
-            lib().omg_aux_destroy(self.h)
-        except Exception:
-            pass
+
+def _read_back(buf, k: int, stream):
+    """The result of an in-place call on a buffer staged by _stage_levels, without the row padding, once the stream
+    and the device have drained; None for None (a device address was passed: nothing to return)."""
+    if buf is None:
+        return None
+    if stream is not None:
+        stream.synchronize()
+    device_synchronize()
+    return buf.to_host()[..., :k]
 
 
 def _level_dev(x, rows: int, k: int, keep: list):
     """A level-indexed input as a device pointer: an int is taken as a device address of [rows][level_pitch(k)]
     doubles, a numpy array [rows][k] is staged into a padded device copy (kept alive in `keep`)."""
-    if isinstance(x, (int, np.integer)):
-        return C.c_void_p(int(x))
-    a = np.asarray(x, dtype=np.float64)
-    assert a.shape == (rows, k), f"expected shape {(rows, k)}, got {a.shape}"
-    pad = np.zeros((rows, level_pitch(k)))
-    pad[:, :k] = a
-    b = DeviceBuffer(pad)
-    keep.append(b)
-    return C.c_void_p(b.ptr)
+    return _stage_levels(x, (rows,), k, keep)[0]
 
 
 def _cell_dev(x, rows: int, keep: list):
@@ -952,17 +951,16 @@ def tracer_rows_ptr(tracers: Tracers, index: int, time_level: int = 0) -> int:
     return tracers.device_ptr(time_level) + index * tracers.mesh.NCellsSize * level_pitch(tracers.K) * 8
 
 
-class Eos:
+class Eos(_Handle, _NamedArrays):
     """Eos (omega_amd/csrc/Eos.h): specific volume, linear or TEOS-10.  Level-indexed inputs are numpy arrays
     [NCellsSize][K] or device addresses of [NCellsSize][level_pitch(K)] doubles."""
+    _destroy, _arrays = "omg_eos_destroy", "omg_eos"
 
     def __init__(self, mesh: HorzMesh, nvertlayers: int, eos_type: str = "teos10", drhodt: float = -0.2,
                  drhods: float = 0.8, rhot0s0: float = 1000.0):
         self.mesh, self.K = mesh, nvertlayers
-        h = C.c_void_p()
-        _chk(lib().omg_eos_create(mesh.h, nvertlayers, eos_type.encode(), C.c_double(drhodt), C.c_double(drhods),
-                                  C.c_double(rhot0s0), C.byref(h)))
-        self.h = h
+        self._create("omg_eos_create", mesh.h, nvertlayers, eos_type.encode(), C.c_double(drhodt), C.c_double(drhods),
+                     C.c_double(rhot0s0))
 
     def compute_spec_vol(self, conserv_temp, abs_salinity, pressure, p_scale: float = 1.0, stream=None):
         keep, n = [], self.mesh.NCellsSize
@@ -982,25 +980,8 @@ class Eos:
         if keep:
             device_synchronize()
 
-    def get(self, name: str) -> np.ndarray:
-        out = np.zeros((self.mesh.NCellsSize, self.K))
-        _chk(lib().omg_eos_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
-        return out
-
-    def set(self, name: str, values: np.ndarray):
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        _chk(lib().omg_eos_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
-
-    def device_ptr(self, name: str) -> int:
-        p = PD()
-        _chk(lib().omg_eos_device_ptr(self.h, name.encode(), C.byref(p), None))
-        return C.cast(p, C.c_void_p).value
-
-    def __del__(self):
-        try:
-            lib().omg_eos_destroy(self.h)
-        except Exception:
-            pass
+    def _shape(self, name):
+        return (self.mesh.NCellsSize, self.K)
 
 
 VCOORD_SHAPES = {"PressureInterface": "CK1", "PressureMid": "CK", "ZInterface": "CK1", "ZMid": "CK",
@@ -1011,10 +992,11 @@ VCOORD_I4 = {"MinLayerCell": "C", "MaxLayerCell": "C", "MinLayerEdgeTop": "E", "
              "MinLayerVertexBot": "V", "MaxLayerVertexBot": "V"}
 
 
-class VertCoord:
+class VertCoord(_Handle, _NamedArrays):
     """VertCoord (omega_amd/csrc/VertCoord.h): layer ranges, pressure, z-height, geopotential, target thickness and
     the fused column pass.  min_level_cell / max_level_cell: the mesh file's global 1-based arrays [nCells], gathered
     through `decomp` (default: the mesh's)."""
+    _destroy, _arrays, _i4 = "omg_vcoord_destroy", "omg_vcoord", VCOORD_I4
 
     def __init__(self, mesh: HorzMesh, nvertlayers: int, rho0: float = 1026.0, movement_weight_type: str = "Uniform",
                  min_level_cell=None, max_level_cell=None, decomp: Decomp | None = None):
@@ -1022,10 +1004,8 @@ class VertCoord:
         d = decomp if decomp is not None else getattr(mesh, "decomp", None)
         mn = None if min_level_cell is None else np.ascontiguousarray(min_level_cell, dtype=np.int32)
         mx = None if max_level_cell is None else np.ascontiguousarray(max_level_cell, dtype=np.int32)
-        h = C.c_void_p()
-        _chk(lib().omg_vcoord_create(mesh.h, d.h if d is not None else None, nvertlayers, C.c_double(rho0),
-                                     movement_weight_type.encode(), _pi(mn), _pi(mx), C.byref(h)))
-        self.h = h
+        self._create("omg_vcoord_create", mesh.h, d.h if d is not None else None, nvertlayers, C.c_double(rho0),
+                     movement_weight_type.encode(), _pi(mn), _pi(mx))
 
     def min_max_layer_edge(self, stream=None):
         _chk(lib().omg_vcoord_min_max_layer_edge(self.h, _sh(stream)))
@@ -1071,8 +1051,9 @@ class VertCoord:
         if keep:
             device_synchronize()
 
-    def _shape(self, spec):
+    def _shape(self, name):
         m = self.mesh
+        spec = VCOORD_I4[name] if name in VCOORD_I4 else VCOORD_SHAPES.get(name, "CK")
         rows = {"C": m.NCellsSize, "E": m.NEdgesSize, "V": m.NVerticesSize}
         if spec == "K":
             return (self.K,)
@@ -1082,38 +1063,10 @@ class VertCoord:
             return (rows["C"], self.K + 1)
         return (rows[spec],)
 
-    def get(self, name: str) -> np.ndarray:
-        if name in VCOORD_I4:
-            out = np.zeros(self._shape(VCOORD_I4[name]), dtype=np.int32)
-            _chk(lib().omg_vcoord_copy_to_host_i4(self.h, name.encode(), _pi(out), C.c_size_t(out.size)))
-            return out
-        out = np.zeros(self._shape(VCOORD_SHAPES.get(name, "CK")))
-        _chk(lib().omg_vcoord_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
-        return out
-
-    def set(self, name: str, values: np.ndarray):
-        if name in VCOORD_I4:
-            v = np.ascontiguousarray(values, dtype=np.int32)
-            _chk(lib().omg_vcoord_copy_to_device_i4(self.h, name.encode(), _pi(v), C.c_size_t(v.size)))
-            return
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        _chk(lib().omg_vcoord_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
-
-    def device_ptr(self, name: str) -> int:
-        p = PD()
-        _chk(lib().omg_vcoord_device_ptr(self.h, name.encode(), C.byref(p), None))
-        return C.cast(p, C.c_void_p).value
-
     def get_real(self, name: str) -> float:
         v = C.c_double()
         _chk(lib().omg_vcoord_get_real(self.h, name.encode(), C.byref(v)))
         return v.value
-
-    def __del__(self):
-        try:
-            lib().omg_vcoord_destroy(self.h)
-        except Exception:
-            pass
 
 
 class VertMixConfig(C.Structure):
@@ -1136,20 +1089,18 @@ def vertmix_config(**over) -> VertMixConfig:
     return c
 
 
-class VertMix:
+class VertMix(_Handle, _NamedArrays):
     """VertMix (omega_amd/csrc/VertMix.h): N^2, mixing coefficients and the implicit vertical diffusion of tracers and
     normal velocity.  `config` fields as in VertMixConfig (e.g. ShearExponent=3.0, EnableConvectiveMix=False).
     Level-indexed inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles; the in-place
     solves take a device address (solved asynchronously on `stream`) or a numpy array (staged, solved, returned)."""
+    _destroy, _arrays = "omg_vertmix_destroy", "omg_vertmix"
 
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", **config):
         self.mesh, self.vcoord = mesh, vcoord
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
         self.config = vertmix_config(**config)
-        h = C.c_void_p()
-        _chk(lib().omg_vertmix_create(mesh.h, vcoord.h if vcoord is not None else None, C.byref(self.config),
-                                      C.byref(h)))
-        self.h = h
+        self._create("omg_vertmix_create", mesh.h, vcoord.h if vcoord is not None else None, C.byref(self.config))
 
     def compute_bvf(self, eos: Eos, stream=None):
         _chk(lib().omg_vertmix_compute_bvf(self.h, eos.h, _sh(stream)))
@@ -1163,113 +1114,49 @@ class VertMix:
         if keep:
             device_synchronize()
 
-    def _in_place(self, x, rows_shape):
-        """(device pointer, staged buffer or None) for an in-place array"""
-        if isinstance(x, (int, np.integer)):
-            return C.c_void_p(int(x)), None
-        a = np.asarray(x, dtype=np.float64)
-        assert a.shape == rows_shape + (self.K,), f"expected shape {rows_shape + (self.K,)}, got {a.shape}"
-        pad = np.zeros(rows_shape + (level_pitch(self.K),))
-        pad[..., : self.K] = a
-        b = DeviceBuffer(pad)
-        return C.c_void_p(b.ptr), b
-
-    def _back(self, buf, stream):
-        if buf is None:
-            return None
-        if stream is not None:
-            stream.synchronize()
-        device_synchronize()
-        return buf.to_host()[..., : self.K]
-
     def apply_tracers(self, layer_thickness, tracers, ntracers: int, dt: float, stream=None):
         """Backward-Euler diffusion of tracers [ntracers][NCellsSize][K] with VertDiff, all in one pass"""
         keep, n = [], self.mesh.NCellsSize
         h = _level_dev(layer_thickness, n, self.K, keep)
-        p, buf = self._in_place(tracers, (int(ntracers), n))
+        p, buf = _stage_levels(tracers, (int(ntracers), n), self.K)
         _chk(lib().omg_vertmix_apply_tracers(self.h, h, p, int(ntracers), C.c_double(dt), _sh(stream)))
-        return self._back(buf, stream)
+        return _read_back(buf, self.K, stream)
 
     def apply_velocity(self, layer_thickness, normal_velocity, dt: float, stream=None):
         """Backward-Euler diffusion of the normal velocity [NEdgesSize][K] with VertVisc averaged to the edges"""
         keep = []
         h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
-        p, buf = self._in_place(normal_velocity, (self.mesh.NEdgesSize,))
+        p, buf = _stage_levels(normal_velocity, (self.mesh.NEdgesSize,), self.K)
         _chk(lib().omg_vertmix_apply_velocity(self.h, h, p, C.c_double(dt), _sh(stream)))
-        return self._back(buf, stream)
+        return _read_back(buf, self.K, stream)
 
-    def get(self, name: str) -> np.ndarray:
-        out = np.zeros((self.mesh.NCellsSize, self.K))
-        _chk(lib().omg_vertmix_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
-        return out
-
-    def set(self, name: str, values: np.ndarray):
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        _chk(lib().omg_vertmix_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
-
-    def device_ptr(self, name: str) -> int:
-        p = PD()
-        _chk(lib().omg_vertmix_device_ptr(self.h, name.encode(), C.byref(p), None))
-        return C.cast(p, C.c_void_p).value
-
-    def __del__(self):
-        try:
-            lib().omg_vertmix_destroy(self.h)
-        except Exception:
-            pass
+    def _shape(self, name):
+        return (self.mesh.NCellsSize, self.K)
 
 
 PGRAD_ARRAYS = ("SurfacePressure", "TidalPotential", "SelfAttractionLoading")
 
 
-class PressureGrad:
+class PressureGrad(_Handle, _NamedArrays):
     """PressureGrad (omega_amd/csrc/PressureGrad.h): the layered-ocean pressure-gradient force on edges,
     Tend -= EdgeMask * (grad GeopotentialMid + 0.5 (SpecVol0 + SpecVol1) grad PressureMid), from the column fields of
     `vcoord` and `eos`.  Level-indexed inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)]
     doubles; `tend` is accumulated in place: a device address (asynchronous on `stream`) or a numpy array (staged,
     computed, returned)."""
+    _destroy, _arrays = "omg_pgrad_destroy", "omg_pgrad"
 
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None"):
         self.mesh, self.vcoord, self.eos = mesh, vcoord, eos
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        h = C.c_void_p()
-        _chk(lib().omg_pgrad_create(mesh.h, vcoord.h if vcoord is not None else None,
-                                    eos.h if eos is not None else None, C.byref(h)))
-        self.h = h
-
-    def _tend(self, tend):
-        if isinstance(tend, (int, np.integer)):
-            return C.c_void_p(int(tend)), None
-        a = np.asarray(tend, dtype=np.float64)
-        shape = (self.mesh.NEdgesSize, self.K)
-        assert a.shape == shape, f"expected shape {shape}, got {a.shape}"
-        pad = np.zeros((shape[0], level_pitch(self.K)))
-        pad[:, : self.K] = a
-        b = DeviceBuffer(pad)
-        return C.c_void_p(b.ptr), b
-
-    def _back(self, buf, stream):
-        if buf is None:
-            return None
-        if stream is not None:
-            stream.synchronize()
-        device_synchronize()
-        return buf.to_host()[:, : self.K]
+        self._create("omg_pgrad_create", mesh.h, vcoord.h if vcoord is not None else None,
+                     eos.h if eos is not None else None)
 
     def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
         """The fused column pass from raw arrays: thickness [NCellsSize][K], tracers [ntracers][NCellsSize][K]
         (temperature 0, salinity 1), with this object's SurfacePressure / TidalPotential / SelfAttractionLoading."""
         keep, n = [], self.mesh.NCellsSize
         h = _level_dev(layer_thickness, n, self.K, keep)
-        if isinstance(tracers, (int, np.integer)):
-            t = C.c_void_p(int(tracers))
-        else:
-            a = np.asarray(tracers, dtype=np.float64)
-            assert a.shape == (int(ntracers), n, self.K), f"expected shape {(int(ntracers), n, self.K)}, got {a.shape}"
-            pad = np.zeros((int(ntracers), n, level_pitch(self.K)))
-            pad[..., : self.K] = a
-            keep.append(DeviceBuffer(pad))
-            t = C.c_void_p(keep[-1].ptr)
+        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
         _chk(lib().omg_pgrad_update_column(self.h, h, t, int(ntracers), _sh(stream)))
         if keep:
             device_synchronize()
@@ -1279,7 +1166,7 @@ class PressureGrad:
         VertCoord's and the Eos's arrays as they stand."""
         given = [x is not None for x in (pressure_mid, geopotential_mid, spec_vol)]
         assert all(given) or not any(given), "give PressureMid, GeopotentialMid and SpecVol, or none of them"
-        p, buf = self._tend(tend)
+        p, buf = _stage_levels(tend, (self.mesh.NEdgesSize,), self.K)
         keep, n = [], self.mesh.NCellsSize
         if all(given):
             _chk(lib().omg_pgrad_compute_arrays(self.h, p, _level_dev(pressure_mid, n, self.K, keep),
@@ -1289,27 +1176,10 @@ class PressureGrad:
             _chk(lib().omg_pgrad_compute(self.h, p, _sh(stream)))
         if keep:
             device_synchronize()
-        return self._back(buf, stream)
+        return _read_back(buf, self.K, stream)
 
-    def get(self, name: str) -> np.ndarray:
-        out = np.zeros(self.mesh.NCellsSize)
-        _chk(lib().omg_pgrad_copy_to_host(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
-        return out
-
-    def set(self, name: str, values: np.ndarray):
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        _chk(lib().omg_pgrad_copy_to_device(self.h, name.encode(), _pd(v), C.c_size_t(v.size)))
-
-    def device_ptr(self, name: str) -> int:
-        p = PD()
-        _chk(lib().omg_pgrad_device_ptr(self.h, name.encode(), C.byref(p), None))
-        return C.cast(p, C.c_void_p).value
-
-    def __del__(self):
-        try:
-            lib().omg_pgrad_destroy(self.h)
-        except Exception:
-            pass
+    def _shape(self, name):
+        return (self.mesh.NCellsSize,)
 
 
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
@@ -1321,17 +1191,17 @@ def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edg
     return bool(ok.value), why.value.decode()
 
 
-class Tendencies:
+class Tendencies(_Handle):
+    _destroy = "omg_tend_destroy"
+
     def __init__(self, mesh: HorzMesh, nvertlayers: int, ntracers: int, config: TendConfig | None = None,
                  allow_reference_structured: bool = False):
         """Raises for a mesh outside the fused RHS (fused_limit) unless allow_reference_structured: then
         compute_all_tendencies takes the reference-structured 23-launch path."""
         self.mesh, self.K, self.NT = mesh, nvertlayers, ntracers
         self.config = config if config is not None else default_config()
-        h = C.c_void_p()
-        create = lib().omg_tend_create_reference_structured if allow_reference_structured else lib().omg_tend_create
-        _chk(create(mesh.h, nvertlayers, ntracers, C.byref(self.config), C.byref(h)))
-        self.h = h
+        self._create("omg_tend_create_reference_structured" if allow_reference_structured else "omg_tend_create",
+                     mesh.h, nvertlayers, ntracers, C.byref(self.config))
 
     def set_fused(self, on: bool):
         _chk(lib().omg_tend_set_fused(self.h, int(on)))
@@ -1434,21 +1304,15 @@ class Tendencies:
         _chk(lib().omg_tend_copy_to_host(self.h, which, _pd(out), C.c_size_t(out.size)))
         return out
 
-    def __del__(self):
-        try:
-            lib().omg_tend_destroy(self.h)
-        except Exception:
-            pass
 
+class TimeStepper(_Handle):
+    _destroy = "omg_stepper_destroy"
 
-class TimeStepper:
     def __init__(self, kind: str, dt: float, tend: Tendencies, aux: AuxiliaryState, mesh: HorzMesh,
                  halo: Halo | None, tracers: Tracers):
         self.refs = (tend, aux, mesh, halo, tracers)
-        h = C.c_void_p()
-        _chk(lib().omg_stepper_create(kind.encode(), C.c_double(dt), tend.h, aux.h, mesh.h, halo.h if halo else None,
-                                      tracers.h, C.byref(h)))
-        self.h = h
+        self._create("omg_stepper_create", kind.encode(), C.c_double(dt), tend.h, aux.h, mesh.h, halo.h if halo else None,
+                     tracers.h)
 
     def do_step(self, state: OceanState, stream=None):
         _chk(lib().omg_stepper_do_step(self.h, state.h, _sh(stream)))
@@ -1473,12 +1337,6 @@ class TimeStepper:
     def set_option(self, name: str, value: bool):
         """RungeKutta4: "FuseStageUpdates" (default on), "StoreStageTendencies" (default off)."""
         _chk(lib().omg_stepper_set_option(self.h, name.encode(), int(value)))
-
-    def __del__(self):
-        try:
-            lib().omg_stepper_destroy(self.h)
-        except Exception:
-            pass
 
 
 def update_by_tend(out_ptr: int, in_ptr: int, tend_ptr: int, coeff: float, n_rows: int, k: int, stream_handle=None):

@@ -24,6 +24,7 @@
 #include "PressureGrad.h"
 
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 
@@ -105,6 +106,66 @@ struct ArrRef {
 template <int N> static ArrRef arrRef(const DeviceArray<Real, N> &A) {
    return ArrRef{A.Ptr, A.rows(), A.Ext[N - 1], A.Pitch};
 }
+/// the three things the boundary does with an ArrRef: a compact host copy of at most n values out, one of exactly
+/// n values in, the device address (and the number of values, if asked for) out
+static void refCopyToHost(const ArrRef &R, const char *Name, double *Host, size_t N) {
+   if (N < R.size())
+      OMEGA_ABORT(std::string("output buffer too small for ") + Name);
+   copyRowsToHost(Host, R.Ptr, R.Pitch, R.Rows, R.Width);
+}
+static void refCopyToDevice(const ArrRef &R, const char *Name, const double *Host, size_t N) {
+   if (N != R.size())
+      OMEGA_ABORT(std::string("size mismatch for ") + Name);
+   copyRowsToDevice(R.Ptr, R.Pitch, Host, R.Rows, R.Width);
+}
+static void refPointerOut(const ArrRef &R, double **Dev, size_t *N) {
+   *Dev = R.Ptr;
+   if (N)
+      *N = R.size();
+}
+
+/// A new handle: `Fill` constructs the payload into the handle struct, which reaches *Out only if that did not throw
+/// (a throwing constructor leaks nothing and leaves *Out as it was).
+template <class Handle, class FillFn> static void newHandle(Handle **Out, FillFn &&Fill) {
+   auto R = std::make_unique<Handle>();
+   Fill(*R);
+   *Out = R.release();
+}
+
+/// Name-to-member tables: a flat list of {name, value} and the one finder; `What` is the start of the message an
+/// unknown name aborts with ("Eos: no array named ").
+template <class T> struct Named {
+   const char *Name;
+   T Value;
+};
+template <class T> static T findNamed(std::initializer_list<Named<T>> Table, const char *Name, const char *What) {
+   for (const Named<T> &E : Table)
+      if (std::strcmp(E.Name, Name) == 0)
+         return E.Value;
+   OMEGA_ABORT(std::string(What) + Name);
+}
+
+/// The accessors of a class with named Real arrays, from its handle type, the handle parameter's name (it appears in
+/// the invalid-argument message) and its lookup, an expression in that parameter and `name` that gives the ArrRef.
+#define OMG_NAMED_ARRAYS(TO_HOST, TO_DEVICE, DEVICE_PTR, HANDLE, H, LOOKUP)                                          \
+   int TO_HOST(const HANDLE *H, const char *name, double *host, size_t n) {                                          \
+      OMG_TRY                                                                                                        \
+      OMG_ARG(H && name && host);                                                                                    \
+      refCopyToHost(LOOKUP, name, host, n);                                                                          \
+      OMG_CATCH                                                                                                      \
+   }                                                                                                                 \
+   int TO_DEVICE(HANDLE *H, const char *name, const double *host, size_t n) {                                        \
+      OMG_TRY                                                                                                        \
+      OMG_ARG(H && name && host);                                                                                    \
+      refCopyToDevice(LOOKUP, name, host, n);                                                                        \
+      OMG_CATCH                                                                                                      \
+   }                                                                                                                 \
+   int DEVICE_PTR(const HANDLE *H, const char *name, double **dev, size_t *n) {                                      \
+      OMG_TRY                                                                                                        \
+      OMG_ARG(H && name && dev);                                                                                     \
+      refPointerOut(LOOKUP, dev, n);                                                                                 \
+      OMG_CATCH                                                                                                      \
+   }
 
 extern "C" {
 
@@ -232,14 +293,7 @@ int omg_combine_dd(const double *pairs, int npairs, double *hi_lo) {
 int omg_mesh_file_open(const char *path, omg_mesh_file **out) {
    OMG_TRY
    OMG_ARG(path && out);
-   auto *R = new omg_mesh_file;
-   try {
-      R->F.reset(new MeshFile(path));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_mesh_file &R) { R.F.reset(new MeshFile(path)); });
    OMG_CATCH
 }
 int omg_mesh_file_close(omg_mesh_file *f) {
@@ -311,14 +365,7 @@ int omg_restart_create(const char *path, int64_t ncells_global, int64_t nedges_g
 int omg_restart_open(const char *path, int write, omg_restart_file **out) {
    OMG_TRY
    OMG_ARG(path && out);
-   auto *R = new omg_restart_file;
-   try {
-      R->F.reset(new RestartFile(path, write != 0));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_restart_file &R) { R.F.reset(new RestartFile(path, write != 0)); });
    OMG_CATCH
 }
 int omg_restart_close(omg_restart_file *f) {
@@ -376,14 +423,9 @@ int omg_decomp_create_ordered(const omg_global_mesh *mesh, int nparts, int mytas
                               const int32_t *cell_task, int local_order, omg_decomp **out) {
    OMG_TRY
    OMG_ARG(mesh && out && local_order >= 0 && local_order <= 3);
-   auto *R = new omg_decomp;
-   try {
-      R->D.reset(new Decomp(toDesc(*mesh), nparts, mytask, halo_width, cell_task, (LocalOrder)local_order));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_decomp &R) {
+      R.D.reset(new Decomp(toDesc(*mesh), nparts, mytask, halo_width, cell_task, (LocalOrder)local_order));
+   });
    OMG_CATCH
 }
 int omg_partition_cells(const omg_global_mesh *mesh, int nparts, const char *method, int32_t *cell_task_out,
@@ -413,27 +455,24 @@ int omg_decomp_get_int(const omg_decomp *d, const char *name, int32_t *out) {
    OMG_TRY
    OMG_ARG(d && name && out);
    const Decomp &D = *d->D;
-   const std::map<std::string, I4> V{{"NCellsGlobal", D.NCellsGlobal},
-                                     {"NCellsOwned", D.NCellsOwned},
-                                     {"NCellsAll", D.NCellsAll},
-                                     {"NCellsSize", D.NCellsSize},
-                                     {"NEdgesGlobal", D.NEdgesGlobal},
-                                     {"NEdgesOwned", D.NEdgesOwned},
-                                     {"NEdgesAll", D.NEdgesAll},
-                                     {"NEdgesSize", D.NEdgesSize},
-                                     {"NVerticesGlobal", D.NVerticesGlobal},
-                                     {"NVerticesOwned", D.NVerticesOwned},
-                                     {"NVerticesAll", D.NVerticesAll},
-                                     {"NVerticesSize", D.NVerticesSize},
-                                     {"MaxEdges", D.MaxEdges},
-                                     {"VertexDegree", D.VertexDegree},
-                                     {"HaloWidth", D.HaloWidth},
-                                     {"NumTasks", D.NumTasks},
-                                     {"MyTask", D.MyTask}};
-   auto It = V.find(name);
-   if (It == V.end())
-      OMEGA_ABORT(std::string("Decomp: no integer member named ") + name);
-   *out = It->second;
+   *out = findNamed<I4>({{"NCellsGlobal", D.NCellsGlobal},
+                         {"NCellsOwned", D.NCellsOwned},
+                         {"NCellsAll", D.NCellsAll},
+                         {"NCellsSize", D.NCellsSize},
+                         {"NEdgesGlobal", D.NEdgesGlobal},
+                         {"NEdgesOwned", D.NEdgesOwned},
+                         {"NEdgesAll", D.NEdgesAll},
+                         {"NEdgesSize", D.NEdgesSize},
+                         {"NVerticesGlobal", D.NVerticesGlobal},
+                         {"NVerticesOwned", D.NVerticesOwned},
+                         {"NVerticesAll", D.NVerticesAll},
+                         {"NVerticesSize", D.NVerticesSize},
+                         {"MaxEdges", D.MaxEdges},
+                         {"VertexDegree", D.VertexDegree},
+                         {"HaloWidth", D.HaloWidth},
+                         {"NumTasks", D.NumTasks},
+                         {"MyTask", D.MyTask}},
+                        name, "Decomp: no integer member named ");
    OMG_CATCH
 }
 static void copyOutI4(const I4 *Src, size_t Cnt, int32_t *Out, size_t N, const char *Name) {
@@ -445,18 +484,16 @@ int omg_decomp_get_array(const omg_decomp *d, const char *name, int32_t *out, si
    OMG_TRY
    OMG_ARG(d && name && out);
    const Decomp &D = *d->D;
-   const std::string S(name);
-   const std::map<std::string, const HostArrayI4 *> A{
-       {"CellID", &D.CellIDH},           {"EdgeID", &D.EdgeIDH},         {"VertexID", &D.VertexIDH},
-       {"CellLoc", &D.CellLocH},         {"EdgeLoc", &D.EdgeLocH},       {"VertexLoc", &D.VertexLocH},
-       {"NCellsHalo", &D.NCellsHaloH},   {"NEdgesHalo", &D.NEdgesHaloH}, {"NVerticesHalo", &D.NVerticesHaloH}};
-   auto It = A.find(S);
-   if (It != A.end())
-      copyOutI4(It->second->data(), It->second->size(), out, n, name);
-   else if (S == "CellTask")
+   if (std::strcmp(name, "CellTask") == 0) { // a std::vector, not a host array
       copyOutI4(D.CellTask.data(), D.CellTask.size(), out, n, name);
-   else
-      OMEGA_ABORT("Decomp: no array member named " + S);
+      return 0;
+   }
+   const HostArrayI4 *A = findNamed<const HostArrayI4 *>(
+       {{"CellID", &D.CellIDH},         {"EdgeID", &D.EdgeIDH},         {"VertexID", &D.VertexIDH},
+        {"CellLoc", &D.CellLocH},       {"EdgeLoc", &D.EdgeLocH},       {"VertexLoc", &D.VertexLocH},
+        {"NCellsHalo", &D.NCellsHaloH}, {"NEdgesHalo", &D.NEdgesHaloH}, {"NVerticesHalo", &D.NVerticesHaloH}},
+       name, "Decomp: no array member named ");
+   copyOutI4(A->data(), A->size(), out, n, name);
    OMG_CATCH
 }
 
@@ -464,14 +501,7 @@ int omg_decomp_get_array(const omg_decomp *d, const char *name, int32_t *out, si
 int omg_halo_create(const omg_decomp *d, omg_halo **out) {
    OMG_TRY
    OMG_ARG(d && out);
-   auto *R = new omg_halo;
-   try {
-      R->H.reset(new Halo("Default", d->D.get()));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_halo &R) { R.H.reset(new Halo("Default", d->D.get())); });
    OMG_CATCH
 }
 int omg_halo_destroy(omg_halo *h) {
@@ -529,14 +559,7 @@ int omg_rccl_get_unique_id(char *id) {
 int omg_rccl_create(const char *id, int nranks, int rank, omg_rccl **out) {
    OMG_TRY
    OMG_ARG(id && out);
-   auto *R = new omg_rccl;
-   try {
-      R->C.reset(new RcclComm(id, nranks, rank));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_rccl &R) { R.C.reset(new RcclComm(id, nranks, rank)); });
    OMG_CATCH
 }
 int omg_rccl_destroy(omg_rccl *c) {
@@ -597,14 +620,7 @@ int omg_set_timing_level(int level) {
 int omg_peer_create(int nranks, int rank, size_t mailbox_bytes, omg_peer **out) {
    OMG_TRY
    OMG_ARG(out);
-   auto *R = new omg_peer;
-   try {
-      R->P.reset(new PeerWire(nranks, rank, mailbox_bytes));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_peer &R) { R.P.reset(new PeerWire(nranks, rank, mailbox_bytes)); });
    OMG_CATCH
 }
 int omg_peer_destroy(omg_peer *p) {
@@ -697,14 +713,7 @@ int omg_halo_check(const omg_halo *h) {
 int omg_mesh_create(const omg_decomp *d, int nvertlayers, int host_only, omg_mesh **out) {
    OMG_TRY
    OMG_ARG(d && out);
-   auto *R = new omg_mesh;
-   try {
-      R->M.reset(new HorzMesh("Default", d->D.get(), nvertlayers, host_only != 0));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_mesh &R) { R.M.reset(new HorzMesh("Default", d->D.get(), nvertlayers, host_only != 0)); });
    OMG_CATCH
 }
 int omg_mesh_destroy(omg_mesh *m) {
@@ -764,48 +773,44 @@ int omg_mesh_get_array_i4(const omg_mesh *m, const char *name, int32_t *out, siz
    OMG_TRY
    OMG_ARG(m && name && out);
    const HorzMesh &M = *m->M;
-   const std::map<std::string, const HostArrayI4 *> A{
-       {"CellsOnCell", &M.CellsOnCellH},       {"EdgesOnCell", &M.EdgesOnCellH},   {"NEdgesOnCell", &M.NEdgesOnCellH},
-       {"VerticesOnCell", &M.VerticesOnCellH}, {"CellsOnEdge", &M.CellsOnEdgeH},   {"EdgesOnEdge", &M.EdgesOnEdgeH},
-       {"NEdgesOnEdge", &M.NEdgesOnEdgeH},     {"VerticesOnEdge", &M.VerticesOnEdgeH},
-       {"CellsOnVertex", &M.CellsOnVertexH},   {"EdgesOnVertex", &M.EdgesOnVertexH},
-       {"NCellsHalo", &M.NCellsHaloH},         {"NEdgesHalo", &M.NEdgesHaloH},     {"NVerticesHalo", &M.NVerticesHaloH}};
-   auto It = A.find(name);
-   if (It == A.end())
-      OMEGA_ABORT(std::string("HorzMesh: no int array member named ") + name);
-   copyOutI4(It->second->data(), It->second->size(), out, n, name);
+   const HostArrayI4 *A = findNamed<const HostArrayI4 *>(
+       {{"CellsOnCell", &M.CellsOnCellH},       {"EdgesOnCell", &M.EdgesOnCellH},   {"NEdgesOnCell", &M.NEdgesOnCellH},
+        {"VerticesOnCell", &M.VerticesOnCellH}, {"CellsOnEdge", &M.CellsOnEdgeH},   {"EdgesOnEdge", &M.EdgesOnEdgeH},
+        {"NEdgesOnEdge", &M.NEdgesOnEdgeH},     {"VerticesOnEdge", &M.VerticesOnEdgeH},
+        {"CellsOnVertex", &M.CellsOnVertexH},   {"EdgesOnVertex", &M.EdgesOnVertexH},
+        {"NCellsHalo", &M.NCellsHaloH},         {"NEdgesHalo", &M.NEdgesHaloH},     {"NVerticesHalo", &M.NVerticesHaloH}},
+       name, "HorzMesh: no int array member named ");
+   copyOutI4(A->data(), A->size(), out, n, name);
    OMG_CATCH
 }
 int omg_mesh_get_array_r8(const omg_mesh *m, const char *name, double *out, size_t n) {
    OMG_TRY
    OMG_ARG(m && name && out);
    const HorzMesh &M = *m->M;
-   const std::map<std::string, const HostArrayReal *> A{
-       {"XCell", &M.XCellH},           {"YCell", &M.YCellH},       {"ZCell", &M.ZCellH},
-       {"LonCell", &M.LonCellH},       {"LatCell", &M.LatCellH},   {"XEdge", &M.XEdgeH},
-       {"YEdge", &M.YEdgeH},           {"ZEdge", &M.ZEdgeH},       {"LonEdge", &M.LonEdgeH},
-       {"LatEdge", &M.LatEdgeH},       {"XVertex", &M.XVertexH},   {"YVertex", &M.YVertexH},
-       {"ZVertex", &M.ZVertexH},       {"LonVertex", &M.LonVertexH}, {"LatVertex", &M.LatVertexH},
-       {"AreaCell", &M.AreaCellH},     {"AreaTriangle", &M.AreaTriangleH},
-       {"KiteAreasOnVertex", &M.KiteAreasOnVertexH},               {"DvEdge", &M.DvEdgeH},
-       {"DcEdge", &M.DcEdgeH},         {"AngleEdge", &M.AngleEdgeH}, {"WeightsOnEdge", &M.WeightsOnEdgeH},
-       {"FEdge", &M.FEdgeH},           {"FCell", &M.FCellH},       {"FVertex", &M.FVertexH},
-       {"BottomDepth", &M.BottomDepthH}, {"EdgeSignOnCell", &M.EdgeSignOnCellH},
-       {"EdgeSignOnVertex", &M.EdgeSignOnVertexH},                 {"EdgeMask1D", &M.EdgeMask1DH},
-       {"MeshScalingDel2", &M.MeshScalingDel2H},                   {"MeshScalingDel4", &M.MeshScalingDel4H}};
-   if (std::string(name) == "EdgeMask") { // expanded to the reference's (NEdgesSize, NVertLayers) shape
+   if (std::strcmp(name, "EdgeMask") == 0) { // expanded to the reference's (NEdgesSize, NVertLayers) shape
       const HostArrayReal M2 = M.edgeMask2D();
       if (n < M2.size())
          OMEGA_ABORT("output buffer too small for EdgeMask");
       std::memcpy(out, M2.data(), M2.size() * sizeof(double));
       return 0;
    }
-   auto It = A.find(name);
-   if (It == A.end())
-      OMEGA_ABORT(std::string("HorzMesh: no real array member named ") + name);
-   if (n < It->second->size())
+   const HostArrayReal *A = findNamed<const HostArrayReal *>(
+       {{"XCell", &M.XCellH},           {"YCell", &M.YCellH},       {"ZCell", &M.ZCellH},
+        {"LonCell", &M.LonCellH},       {"LatCell", &M.LatCellH},   {"XEdge", &M.XEdgeH},
+        {"YEdge", &M.YEdgeH},           {"ZEdge", &M.ZEdgeH},       {"LonEdge", &M.LonEdgeH},
+        {"LatEdge", &M.LatEdgeH},       {"XVertex", &M.XVertexH},   {"YVertex", &M.YVertexH},
+        {"ZVertex", &M.ZVertexH},       {"LonVertex", &M.LonVertexH}, {"LatVertex", &M.LatVertexH},
+        {"AreaCell", &M.AreaCellH},     {"AreaTriangle", &M.AreaTriangleH},
+        {"KiteAreasOnVertex", &M.KiteAreasOnVertexH},               {"DvEdge", &M.DvEdgeH},
+        {"DcEdge", &M.DcEdgeH},         {"AngleEdge", &M.AngleEdgeH}, {"WeightsOnEdge", &M.WeightsOnEdgeH},
+        {"FEdge", &M.FEdgeH},           {"FCell", &M.FCellH},       {"FVertex", &M.FVertexH},
+        {"BottomDepth", &M.BottomDepthH}, {"EdgeSignOnCell", &M.EdgeSignOnCellH},
+        {"EdgeSignOnVertex", &M.EdgeSignOnVertexH},                 {"EdgeMask1D", &M.EdgeMask1DH},
+        {"MeshScalingDel2", &M.MeshScalingDel2H},                   {"MeshScalingDel4", &M.MeshScalingDel4H}},
+       name, "HorzMesh: no real array member named ");
+   if (n < A->size())
       OMEGA_ABORT(std::string("output buffer too small for ") + name);
-   std::memcpy(out, It->second->data(), It->second->size() * sizeof(double));
+   std::memcpy(out, A->data(), A->size() * sizeof(double));
    OMG_CATCH
 }
 int omg_mesh_set_fvertex(omg_mesh *m, const double *host_values) {
@@ -889,14 +894,9 @@ int omg_state_create(const omg_mesh *m, omg_halo *halo, int nvertlayers, int nti
    OMG_TRY
    OMG_ARG(m && out);
    requireDevice(m->M.get());
-   auto *R = new omg_state;
-   try {
-      R->S.reset(new OceanState("Default", m->M.get(), halo ? halo->H.get() : nullptr, nvertlayers, ntimelevels));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_state &R) {
+      R.S.reset(new OceanState("Default", m->M.get(), halo ? halo->H.get() : nullptr, nvertlayers, ntimelevels));
+   });
    OMG_CATCH
 }
 int omg_state_destroy(omg_state *s) {
@@ -961,14 +961,9 @@ int omg_tracers_create(const omg_mesh *m, omg_halo *halo, int nvertlayers, int n
    OMG_TRY
    OMG_ARG(m && out);
    requireDevice(m->M.get());
-   auto *R = new omg_tracers;
-   try {
-      R->T.reset(new TracerStore(m->M.get(), halo ? halo->H.get() : nullptr, nvertlayers, ntracers, ntimelevels));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_tracers &R) {
+      R.T.reset(new TracerStore(m->M.get(), halo ? halo->H.get() : nullptr, nvertlayers, ntracers, ntimelevels));
+   });
    OMG_CATCH
 }
 int omg_tracers_destroy(omg_tracers *t) {
@@ -1017,14 +1012,9 @@ int omg_aux_create(const omg_mesh *m, omg_halo *halo, int nvertlayers, int ntrac
    OMG_TRY
    OMG_ARG(m && out);
    requireDevice(m->M.get());
-   auto *R = new omg_aux;
-   try {
-      R->A.reset(new AuxiliaryState("Default", m->M.get(), halo ? halo->H.get() : nullptr, nvertlayers, ntracers));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_aux &R) {
+      R.A.reset(new AuxiliaryState("Default", m->M.get(), halo ? halo->H.get() : nullptr, nvertlayers, ntracers));
+   });
    OMG_CATCH
 }
 int omg_aux_destroy(omg_aux *a) {
@@ -1059,72 +1049,37 @@ int omg_aux_compute_all(omg_aux *a, const omg_state *s, const omg_tracers *t, in
    a->A->computeAll(s->S.get(), tracerArray(t, trtl), ttl, vtl, (hipStream_t)stream);
    OMG_CATCH
 }
-static ArrRef auxLookup(const AuxiliaryState &A, const std::string &Name) {
-   const std::map<std::string, ArrRef> M{
-       {"KineticEnergyCell", arrRef(A.KineticAux.KineticEnergyCell)},
-       {"VelocityDivCell", arrRef(A.KineticAux.VelocityDivCell)},
-       {"FluxLayerThickEdge", arrRef(A.LayerThicknessAux.FluxLayerThickEdge)},
-       {"MeanLayerThickEdge", arrRef(A.LayerThicknessAux.MeanLayerThickEdge)},
-       {"SshCell", arrRef(A.LayerThicknessAux.SshCell)},
-       {"RelVortVertex", arrRef(A.VorticityAux.RelVortVertex)},
-       {"NormRelVortVertex", arrRef(A.VorticityAux.NormRelVortVertex)},
-       {"NormPlanetVortVertex", arrRef(A.VorticityAux.NormPlanetVortVertex)},
-       {"NormRelVortEdge", arrRef(A.VorticityAux.NormRelVortEdge)},
-       {"NormPlanetVortEdge", arrRef(A.VorticityAux.NormPlanetVortEdge)},
-       {"Del2Edge", arrRef(A.VelocityDel2Aux.Del2Edge)},
-       {"Del2DivCell", arrRef(A.VelocityDel2Aux.Del2DivCell)},
-       {"Del2RelVortVertex", arrRef(A.VelocityDel2Aux.Del2RelVortVertex)},
-       {"HTracersEdge", arrRef(A.TracerAux.HTracersEdge)},
-       {"Del2TracersCell", arrRef(A.TracerAux.Del2TracersCell)},
-       {"NormalStressEdge", arrRef(A.WindForcingAux.NormalStressEdge)},
-       {"ZonalStressCell", arrRef(A.WindForcingAux.ZonalStressCell)},
-       {"MeridStressCell", arrRef(A.WindForcingAux.MeridStressCell)}};
-   auto It = M.find(Name);
-   if (It == M.end())
-      OMEGA_ABORT("AuxiliaryState: no array named " + Name);
-   return It->second;
+static ArrRef auxLookup(const AuxiliaryState &A, const char *Name) {
+   return findNamed<ArrRef>({{"KineticEnergyCell", arrRef(A.KineticAux.KineticEnergyCell)},
+                             {"VelocityDivCell", arrRef(A.KineticAux.VelocityDivCell)},
+                             {"FluxLayerThickEdge", arrRef(A.LayerThicknessAux.FluxLayerThickEdge)},
+                             {"MeanLayerThickEdge", arrRef(A.LayerThicknessAux.MeanLayerThickEdge)},
+                             {"SshCell", arrRef(A.LayerThicknessAux.SshCell)},
+                             {"RelVortVertex", arrRef(A.VorticityAux.RelVortVertex)},
+                             {"NormRelVortVertex", arrRef(A.VorticityAux.NormRelVortVertex)},
+                             {"NormPlanetVortVertex", arrRef(A.VorticityAux.NormPlanetVortVertex)},
+                             {"NormRelVortEdge", arrRef(A.VorticityAux.NormRelVortEdge)},
+                             {"NormPlanetVortEdge", arrRef(A.VorticityAux.NormPlanetVortEdge)},
+                             {"Del2Edge", arrRef(A.VelocityDel2Aux.Del2Edge)},
+                             {"Del2DivCell", arrRef(A.VelocityDel2Aux.Del2DivCell)},
+                             {"Del2RelVortVertex", arrRef(A.VelocityDel2Aux.Del2RelVortVertex)},
+                             {"HTracersEdge", arrRef(A.TracerAux.HTracersEdge)},
+                             {"Del2TracersCell", arrRef(A.TracerAux.Del2TracersCell)},
+                             {"NormalStressEdge", arrRef(A.WindForcingAux.NormalStressEdge)},
+                             {"ZonalStressCell", arrRef(A.WindForcingAux.ZonalStressCell)},
+                             {"MeridStressCell", arrRef(A.WindForcingAux.MeridStressCell)}},
+                            Name, "AuxiliaryState: no array named ");
 }
-int omg_aux_copy_to_host(const omg_aux *a, const char *name, double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(a && name && host);
-   const ArrRef R = auxLookup(*a->A, name);
-   if (n < R.size())
-      OMEGA_ABORT(std::string("output buffer too small for ") + name);
-   copyRowsToHost(host, R.Ptr, R.Pitch, R.Rows, R.Width);
-   OMG_CATCH
-}
-int omg_aux_copy_to_device(omg_aux *a, const char *name, const double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(a && name && host);
-   const ArrRef R = auxLookup(*a->A, name);
-   if (n != R.size())
-      OMEGA_ABORT(std::string("size mismatch for ") + name);
-   copyRowsToDevice(R.Ptr, R.Pitch, host, R.Rows, R.Width);
-   OMG_CATCH
-}
-int omg_aux_device_ptr(const omg_aux *a, const char *name, double **dev, size_t *n) {
-   OMG_TRY
-   OMG_ARG(a && name && dev);
-   const ArrRef R = auxLookup(*a->A, name);
-   *dev = R.Ptr;
-   if (n)
-      *n = R.size();
-   OMG_CATCH
-}
+OMG_NAMED_ARRAYS(omg_aux_copy_to_host, omg_aux_copy_to_device, omg_aux_device_ptr, omg_aux, a, auxLookup(*a->A, name))
 
 // ---------------------------------------------------------------- Tendencies
 static int tendCreate(const omg_mesh *m, int nvertlayers, int ntracers, const omg_tend_config *c, omg_tend **out, bool Allow) {
    OMG_TRY
    OMG_ARG(m && out);
    requireDevice(m->M.get());
-   auto *R = new omg_tend;
-   try {
-      R->T.reset(new Tendencies("Default", m->M.get(), nvertlayers, ntracers, c ? toParams(c) : TendParams(), Allow));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_tend &R) {
+      R.T.reset(new Tendencies("Default", m->M.get(), nvertlayers, ntracers, c ? toParams(c) : TendParams(), Allow));
+   });
    OMG_CATCH
 }
 int omg_tend_create(const omg_mesh *m, int nvertlayers, int ntracers, const omg_tend_config *c, omg_tend **out) {
@@ -1304,19 +1259,13 @@ static ArrRef tendLookup(const Tendencies &T, int Which) {
 int omg_tend_copy_to_host(const omg_tend *t, int which, double *host, size_t n) {
    OMG_TRY
    OMG_ARG(t && host);
-   const ArrRef R = tendLookup(*t->T, which);
-   if (n < R.size())
-      OMEGA_ABORT("output buffer too small for tendency array");
-   copyRowsToHost(host, R.Ptr, R.Pitch, R.Rows, R.Width);
+   refCopyToHost(tendLookup(*t->T, which), "tendency array", host, n);
    OMG_CATCH
 }
 int omg_tend_device_ptr(const omg_tend *t, int which, double **dev, size_t *n) {
    OMG_TRY
    OMG_ARG(t && dev);
-   const ArrRef R = tendLookup(*t->T, which);
-   *dev = R.Ptr;
-   if (n)
-      *n = R.size();
+   refPointerOut(tendLookup(*t->T, which), dev, n);
    OMG_CATCH
 }
 int omg_level_pitch(int nvertlayers) { return levelPitch(nvertlayers); }
@@ -1329,16 +1278,11 @@ int omg_stepper_create(const char *type, double dt, omg_tend *t, omg_aux *a, con
    const TimeStepperType Ty = TimeStepper::getFromStr(type);
    if (Ty == TimeStepperType::Invalid)
       OMEGA_ABORT(std::string("TimeStepper: unknown type ") + type);
-   auto *R = new omg_stepper;
-   try {
-      R->St.reset(TimeStepper::make("Default", Ty, dt));
-      R->St->attachData(t->T.get(), a->A.get(), m->M.get(), halo ? halo->H.get() : nullptr, tr->T.get());
-      R->St->finalizeInit();
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_stepper &R) {
+      R.St.reset(TimeStepper::make("Default", Ty, dt));
+      R.St->attachData(t->T.get(), a->A.get(), m->M.get(), halo ? halo->H.get() : nullptr, tr->T.get());
+      R.St->finalizeInit();
+   });
    OMG_CATCH
 }
 int omg_stepper_destroy(omg_stepper *st) {
@@ -1408,6 +1352,14 @@ static Array2DReal levelView(const double *Dev, int Rows, int K) {
    A.Pitch  = levelPitch(K);
    return A;
 }
+/// a raw device array [ntracers][rows][levelPitch(k)] of the caller's as a 3-D array handle (no ownership)
+static Array3DReal tracerView(const double *Dev, int NTracers, int Rows, int K) {
+   Array3DReal A;
+   A.Ptr    = const_cast<Real *>(Dev);
+   A.Ext[0] = NTracers, A.Ext[1] = Rows, A.Ext[2] = K;
+   A.Pitch  = levelPitch(K);
+   return A;
+}
 /// a raw device array [rows] of the caller's (NULL: empty, read as zero)
 static Array1DReal cellView(const double *Dev, int Rows) {
    Array1DReal A;
@@ -1421,15 +1373,10 @@ int omg_vcoord_create(const omg_mesh *m, const omg_decomp *d, int nvertlayers, d
                       omg_vcoord **out) {
    OMG_TRY
    OMG_ARG(m && out && movement_weight_type);
-   auto *R = new omg_vcoord;
-   try {
-      R->V.reset(new VertCoord("Default", m->M.get(), d ? d->D.get() : nullptr, nvertlayers, rho0,
-                               movement_weight_type, min_level_cell, max_level_cell));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_vcoord &R) {
+      R.V.reset(new VertCoord("Default", m->M.get(), d ? d->D.get() : nullptr, nvertlayers, rho0,
+                              movement_weight_type, min_level_cell, max_level_cell));
+   });
    OMG_CATCH
 }
 int omg_vcoord_destroy(omg_vcoord *v) {
@@ -1492,66 +1439,29 @@ int omg_vcoord_compute_column(omg_vcoord *v, const omg_state *s, int thick_time_
                        (hipStream_t)stream, temp_index, salt_index);
    OMG_CATCH
 }
-static ArrRef vcoordLookup(const VertCoord &V, const std::string &Name) {
-   const std::map<std::string, ArrRef> M{{"PressureInterface", arrRef(V.PressureInterface)},
-                                         {"PressureMid", arrRef(V.PressureMid)},
-                                         {"ZInterface", arrRef(V.ZInterface)},
-                                         {"ZMid", arrRef(V.ZMid)},
-                                         {"GeopotentialMid", arrRef(V.GeopotentialMid)},
-                                         {"LayerThicknessTarget", arrRef(V.LayerThicknessTarget)},
-                                         {"RefLayerThickness", arrRef(V.RefLayerThickness)},
-                                         {"VertCoordMovementWeights", arrRef(V.VertCoordMovementWeights)},
-                                         {"BottomDepth", arrRef(V.BottomDepth)}};
-   auto It = M.find(Name);
-   if (It == M.end())
-      OMEGA_ABORT("VertCoord: no real array named " + Name);
-   return It->second;
+static ArrRef vcoordLookup(const VertCoord &V, const char *Name) {
+   return findNamed<ArrRef>({{"PressureInterface", arrRef(V.PressureInterface)},
+                             {"PressureMid", arrRef(V.PressureMid)},
+                             {"ZInterface", arrRef(V.ZInterface)},
+                             {"ZMid", arrRef(V.ZMid)},
+                             {"GeopotentialMid", arrRef(V.GeopotentialMid)},
+                             {"LayerThicknessTarget", arrRef(V.LayerThicknessTarget)},
+                             {"RefLayerThickness", arrRef(V.RefLayerThickness)},
+                             {"VertCoordMovementWeights", arrRef(V.VertCoordMovementWeights)},
+                             {"BottomDepth", arrRef(V.BottomDepth)}},
+                            Name, "VertCoord: no real array named ");
 }
-static const Array1DI4 &vcoordLookupI4(const VertCoord &V, const std::string &Name) {
-   const std::map<std::string, const Array1DI4 *> M{
-       {"MinLayerCell", &V.MinLayerCell},           {"MaxLayerCell", &V.MaxLayerCell},
-       {"MinLayerEdgeTop", &V.MinLayerEdgeTop},     {"MaxLayerEdgeTop", &V.MaxLayerEdgeTop},
-       {"MinLayerEdgeBot", &V.MinLayerEdgeBot},     {"MaxLayerEdgeBot", &V.MaxLayerEdgeBot},
-       {"MinLayerVertexTop", &V.MinLayerVertexTop}, {"MaxLayerVertexTop", &V.MaxLayerVertexTop},
-       {"MinLayerVertexBot", &V.MinLayerVertexBot}, {"MaxLayerVertexBot", &V.MaxLayerVertexBot}};
-   auto It = M.find(Name);
-   if (It == M.end())
-      OMEGA_ABORT("VertCoord: no integer array named " + Name);
-   return *It->second;
+static const Array1DI4 &vcoordLookupI4(const VertCoord &V, const char *Name) {
+   return *findNamed<const Array1DI4 *>(
+       {{"MinLayerCell", &V.MinLayerCell},           {"MaxLayerCell", &V.MaxLayerCell},
+        {"MinLayerEdgeTop", &V.MinLayerEdgeTop},     {"MaxLayerEdgeTop", &V.MaxLayerEdgeTop},
+        {"MinLayerEdgeBot", &V.MinLayerEdgeBot},     {"MaxLayerEdgeBot", &V.MaxLayerEdgeBot},
+        {"MinLayerVertexTop", &V.MinLayerVertexTop}, {"MaxLayerVertexTop", &V.MaxLayerVertexTop},
+        {"MinLayerVertexBot", &V.MinLayerVertexBot}, {"MaxLayerVertexBot", &V.MaxLayerVertexBot}},
+       Name, "VertCoord: no integer array named ");
 }
-static int refCopyToHost(const ArrRef &R, const char *name, double *host, size_t n) {
-   if (n < R.size())
-      OMEGA_ABORT(std::string("output buffer too small for ") + name);
-   copyRowsToHost(host, R.Ptr, R.Pitch, R.Rows, R.Width);
-   return 0;
-}
-static int refCopyToDevice(const ArrRef &R, const char *name, const double *host, size_t n) {
-   if (n != R.size())
-      OMEGA_ABORT(std::string("size mismatch for ") + name);
-   copyRowsToDevice(R.Ptr, R.Pitch, host, R.Rows, R.Width);
-   return 0;
-}
-int omg_vcoord_copy_to_host(const omg_vcoord *v, const char *name, double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(v && name && host);
-   refCopyToHost(vcoordLookup(*v->V, name), name, host, n);
-   OMG_CATCH
-}
-int omg_vcoord_copy_to_device(omg_vcoord *v, const char *name, const double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(v && name && host);
-   refCopyToDevice(vcoordLookup(*v->V, name), name, host, n);
-   OMG_CATCH
-}
-int omg_vcoord_device_ptr(const omg_vcoord *v, const char *name, double **dev, size_t *n) {
-   OMG_TRY
-   OMG_ARG(v && name && dev);
-   const ArrRef R = vcoordLookup(*v->V, name);
-   *dev = R.Ptr;
-   if (n)
-      *n = R.size();
-   OMG_CATCH
-}
+OMG_NAMED_ARRAYS(omg_vcoord_copy_to_host, omg_vcoord_copy_to_device, omg_vcoord_device_ptr, omg_vcoord, v,
+                 vcoordLookup(*v->V, name))
 int omg_vcoord_copy_to_host_i4(const omg_vcoord *v, const char *name, int32_t *host, size_t n) {
    OMG_TRY
    OMG_ARG(v && name && host);
@@ -1590,14 +1500,9 @@ int omg_eos_create(const omg_mesh *m, int nvertlayers, const char *eos_type, dou
                    double rhot0s0, omg_eos **out) {
    OMG_TRY
    OMG_ARG(m && out && eos_type);
-   auto *R = new omg_eos;
-   try {
-      R->E.reset(new Eos("Default", m->M.get(), nvertlayers, eos_type, drhodt, drhods, rhot0s0));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_eos &R) {
+      R.E.reset(new Eos("Default", m->M.get(), nvertlayers, eos_type, drhodt, drhods, rhot0s0));
+   });
    OMG_CATCH
 }
 int omg_eos_destroy(omg_eos *e) {
@@ -1622,34 +1527,11 @@ int omg_eos_compute_spec_vol_disp(omg_eos *e, const double *conserv_temp, const 
                             kdisp, p_scale, (hipStream_t)stream);
    OMG_CATCH
 }
-static ArrRef eosLookup(const Eos &E, const std::string &Name) {
-   if (Name == "SpecVol")
-      return arrRef(E.SpecVol);
-   if (Name == "SpecVolDisplaced")
-      return arrRef(E.SpecVolDisplaced);
-   OMEGA_ABORT("Eos: no array named " + Name);
+static ArrRef eosLookup(const Eos &E, const char *Name) {
+   return findNamed<ArrRef>({{"SpecVol", arrRef(E.SpecVol)}, {"SpecVolDisplaced", arrRef(E.SpecVolDisplaced)}}, Name,
+                            "Eos: no array named ");
 }
-int omg_eos_copy_to_host(const omg_eos *e, const char *name, double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(e && name && host);
-   refCopyToHost(eosLookup(*e->E, name), name, host, n);
-   OMG_CATCH
-}
-int omg_eos_copy_to_device(omg_eos *e, const char *name, const double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(e && name && host);
-   refCopyToDevice(eosLookup(*e->E, name), name, host, n);
-   OMG_CATCH
-}
-int omg_eos_device_ptr(const omg_eos *e, const char *name, double **dev, size_t *n) {
-   OMG_TRY
-   OMG_ARG(e && name && dev);
-   const ArrRef R = eosLookup(*e->E, name);
-   *dev = R.Ptr;
-   if (n)
-      *n = R.size();
-   OMG_CATCH
-}
+OMG_NAMED_ARRAYS(omg_eos_copy_to_host, omg_eos_copy_to_device, omg_eos_device_ptr, omg_eos, e, eosLookup(*e->E, name))
 
 // ---- VertMix (VertMix.h)
 static VertMixConfig toVertMixConfig(const omg_vertmix_config &c) {
@@ -1684,14 +1566,9 @@ int omg_vertmix_create(const omg_mesh *m, const omg_vcoord *v, const omg_vertmix
    OMG_TRY
    OMG_ARG(m && out);
    const VertMixConfig Cfg = c ? toVertMixConfig(*c) : VertMixConfig();
-   auto *R = new omg_vertmix;
-   try {
-      R->X.reset(new VertMix("Default", m->M.get(), v ? v->V.get() : nullptr, Cfg));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_vertmix &R) {
+      R.X.reset(new VertMix("Default", m->M.get(), v ? v->V.get() : nullptr, Cfg));
+   });
    OMG_CATCH
 }
 int omg_vertmix_destroy(omg_vertmix *x) {
@@ -1720,11 +1597,8 @@ int omg_vertmix_apply_tracers(omg_vertmix *x, const double *layer_thickness, dou
    OMG_ARG(x && layer_thickness && ntracers >= 0 && (tracers || ntracers == 0));
    const HorzMesh *M = x->X->Mesh;
    const int K       = x->X->NVertLayers;
-   Array3DReal Tr;
-   Tr.Ptr    = tracers;
-   Tr.Ext[0] = ntracers, Tr.Ext[1] = M->NCellsSize, Tr.Ext[2] = K;
-   Tr.Pitch  = levelPitch(K);
-   x->X->applyTracerVertMix(levelView(layer_thickness, M->NCellsSize, K), Tr, ntracers, dt, (hipStream_t)stream);
+   x->X->applyTracerVertMix(levelView(layer_thickness, M->NCellsSize, K), tracerView(tracers, ntracers, M->NCellsSize, K),
+                            ntracers, dt, (hipStream_t)stream);
    OMG_CATCH
 }
 int omg_vertmix_apply_velocity(omg_vertmix *x, const double *layer_thickness, double *normal_velocity, double dt,
@@ -1737,49 +1611,22 @@ int omg_vertmix_apply_velocity(omg_vertmix *x, const double *layer_thickness, do
                               dt, (hipStream_t)stream);
    OMG_CATCH
 }
-static ArrRef vertMixLookup(const VertMix &X, const std::string &Name) {
-   if (Name == "VertDiff")
-      return arrRef(X.VertDiff);
-   if (Name == "VertVisc")
-      return arrRef(X.VertVisc);
-   if (Name == "BruntVaisalaFreqSq")
-      return arrRef(X.BruntVaisalaFreqSq);
-   OMEGA_ABORT("VertMix: no array named " + Name);
+static ArrRef vertMixLookup(const VertMix &X, const char *Name) {
+   return findNamed<ArrRef>({{"VertDiff", arrRef(X.VertDiff)},
+                             {"VertVisc", arrRef(X.VertVisc)},
+                             {"BruntVaisalaFreqSq", arrRef(X.BruntVaisalaFreqSq)}},
+                            Name, "VertMix: no array named ");
 }
-int omg_vertmix_copy_to_host(const omg_vertmix *x, const char *name, double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(x && name && host);
-   refCopyToHost(vertMixLookup(*x->X, name), name, host, n);
-   OMG_CATCH
-}
-int omg_vertmix_copy_to_device(omg_vertmix *x, const char *name, const double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(x && name && host);
-   refCopyToDevice(vertMixLookup(*x->X, name), name, host, n);
-   OMG_CATCH
-}
-int omg_vertmix_device_ptr(const omg_vertmix *x, const char *name, double **dev, size_t *n) {
-   OMG_TRY
-   OMG_ARG(x && name && dev);
-   const ArrRef R = vertMixLookup(*x->X, name);
-   *dev = R.Ptr;
-   if (n)
-      *n = R.size();
-   OMG_CATCH
-}
+OMG_NAMED_ARRAYS(omg_vertmix_copy_to_host, omg_vertmix_copy_to_device, omg_vertmix_device_ptr, omg_vertmix, x,
+                 vertMixLookup(*x->X, name))
 
 // ---- PressureGrad (PressureGrad.h)
 int omg_pgrad_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, omg_pgrad **out) {
    OMG_TRY
    OMG_ARG(m && out);
-   auto *R = new omg_pgrad;
-   try {
-      R->P.reset(new PressureGrad("Default", m->M.get(), v ? v->V.get() : nullptr, e ? e->E.get() : nullptr));
-   } catch (...) {
-      delete R;
-      throw;
-   }
-   *out = R;
+   newHandle(out, [&](omg_pgrad &R) {
+      R.P.reset(new PressureGrad("Default", m->M.get(), v ? v->V.get() : nullptr, e ? e->E.get() : nullptr));
+   });
    OMG_CATCH
 }
 int omg_pgrad_destroy(omg_pgrad *p) {
@@ -1792,11 +1639,8 @@ int omg_pgrad_update_column(omg_pgrad *p, const double *layer_thickness, const d
    OMG_ARG(p && layer_thickness && tracers && ntracers >= 2);
    const HorzMesh *M = p->P->Mesh;
    const int K       = p->P->NVertLayers;
-   Array3DReal Tr;
-   Tr.Ptr    = const_cast<Real *>(tracers);
-   Tr.Ext[0] = ntracers, Tr.Ext[1] = M->NCellsSize, Tr.Ext[2] = K;
-   Tr.Pitch  = levelPitch(K);
-   p->P->updateColumn(levelView(layer_thickness, M->NCellsSize, K), Tr, (hipStream_t)stream);
+   p->P->updateColumn(levelView(layer_thickness, M->NCellsSize, K), tracerView(tracers, ntracers, M->NCellsSize, K),
+                      (hipStream_t)stream);
    OMG_CATCH
 }
 int omg_pgrad_compute(omg_pgrad *p, double *tend, void *stream) {
@@ -1816,36 +1660,14 @@ int omg_pgrad_compute_arrays(omg_pgrad *p, double *tend, const double *pressure_
                              (hipStream_t)stream);
    OMG_CATCH
 }
-static ArrRef pgradLookup(const PressureGrad &P, const std::string &Name) {
-   if (Name == "SurfacePressure")
-      return arrRef(P.SurfacePressure);
-   if (Name == "TidalPotential")
-      return arrRef(P.TidalPotential);
-   if (Name == "SelfAttractionLoading")
-      return arrRef(P.SelfAttractionLoading);
-   OMEGA_ABORT("PressureGrad: no array named " + Name);
+static ArrRef pgradLookup(const PressureGrad &P, const char *Name) {
+   return findNamed<ArrRef>({{"SurfacePressure", arrRef(P.SurfacePressure)},
+                             {"TidalPotential", arrRef(P.TidalPotential)},
+                             {"SelfAttractionLoading", arrRef(P.SelfAttractionLoading)}},
+                            Name, "PressureGrad: no array named ");
 }
-int omg_pgrad_device_ptr(const omg_pgrad *p, const char *name, double **dev, size_t *n) {
-   OMG_TRY
-   OMG_ARG(p && name && dev);
-   const ArrRef R = pgradLookup(*p->P, name);
-   *dev = R.Ptr;
-   if (n)
-      *n = R.size();
-   OMG_CATCH
-}
-int omg_pgrad_copy_to_device(omg_pgrad *p, const char *name, const double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(p && name && host);
-   refCopyToDevice(pgradLookup(*p->P, name), name, host, n);
-   OMG_CATCH
-}
-int omg_pgrad_copy_to_host(const omg_pgrad *p, const char *name, double *host, size_t n) {
-   OMG_TRY
-   OMG_ARG(p && name && host);
-   refCopyToHost(pgradLookup(*p->P, name), name, host, n);
-   OMG_CATCH
-}
+OMG_NAMED_ARRAYS(omg_pgrad_copy_to_host, omg_pgrad_copy_to_device, omg_pgrad_device_ptr, omg_pgrad, p,
+                 pgradLookup(*p->P, name))
 int omg_tend_attach_pressure_grad(omg_tend *t, omg_pgrad *p) {
    OMG_TRY
    OMG_ARG(t);
