@@ -39,6 +39,7 @@ typedef struct omg_vcoord omg_vcoord;   /* O/src/ocn/VertCoord.h class VertCoord
 typedef struct omg_eos omg_eos;         /* O/src/ocn/Eos.h       class Eos           */
 typedef struct omg_vertmix omg_vertmix; /* O/doc/design/VerticalMixingCoeff.md (design only) */
 typedef struct omg_pgrad omg_pgrad;     /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
+typedef struct omg_vertadv omg_vertadv; /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
 
 enum { OMG_ON_CELL = 0, OMG_ON_EDGE = 1, OMG_ON_VERTEX = 2 }; /* O/src/base/Halo.h:45 MeshElement */
 
@@ -578,6 +579,36 @@ int omg_pgrad_copy_to_host(const omg_pgrad *p, const char *name, double *host, s
  * tracers first; the velocity-only calls use the column fields as they stand; the Runge-Kutta stage updates run as
  * separate kernels and nothing is replayed as a graph.  Detach before destroying p. */
 int omg_tend_attach_pressure_grad(omg_tend *t, omg_pgrad *p);
+
+/* ---- VertAdv: vertical transport through the layer interfaces and the vertical advection of thickness, tracers and
+ * momentum (O/doc/design/OmegaV1GoverningEqns.md, discrete-mass / -tracer / -momentum; the reference has no code for
+ * them).  Numerical contract: omega_amd/csrc/VertAdv.h.  Arrays are level-indexed device arrays as above.  Every call
+ * is asynchronous on stream and allocates nothing.  The object keeps a pointer to v: destroy it before v. ---- */
+/* tracer_flux_order: 1 upwind, 2 centred.  Fails for another order, a host-only mesh, a VertCoord of another mesh or
+ * layer count, and more layers than omg_vertadv_max_layers */
+int omg_vertadv_create(const omg_mesh *m, const omg_vcoord *v, int tracer_flux_order, omg_vertadv **out);
+int omg_vertadv_destroy(omg_vertadv *a);
+int omg_vertadv_max_layers(int *n);
+/* VerticalTransport from thickness_tend_dev [NCellsSize][pitch] (the horizontal part); add_thickness != 0 also applies
+ * omg_vertadv_add_thickness to thickness_tend_dev in the same launch */
+int omg_vertadv_compute_transport(omg_vertadv *a, double *thickness_tend_dev, int add_thickness, void *stream);
+/* thickness_tend_dev [NCellsSize][pitch] += VerticalTransport[K+1] - VerticalTransport[K] */
+int omg_vertadv_add_thickness(omg_vertadv *a, double *thickness_tend_dev, void *stream);
+/* tracer_tend_dev, tracers_dev [ntracers][NCellsSize][pitch]; layer_thickness_dev [NCellsSize][pitch] */
+int omg_vertadv_add_tracers(omg_vertadv *a, double *tracer_tend_dev, const double *layer_thickness_dev,
+                            const double *tracers_dev, int ntracers, void *stream);
+/* velocity_tend_dev, normal_velocity_dev [NEdgesSize][pitch]; layer_thickness_dev [NCellsSize][pitch] */
+int omg_vertadv_add_velocity(omg_vertadv *a, double *velocity_tend_dev, const double *layer_thickness_dev,
+                             const double *normal_velocity_dev, void *stream);
+/* "VerticalTransport" ([NCellsSize][NVertLayers], zero at creation) */
+int omg_vertadv_device_ptr(const omg_vertadv *a, const char *name, double **dev, size_t *n);
+int omg_vertadv_copy_to_device(omg_vertadv *a, const char *name, const double *host, size_t n);
+int omg_vertadv_copy_to_host(const omg_vertadv *a, const char *name, double *host, size_t n);
+/* Tendencies::attachVertAdv: the terms become opt-in terms of t (a NULL: detach).  While attached omg_tend_compute_all
+ * adds them after the built-in terms and before an attached PressureGrad and the custom hooks; the velocity and tracer
+ * group calls use VerticalTransport as it stands; the Runge-Kutta stage updates run as separate kernels and nothing is
+ * replayed as a graph.  Detach before destroying a. */
+int omg_tend_attach_vert_adv(omg_tend *t, omg_vertadv *a);
 
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at

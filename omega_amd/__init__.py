@@ -2,7 +2,7 @@
 
 Thin ctypes plumbing used by tests/, bench.py and __graft_entry__.py: the product is the
 C++/HIP library under omega_amd/csrc (classes named after Omega's own: Decomp, Halo,
-HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, PressureGrad, Tendencies, TimeStepper).  There is no
+HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, PressureGrad, VertAdv, Tendencies, TimeStepper).  There is no
 Python or CPU implementation of the hot path here: if the shared library is missing,
 importing the binding raises, and without a HIP device every device call fails.
 """
@@ -1182,6 +1182,60 @@ class PressureGrad(_Handle, _NamedArrays):
         return (self.mesh.NCellsSize,)
 
 
+class VertAdv(_Handle, _NamedArrays):
+    """VertAdv (omega_amd/csrc/VertAdv.h): the vertical transport that holds the layers to the VertCoord's z-star /
+    z-level shape and the vertical advection of thickness, tracers and momentum.  Level-indexed inputs are numpy arrays
+    [rows][K] or device addresses of [rows][level_pitch(K)] doubles; a tendency is accumulated in place: a device
+    address (asynchronous on `stream`) or a numpy array (staged, computed, returned)."""
+    _destroy, _arrays = "omg_vertadv_destroy", "omg_vertadv"
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", tracer_flux_order: int = 2):
+        self.mesh, self.vcoord, self.order = mesh, vcoord, tracer_flux_order
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self._create("omg_vertadv_create", mesh.h, vcoord.h if vcoord is not None else None, int(tracer_flux_order))
+
+    @staticmethod
+    def max_layers() -> int:
+        n = C.c_int()
+        _chk(lib().omg_vertadv_max_layers(C.byref(n)))
+        return n.value
+
+    def compute_transport(self, thickness_tend, add_thickness: bool = False, stream=None):
+        """VerticalTransport from the horizontal thickness tendency; add_thickness: also the thickness update, in the
+        same launch (computeAndAddThickness)"""
+        p, buf = _stage_levels(thickness_tend, (self.mesh.NCellsSize,), self.K)
+        _chk(lib().omg_vertadv_compute_transport(self.h, p, int(bool(add_thickness)), _sh(stream)))
+        return _read_back(buf, self.K, stream)
+
+    def add_thickness(self, thickness_tend, stream=None):
+        p, buf = _stage_levels(thickness_tend, (self.mesh.NCellsSize,), self.K)
+        _chk(lib().omg_vertadv_add_thickness(self.h, p, _sh(stream)))
+        return _read_back(buf, self.K, stream)
+
+    def add_tracers(self, tracer_tend, layer_thickness, tracers, ntracers: int, stream=None):
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
+        p, buf = _stage_levels(tracer_tend, (int(ntracers), n), self.K)
+        _chk(lib().omg_vertadv_add_tracers(self.h, p, h, t, int(ntracers), _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def add_velocity(self, velocity_tend, layer_thickness, normal_velocity, stream=None):
+        keep = []
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        u = _level_dev(normal_velocity, self.mesh.NEdgesSize, self.K, keep)
+        p, buf = _stage_levels(velocity_tend, (self.mesh.NEdgesSize,), self.K)
+        _chk(lib().omg_vertadv_add_velocity(self.h, p, h, u, _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def _shape(self, name):
+        return (self.mesh.NCellsSize, self.K)
+
+
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""
@@ -1211,6 +1265,12 @@ class Tendencies(_Handle):
         raises while SSHTendencyEnable is on."""
         _chk(lib().omg_tend_attach_pressure_grad(self.h, pgrad.h if pgrad is not None else None))
         self._pgrad = pgrad  # the library keeps a pointer to it
+
+    def attach_vert_adv(self, vert_adv: "VertAdv | None"):
+        """Tendencies::attachVertAdv: vertical transport and advection as opt-in terms of all three tendencies (None
+        detaches)."""
+        _chk(lib().omg_tend_attach_vert_adv(self.h, vert_adv.h if vert_adv is not None else None))
+        self._vert_adv = vert_adv  # the library keeps a pointer to it
 
     def set_graphs(self, on: bool):
         _chk(lib().omg_tend_set_graphs(self.h, int(on)))

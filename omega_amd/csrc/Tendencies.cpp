@@ -2,6 +2,7 @@
 #include "Tendencies.h"
 #include "Pacer.h"
 #include "PressureGrad.h"
+#include "VertAdv.h"
 #include "kernels/KernelCommon.h"
 
 namespace OMEGA {
@@ -84,6 +85,13 @@ void Tendencies::attachPressureGrad(PressureGrad *P) {
    PGrad = P;
 }
 
+void Tendencies::attachVertAdv(VertAdv *V) {
+   if (V)
+      OMEGA_REQUIRE(V->Mesh == Mesh && V->NVertLayers == NVertLayers,
+                    "Tendencies::attachVertAdv: the VertAdv was built for another mesh or layer count");
+   VAdv = V;
+}
+
 void Tendencies::addPressureGrad(hipStream_t S) {
    OMEGA_REQUIRE(!Params.SSHTendencyEnable,
                  "Tendencies: SSHTendencyEnable was turned on while a PressureGrad is attached: two pressure forces");
@@ -99,6 +107,10 @@ void Tendencies::computeThicknessTendenciesOnly(const OceanState *State, const A
    OMEGA_REQUIRE(State->getNormalVelocity(NormalVelEdge, VelLvl) == 0, "Tendencies: bad velocity time level");
    launchThicknessTendOnly(Mesh->view(), NVertLayers, paramsFor(Aux), Aux->ptrs(), LayerThicknessTend.Ptr,
                            NormalVelEdge.Ptr, S);
+   if (VAdv) {
+      Pacer::Range T2("Tend:vertAdvThickness", 2);
+      VAdv->computeAndAddThickness(LayerThicknessTend, S);
+   }
    if (CustomThicknessTend) { // Tendencies.cpp:288-291
       Pacer::Range T2("Tend:customThicknessTend", 2);
       CustomThicknessTend(LayerThicknessTend, State, Aux, ThickLvl, VelLvl, ModelTime, S);
@@ -112,6 +124,12 @@ void Tendencies::computeVelocityTendenciesOnly(const OceanState *State, const Au
    OMEGA_REQUIRE(State->getNormalVelocity(NormalVelEdge, VelLvl) == 0, "Tendencies: bad velocity time level");
    launchVelocityTendOnly(Mesh->view(), NVertLayers, paramsFor(Aux), Aux->ptrs(), NormalVelocityTend.Ptr,
                           NormalVelEdge.Ptr, S);
+   if (VAdv) { // from VerticalTransport as it stands
+      Pacer::Range T2("Tend:vertAdvVelocity", 2);
+      Array2DReal LayerThick;
+      OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0, "Tendencies: bad thickness time level");
+      VAdv->addVelocityTend(NormalVelocityTend, LayerThick, NormalVelEdge, S);
+   }
    if (PGrad)
       addPressureGrad(S);
    if (CustomVelocityTend) { // Tendencies.cpp:416-419
@@ -121,12 +139,18 @@ void Tendencies::computeVelocityTendenciesOnly(const OceanState *State, const Au
 }
 // Tendencies.cpp:427-486
 void Tendencies::computeTracerTendenciesOnly(const OceanState *State, const AuxiliaryState *Aux,
-                                             const Array3DReal &TracerArray, int, int VelLvl, hipStream_t S) {
+                                             const Array3DReal &TracerArray, int ThickLvl, int VelLvl, hipStream_t S) {
    Pacer::Range Timer("Tend:computeTracerTendenciesOnly", 1);
    Array2DReal NormalVelEdge;
    OMEGA_REQUIRE(State->getNormalVelocity(NormalVelEdge, VelLvl) == 0, "Tendencies: bad velocity time level");
    launchTracerTendOnly(Mesh->view(), NVertLayers, NTracers, paramsFor(Aux), Aux->ptrs(), TracerTend.Ptr,
                         NormalVelEdge.Ptr, TracerArray.Ptr, S);
+   if (VAdv) { // from VerticalTransport as it stands
+      Pacer::Range T2("Tend:vertAdvTracer", 2);
+      Array2DReal LayerThick;
+      OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0, "Tendencies: bad thickness time level");
+      VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
+   }
 }
 // Tendencies.cpp:488-519
 void Tendencies::computeThicknessTendencies(const OceanState *State, const AuxiliaryState *Aux, int ThickLvl, int VelLvl,
@@ -174,8 +198,8 @@ bool Tendencies::computeAllTendenciesStage(const OceanState *State, const Auxili
       return false;
    if (CustomThicknessTend || CustomVelocityTend)
       return false; // the custom terms are added to the stored tendencies: needs the plain sequence
-   if (PGrad)
-      return false; // so is the attached pressure gradient
+   if (PGrad || VAdv)
+      return false; // so are the attached pressure gradient and vertical advection
    Array2DReal LayerThick, NormVel;
    OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0 && State->getNormalVelocity(NormVel, VelLvl) == 0,
                  "Tendencies: bad time level");
@@ -210,7 +234,7 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
                         EdgeScratch.Ptr, nullptr, Mesh->narrowView());
       };
       // wind forcing reads the stress arrays through a non-tile kernel too, still plain launches: capturable
-      if (graphsOn() && !Ev && !CustomThicknessTend && !CustomVelocityTend && !PGrad) {
+      if (graphsOn() && !Ev && !CustomThicknessTend && !CustomVelocityTend && !PGrad && !VAdv) {
          GraphCache::Key Key;
          GraphCache::add(Key, LayerThick.Ptr), GraphCache::add(Key, NormVel.Ptr), GraphCache::add(Key, TracerArray.Ptr);
          GraphCache::add(Key, Aux), GraphCache::add(Key, P), GraphCache::add(Key, S);
@@ -218,6 +242,12 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
          Graphs.run(Key, S, Launch);
       } else {
          Launch();
+      }
+      if (VAdv) { // the transport of the built-in thickness terms, then the three vertical-advection terms
+         Pacer::Range T2("Tend:vertAdv", 2);
+         VAdv->computeAndAddThickness(LayerThicknessTend, S);
+         VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
+         VAdv->addVelocityTend(NormalVelocityTend, LayerThick, NormVel, S);
       }
       if (PGrad)
          addPressureGrad(S);

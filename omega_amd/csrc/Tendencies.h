@@ -20,6 +20,7 @@
 namespace OMEGA {
 
 class PressureGrad;
+class VertAdv;
 
 /// A custom tendency hook (Tendencies.h:51-53): holds a callable of EITHER form --
 ///   native:     void(const Array2DReal &Tend, const OceanState *, const AuxiliaryState *, int ThickLvl, int VelLvl,
@@ -108,6 +109,23 @@ class Tendencies : public Registry<Tendencies> {
    void attachPressureGrad(PressureGrad *PGrad);
    PressureGrad *pressureGrad() const { return PGrad; }
 
+   /// Vertical transport and vertical advection (VertAdv.h) as opt-in terms of all three tendencies; nullptr detaches.
+   /// Refused (OmegaError) for an object of another mesh or layer count.  While attached:
+   ///  - computeAllTendencies runs the existing RHS unchanged, then VertAdv::computeAndAddThickness on
+   ///    LayerThicknessTend, addTracerTend with the stage's layer thickness and the TracerArray argument, and
+   ///    addVelocityTend with the stage's thickness and velocity, all on the same stream, BEFORE an attached
+   ///    PressureGrad and before both custom hooks: the transport is derived from the built-in thickness terms only,
+   ///    not from what CustomThicknessTend adds;
+   ///  - computeThicknessTendencies / ...Only do the thickness part (transport included) after the built-in terms and
+   ///    before CustomThicknessTend;
+   ///  - the velocity and tracer group methods add their term from VerticalTransport AS IT STANDS (the last thickness
+   ///    evaluation) -- the caller keeps it current; the Forward-Backward stepper calls the thickness group first;
+   ///  - computeAllTendenciesStage returns false (the Runge-Kutta stage updates then run as separate kernels), and
+   ///    the RHS is not replayed as a graph.
+   /// With nothing attached every code path, launch count, allocation and result is what it was.
+   void attachVertAdv(VertAdv *VAdv);
+   VertAdv *vertAdv() const { return VAdv; }
+
    void computeThicknessTendenciesOnly(const OceanState *State, const AuxiliaryState *AuxState, int ThickTimeLevel,
                                        int VelTimeLevel, hipStream_t S);
    void computeVelocityTendenciesOnly(const OceanState *State, const AuxiliaryState *AuxState, int ThickTimeLevel,
@@ -184,6 +202,7 @@ class Tendencies : public Registry<Tendencies> {
 
  private:
    PressureGrad *PGrad = nullptr;
+   VertAdv *VAdv       = nullptr;
    void addPressureGrad(hipStream_t S); ///< NormalVelocityTend -= the attached term, from the column fields as they stand
    Array2DReal EdgeScratch; ///< running PV sums of the fused RHS (allocated by the constructor)
    bool TimingOn = false;

@@ -493,7 +493,7 @@ bool RungeKutta4Stepper::doStepFused(OceanState *State, hipStream_t S) {
    }
    };
    if (!Exchanges && (UseGraphs || GraphCache::defaultOn()) && StageFusedKnownGood && !Tend->CustomThicknessTend && !Tend->CustomVelocityTend &&
-       !Tend->pressureGrad()) {
+       !Tend->pressureGrad() && !Tend->vertAdv()) {
       // one rank: nothing but kernel launches on S -- replay them as a graph (keyed by everything that enters them)
       GraphCache::Key Key;
       GraphCache::add(Key, State), GraphCache::add(Key, CurH.Ptr), GraphCache::add(Key, NextH.Ptr);

@@ -22,6 +22,7 @@
 #include "TriDiagSolvers.h"
 #include "VertMix.h"
 #include "PressureGrad.h"
+#include "VertAdv.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -75,6 +76,9 @@ struct omg_vertmix {
 };
 struct omg_pgrad {
    std::unique_ptr<PressureGrad> P;
+};
+struct omg_vertadv {
+   std::unique_ptr<VertAdv> A;
 };
 
 static thread_local std::string LastError;
@@ -1672,6 +1676,73 @@ int omg_tend_attach_pressure_grad(omg_tend *t, omg_pgrad *p) {
    OMG_TRY
    OMG_ARG(t);
    t->T->attachPressureGrad(p ? p->P.get() : nullptr);
+   OMG_CATCH
+}
+
+// ---- VertAdv (VertAdv.h)
+int omg_vertadv_create(const omg_mesh *m, const omg_vcoord *v, int tracer_flux_order, omg_vertadv **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   VertAdvConfig Cfg;
+   Cfg.TracerFluxOrder = tracer_flux_order;
+   newHandle(out, [&](omg_vertadv &R) { R.A.reset(new VertAdv("Default", m->M.get(), v ? v->V.get() : nullptr, Cfg)); });
+   OMG_CATCH
+}
+int omg_vertadv_destroy(omg_vertadv *a) {
+   delete a;
+   return 0;
+}
+int omg_vertadv_compute_transport(omg_vertadv *a, double *thickness_tend, int add_thickness, void *stream) {
+   OMG_TRY
+   OMG_ARG(a && thickness_tend);
+   const Array2DReal T = levelView(thickness_tend, a->A->Mesh->NCellsSize, a->A->NVertLayers);
+   if (add_thickness)
+      a->A->computeAndAddThickness(T, (hipStream_t)stream);
+   else
+      a->A->computeVerticalTransport(T, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertadv_add_thickness(omg_vertadv *a, double *thickness_tend, void *stream) {
+   OMG_TRY
+   OMG_ARG(a && thickness_tend);
+   a->A->addThicknessTend(levelView(thickness_tend, a->A->Mesh->NCellsSize, a->A->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertadv_add_tracers(omg_vertadv *a, double *tracer_tend, const double *layer_thickness, const double *tracers,
+                            int ntracers, void *stream) {
+   OMG_TRY
+   OMG_ARG(a && layer_thickness && ntracers >= 0 && ((tracer_tend && tracers) || ntracers == 0));
+   const HorzMesh *M = a->A->Mesh;
+   const int K       = a->A->NVertLayers;
+   a->A->addTracerTend(tracerView(tracer_tend, ntracers, M->NCellsSize, K), levelView(layer_thickness, M->NCellsSize, K),
+                       tracerView(tracers, ntracers, M->NCellsSize, K), ntracers, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertadv_add_velocity(omg_vertadv *a, double *velocity_tend, const double *layer_thickness,
+                             const double *normal_velocity, void *stream) {
+   OMG_TRY
+   OMG_ARG(a && velocity_tend && layer_thickness && normal_velocity);
+   const HorzMesh *M = a->A->Mesh;
+   const int K       = a->A->NVertLayers;
+   a->A->addVelocityTend(levelView(velocity_tend, M->NEdgesSize, K), levelView(layer_thickness, M->NCellsSize, K),
+                         levelView(normal_velocity, M->NEdgesSize, K), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertadv_max_layers(int *n) {
+   OMG_TRY
+   OMG_ARG(n);
+   *n = VertAdv::maxLayers();
+   OMG_CATCH
+}
+static ArrRef vertAdvLookup(const VertAdv &A, const char *Name) {
+   return findNamed<ArrRef>({{"VerticalTransport", arrRef(A.VerticalTransport)}}, Name, "VertAdv: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_vertadv_copy_to_host, omg_vertadv_copy_to_device, omg_vertadv_device_ptr, omg_vertadv, a,
+                 vertAdvLookup(*a->A, name))
+int omg_tend_attach_vert_adv(omg_tend *t, omg_vertadv *a) {
+   OMG_TRY
+   OMG_ARG(t);
+   t->T->attachVertAdv(a ? a->A.get() : nullptr);
    OMG_CATCH
 }
 
