@@ -125,6 +125,26 @@ using Array1DReal = DeviceArray<Real, 1>;
 using Array2DReal = DeviceArray<Real, 2>;
 using Array3DReal = DeviceArray<Real, 3>;
 
+/// What a class asks of a level-indexed array it is handed: not empty, at least MinRows rows of K levels, rows of
+/// levelPitch(K) values.  The message is "<Owner>: <What> must be [<Rows>][NVertLayers] ..." with Rows the number
+/// unless the caller words it (the classes that accept NCellsAll rows say "NCellsSize").
+inline std::string levelArrayText(const char *Owner, const char *What, const std::string &Dims) {
+   return std::string(Owner) + ": " + What + " must be " + Dims + "[NVertLayers] with rows of levelPitch(NVertLayers)";
+}
+inline void requireLevelArray(const char *Owner, const Array2DReal &A, int MinRows, int K, const char *What,
+                              const std::string &Rows = "") {
+   OMEGA_REQUIRE(A.Ptr != nullptr, std::string(Owner) + ": " + What + " is empty");
+   OMEGA_REQUIRE(A.Ext[0] >= MinRows && A.Ext[1] == K && A.Pitch == levelPitch(K),
+                 levelArrayText(Owner, What, "[" + (Rows.empty() ? std::to_string(MinRows) : Rows) + "]"));
+}
+/// The same of a [tracer][row][level] array with at least NT planes of at least MinRows rows
+inline void requireLevelArray(const char *Owner, const Array3DReal &A, int NT, int MinRows, int K, const char *What,
+                              const std::string &Rows = "") {
+   OMEGA_REQUIRE(A.Ptr != nullptr, std::string(Owner) + ": " + What + " is empty");
+   OMEGA_REQUIRE(A.Ext[0] >= NT && A.Ext[1] >= MinRows && A.Ext[2] == K && A.Pitch == levelPitch(K),
+                 levelArrayText(Owner, What, "[NTracers][" + (Rows.empty() ? std::to_string(MinRows) : Rows) + "]"));
+}
+
 /// Host arrays are plain vectors with extents.
 template <class T> struct HostArray {
    std::vector<T> V;

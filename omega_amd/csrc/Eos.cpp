@@ -42,17 +42,11 @@ EosParams Eos::params() const {
    return E;
 }
 
-static void requireLevels(const Array2DReal &A, const HorzMesh *M, int K, const char *What) {
-   OMEGA_REQUIRE(A.Ptr != nullptr, std::string("Eos: ") + What + " is empty");
-   OMEGA_REQUIRE(A.Ext[0] >= M->NCellsAll && A.Ext[1] == K && A.Pitch == levelPitch(K),
-                 std::string("Eos: ") + What + " must be [NCellsSize][NVertLayers] with rows of levelPitch(NVertLayers)");
-}
-
 void Eos::computeSpecVol(const Array2DReal &Ct, const Array2DReal &Sa, const Array2DReal &P, Real PScale,
                          hipStream_t S) const {
-   requireLevels(Ct, Mesh, NVertLayers, "ConservTemp");
-   requireLevels(Sa, Mesh, NVertLayers, "AbsSalinity");
-   requireLevels(P, Mesh, NVertLayers, "Pressure");
+   requireLevelArray("Eos", Ct, Mesh->NCellsAll, NVertLayers, "ConservTemp", "NCellsSize");
+   requireLevelArray("Eos", Sa, Mesh->NCellsAll, NVertLayers, "AbsSalinity", "NCellsSize");
+   requireLevelArray("Eos", P, Mesh->NCellsAll, NVertLayers, "Pressure", "NCellsSize");
    ColumnArgs A;
    A.NCells = Mesh->NCellsAll, A.K = NVertLayers, A.Pitch = levelPitch(NVertLayers), A.Pitch1 = levelPitch(NVertLayers + 1);
    A.MinLayer = nullptr;
@@ -64,9 +58,9 @@ void Eos::computeSpecVol(const Array2DReal &Ct, const Array2DReal &Sa, const Arr
 
 void Eos::computeSpecVolDisp(const Array2DReal &Ct, const Array2DReal &Sa, const Array2DReal &P, I4 KDisp, Real PScale,
                              hipStream_t S) const {
-   requireLevels(Ct, Mesh, NVertLayers, "ConservTemp");
-   requireLevels(Sa, Mesh, NVertLayers, "AbsSalinity");
-   requireLevels(P, Mesh, NVertLayers, "Pressure");
+   requireLevelArray("Eos", Ct, Mesh->NCellsAll, NVertLayers, "ConservTemp", "NCellsSize");
+   requireLevelArray("Eos", Sa, Mesh->NCellsAll, NVertLayers, "AbsSalinity", "NCellsSize");
+   requireLevelArray("Eos", P, Mesh->NCellsAll, NVertLayers, "Pressure", "NCellsSize");
    ColumnArgs A;
    A.NCells = Mesh->NCellsAll, A.K = NVertLayers, A.Pitch = levelPitch(NVertLayers), A.Pitch1 = levelPitch(NVertLayers + 1);
    A.ConservTemp = Ct.Ptr, A.AbsSalinity = Sa.Ptr, A.PressureIn = P.Ptr, A.PScale = PScale, A.KDisp = KDisp;

@@ -22,19 +22,12 @@ PressureGrad::PressureGrad(const std::string &Name_, const HorzMesh *Mesh_, Vert
    SelfAttractionLoading = Array1DReal("SelfAttractionLoading", Mesh->NCellsSize);
 }
 
-static void requireRows(const Array2DReal &A, int Rows, int K, const char *What) {
-   OMEGA_REQUIRE(A.Ptr != nullptr, std::string("PressureGrad: ") + What + " is empty");
-   OMEGA_REQUIRE(A.Ext[0] >= Rows && A.Ext[1] == K && A.Pitch == levelPitch(K),
-                 std::string("PressureGrad: ") + What + " must be [" + std::to_string(Rows) +
-                     "][NVertLayers] with rows of levelPitch(NVertLayers)");
-}
-
 void PressureGrad::computePressureGrad(const Array2DReal &Tend, const Array2DReal &PMid, const Array2DReal &GeoMid,
                                        const Array2DReal &SpecVol, hipStream_t S) const {
-   requireRows(Tend, Mesh->NEdgesSize, NVertLayers, "Tend");
-   requireRows(PMid, Mesh->NCellsSize, NVertLayers, "PressureMid");
-   requireRows(GeoMid, Mesh->NCellsSize, NVertLayers, "GeopotentialMid");
-   requireRows(SpecVol, Mesh->NCellsSize, NVertLayers, "SpecVol");
+   requireLevelArray("PressureGrad", Tend, Mesh->NEdgesSize, NVertLayers, "Tend");
+   requireLevelArray("PressureGrad", PMid, Mesh->NCellsSize, NVertLayers, "PressureMid");
+   requireLevelArray("PressureGrad", GeoMid, Mesh->NCellsSize, NVertLayers, "GeopotentialMid");
+   requireLevelArray("PressureGrad", SpecVol, Mesh->NCellsSize, NVertLayers, "SpecVol");
    Pacer::Range Timer("PressureGrad:computePressureGrad", 1);
    PressureGradArgs A;
    A.NEdgesAll = Mesh->NEdgesAll, A.NCellsSize = Mesh->NCellsSize, A.K = NVertLayers;

@@ -39,22 +39,14 @@ VertAdv::VertAdv(const std::string &Name_, const HorzMesh *Mesh_, const VertCoor
    VerticalTransportH = HostArrayReal(Mesh->NCellsSize, NVertLayers);
 }
 
-static void requireRows(const Array2DReal &A, int Rows, int K, const char *What) {
-   OMEGA_REQUIRE(A.Ptr != nullptr, std::string("VertAdv: ") + What + " is empty");
-   OMEGA_REQUIRE(A.Ext[0] >= Rows && A.Ext[1] == K && A.Pitch == levelPitch(K),
-                 std::string("VertAdv: ") + What + " must be [" + std::to_string(Rows) +
-                     "][NVertLayers] with rows of levelPitch(NVertLayers)");
-}
-
+/// a tracer array of the kernel's plane stride: exactly NCellsSize rows per tracer
 static void requirePlanes(const Array3DReal &A, int NT, int Rows, int K, const char *What) {
-   OMEGA_REQUIRE(A.Ptr != nullptr, std::string("VertAdv: ") + What + " is empty");
-   OMEGA_REQUIRE(A.Ext[0] >= NT && A.Ext[1] == Rows && A.Ext[2] == K && A.Pitch == levelPitch(K),
-                 std::string("VertAdv: ") + What + " must be [NTracers][" + std::to_string(Rows) +
-                     "][NVertLayers] with rows of levelPitch(NVertLayers)");
+   requireLevelArray("VertAdv", A, NT, Rows, K, What);
+   OMEGA_REQUIRE(A.Ext[1] == Rows, levelArrayText("VertAdv", What, "[NTracers][" + std::to_string(Rows) + "]"));
 }
 
 void VertAdv::columnLaunch(const Array2DReal &Tend, bool Scan, bool Thick, hipStream_t S) const {
-   requireRows(Tend, Mesh->NCellsSize, NVertLayers, "the thickness tendency");
+   requireLevelArray("VertAdv", Tend, Mesh->NCellsSize, NVertLayers, "the thickness tendency");
    VertAdvColumnArgs A;
    A.NCellsAll = Mesh->NCellsAll, A.K = NVertLayers;
    A.MinLayerCell = VCoord->MinLayerCell.Ptr, A.MaxLayerCell = VCoord->MaxLayerCell.Ptr;
@@ -85,7 +77,7 @@ void VertAdv::addTracerTend(const Array3DReal &Tend, const Array2DReal &H, const
       return;
    requirePlanes(Tend, NTracers, Mesh->NCellsSize, NVertLayers, "the tracer tendency");
    requirePlanes(Tracers, NTracers, Mesh->NCellsSize, NVertLayers, "Tracers");
-   requireRows(H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
+   requireLevelArray("VertAdv", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
    Pacer::Range Timer("VertAdv:addTracerTend", 1);
    VertAdvTracerArgs A;
    A.NCellsAll = Mesh->NCellsAll, A.NCellsSize = Mesh->NCellsSize, A.K = NVertLayers, A.NTracers = NTracers;
@@ -96,9 +88,9 @@ void VertAdv::addTracerTend(const Array3DReal &Tend, const Array2DReal &H, const
 }
 
 void VertAdv::addVelocityTend(const Array2DReal &Tend, const Array2DReal &H, const Array2DReal &U, hipStream_t S) const {
-   requireRows(Tend, Mesh->NEdgesSize, NVertLayers, "the velocity tendency");
-   requireRows(H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
-   requireRows(U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
+   requireLevelArray("VertAdv", Tend, Mesh->NEdgesSize, NVertLayers, "the velocity tendency");
+   requireLevelArray("VertAdv", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
+   requireLevelArray("VertAdv", U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
    Pacer::Range Timer("VertAdv:addVelocityTend", 1);
    VertAdvEdgeArgs A;
    A.NEdgesAll = Mesh->NEdgesAll, A.NCellsSize = Mesh->NCellsSize, A.K = NVertLayers;

@@ -109,19 +109,13 @@ ColumnArgs VertCoord::baseArgs() const {
    return A;
 }
 
-static void requireLevels(const Array2DReal &A, const HorzMesh *M, int K, const char *What) {
-   OMEGA_REQUIRE(A.Ptr != nullptr, std::string("VertCoord: ") + What + " is empty");
-   OMEGA_REQUIRE(A.Ext[0] >= M->NCellsAll && A.Ext[1] == K && A.Pitch == levelPitch(K),
-                 std::string("VertCoord: ") + What +
-                     " must be [NCellsSize][NVertLayers] with rows of levelPitch(NVertLayers)");
-}
 static void requireCells(const Array1DReal &A, const HorzMesh *M, const char *What) {
    OMEGA_REQUIRE(A.Ptr == nullptr || A.Ext[0] >= M->NCellsAll,
                  std::string("VertCoord: ") + What + " must hold NCellsAll values (or be empty: zero)");
 }
 
 void VertCoord::computePressure(const Array2DReal &H, const Array1DReal &Ps, hipStream_t S) {
-   requireLevels(H, Mesh, NVertLayers, "LayerThickness");
+   requireLevelArray("VertCoord", H, Mesh->NCellsAll, NVertLayers, "LayerThickness", "NCellsSize");
    requireCells(Ps, Mesh, "SurfacePressure");
    Pacer::Range Timer("VertCoord:computePressure", 1);
    ColumnArgs A     = baseArgs();
@@ -133,8 +127,8 @@ void VertCoord::computePressure(const Array2DReal &H, const Array1DReal &Ps, hip
 }
 
 void VertCoord::computeZHeight(const Array2DReal &H, const Array2DReal &SpecVol, hipStream_t S) {
-   requireLevels(H, Mesh, NVertLayers, "LayerThickness");
-   requireLevels(SpecVol, Mesh, NVertLayers, "SpecVol");
+   requireLevelArray("VertCoord", H, Mesh->NCellsAll, NVertLayers, "LayerThickness", "NCellsSize");
+   requireLevelArray("VertCoord", SpecVol, Mesh->NCellsAll, NVertLayers, "SpecVol", "NCellsSize");
    Pacer::Range Timer("VertCoord:computeZHeight", 1);
    ColumnArgs A  = baseArgs();
    A.LayerThick  = H.Ptr;
@@ -187,8 +181,8 @@ void VertCoord::computeColumn(const Array2DReal &H, const Array3DReal &Tr, const
                  "VertCoord::computeColumn: the Eos was built for another mesh or layer count");
    OMEGA_REQUIRE(Tr.Ptr != nullptr, "VertCoord::computeColumn: the tracer array is empty");
    const Array2DReal T = tracerRows(Tr, TIndex), Sa = tracerRows(Tr, SIndex);
-   requireLevels(H, Mesh, NVertLayers, "LayerThickness");
-   requireLevels(T, Mesh, NVertLayers, "tracer rows");
+   requireLevelArray("VertCoord", H, Mesh->NCellsAll, NVertLayers, "LayerThickness", "NCellsSize");
+   requireLevelArray("VertCoord", T, Mesh->NCellsAll, NVertLayers, "tracer rows", "NCellsSize");
    requireCells(Ps, Mesh, "SurfacePressure");
    requireCells(Tidal, Mesh, "TidalPotential");
    requireCells(SAL, Mesh, "SelfAttractionLoading");

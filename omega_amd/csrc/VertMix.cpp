@@ -33,13 +33,6 @@ VertMix::VertMix(const std::string &Name_, const HorzMesh *Mesh_, const VertCoor
    BruntVaisalaFreqSqH = HostArrayReal(NC, K);
 }
 
-static void requireRows(const Array2DReal &A, int Rows, int K, const char *What) {
-   OMEGA_REQUIRE(A.Ptr != nullptr, std::string("VertMix: ") + What + " is empty");
-   OMEGA_REQUIRE(A.Ext[0] >= Rows && A.Ext[1] == K && A.Pitch == levelPitch(K),
-                 std::string("VertMix: ") + What + " must be [" + std::to_string(Rows) +
-                     "][NVertLayers] with rows of levelPitch(NVertLayers)");
-}
-
 void VertMix::computeBruntVaisalaFreqSq(const Eos &EqState, hipStream_t S) {
    OMEGA_REQUIRE(EqState.Mesh == Mesh && EqState.NVertLayers == NVertLayers,
                  "VertMix::computeBruntVaisalaFreqSq: the Eos was built for another mesh or layer count");
@@ -50,9 +43,9 @@ void VertMix::computeBruntVaisalaFreqSq(const Eos &EqState, hipStream_t S) {
 }
 
 void VertMix::computeVertMix(const Array2DReal &Un, const Array2DReal &Ut, const Array2DReal &N2, hipStream_t S) {
-   requireRows(Un, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
-   requireRows(Ut, Mesh->NEdgesSize, NVertLayers, "TangentialVelocity");
-   requireRows(N2, Mesh->NCellsSize, NVertLayers, "BruntVaisalaFreqSq");
+   requireLevelArray("VertMix", Un, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
+   requireLevelArray("VertMix", Ut, Mesh->NEdgesSize, NVertLayers, "TangentialVelocity");
+   requireLevelArray("VertMix", N2, Mesh->NCellsSize, NVertLayers, "BruntVaisalaFreqSq");
    Pacer::Range Timer("VertMix:computeVertMix", 1);
    VertMixCoeffArgs A;
    A.NCellsAll = Mesh->NCellsAll, A.NCellsSize = Mesh->NCellsSize, A.K = NVertLayers, A.MaxEdges = Mesh->MaxEdges;
@@ -74,15 +67,13 @@ void VertMix::computeVertMix(const Array2DReal &Un, const Array2DReal &Ut, const
 }
 
 void VertMix::applyTracerVertMix(const Array2DReal &H, const Array3DReal &Tr, int NTracers, Real Dt, hipStream_t S) {
-   requireRows(H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
+   requireLevelArray("VertMix", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
    OMEGA_REQUIRE(NTracers >= 0 && NTracers <= Tr.Ext[0], "VertMix::applyTracerVertMix: NTracers = " +
                                                               std::to_string(NTracers) + " is outside 0 .. " +
                                                               std::to_string(Tr.Ext[0]));
    if (NTracers == 0)
       return;
-   OMEGA_REQUIRE(Tr.Ptr != nullptr, "VertMix: Tracers is empty");
-   OMEGA_REQUIRE(Tr.Ext[1] >= Mesh->NCellsSize && Tr.Ext[2] == NVertLayers && Tr.Pitch == levelPitch(NVertLayers),
-                 "VertMix: Tracers must be [NTracers][NCellsSize][NVertLayers] with rows of levelPitch(NVertLayers)");
+   requireLevelArray("VertMix", Tr, NTracers, Mesh->NCellsSize, NVertLayers, "Tracers", "NCellsSize");
    Pacer::Range Timer("VertMix:applyTracerVertMix", 1);
    launchTracerVertMix(Mesh->NCellsOwned, NVertLayers, VCoord->MinLayerCell.Ptr, VCoord->MaxLayerCell.Ptr, H.Ptr,
                        VertDiff.Ptr, Tr.Ptr, NTracers, Tr.Ext[1], Dt, S);
@@ -99,8 +90,8 @@ void VertMix::applyTracerVertMix(const OceanState *State, int ThickLevel, const 
 }
 
 void VertMix::applyVelocityVertMix(const Array2DReal &H, const Array2DReal &U, Real Dt, hipStream_t S) {
-   requireRows(H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
-   requireRows(U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
+   requireLevelArray("VertMix", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
+   requireLevelArray("VertMix", U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
    Pacer::Range Timer("VertMix:applyVelocityVertMix", 1);
    launchVelocityVertMix(Mesh->NEdgesOwned, NVertLayers, Mesh->CellsOnEdge.Ptr, VCoord->MinLayerEdgeBot.Ptr,
                          VCoord->MaxLayerEdgeTop.Ptr, H.Ptr, VertVisc.Ptr, U.Ptr, Dt, S);

@@ -1,25 +1,18 @@
 // ColumnKernels.hip -- VertCoord (VertCoord.cpp:484-864) and Eos (Eos.h / Eos.cpp) on gfx950.
 //
-// One kernel template over a compile-time stage mask (ColumnKernels.h).  A workgroup of 256 threads owns a tile of
-// `Tile` consecutive cells.  Because the level-indexed arrays are [cell][Pitch] rows, a tile of one array is one
-// contiguous run of Tile*Pitch values: it is staged into LDS with 16-byte-per-lane loads (and written back with
-// 16-byte-per-lane stores) whatever the column length.  The sequential parts (the pressure and z-height scans, the
-// target-thickness sums) run one lane per column out of LDS; the point-wise parts (equation of state, geopotential,
-// target thickness) run with the lanes along the flat [cell][level] run.  The LDS rows are padded to an odd number of
-// doubles so the one-lane-per-column scans read distinct banks.
+// One kernel template over a compile-time stage mask (ColumnKernels.h), on the column tile of LevelTile.h: a workgroup
+// of 256 threads owns a tile of `Tile` consecutive cells, staged into LDS rows of odd pitch.  The sequential parts (the
+// pressure and z-height scans, the target-thickness sums) run one lane per column out of LDS; the point-wise parts
+// (equation of state, geopotential, target thickness) run with the lanes along the flat [cell][level] run.
 //
 // A single-stage instantiation (what VertCoord::computePressure, Eos::computeSpecVol, ... launch) and the fused
 // instantiation (VertCoord::computeColumn) run the same stage code; the results agree bit for bit.
 #include "ColumnKernels.h"
+#include "LevelTile.h"
 
 namespace OMEGA {
 
 namespace {
-
-constexpr int ColThreads = 256;
-
-/// LDS row pitch of a column of `P` values: odd, so that lanes c and c+1 of a scan sit on different banks
-__host__ __device__ inline int ldsPitch(int P) { return P + ((P & 1) == 0 ? 1 : 0); }
 
 /// Offsets (in doubles) of the LDS buffers a stage mask needs, for a tile of `T` columns:
 ///   H  LayerThickness (Pressure, ZHeight) or RefLayerThickness (TargetThickness)        [T][LP]
@@ -41,74 +34,6 @@ struct ColLayout {
       End = Sc + 3 * T;
    }
 };
-
-__device__ inline bool aligned16(const void *P) { return ((uintptr_t)P & 15) == 0; }
-
-/// Visit the flat run [0, N) in pairs (i, i+1), lanes along the run: F(i, Two) with Two = (i+1 < N)
-template <class F> __device__ inline void forPairs(int N, F &&Fn) {
-   for (int I = 2 * (int)threadIdx.x; I < N; I += 2 * ColThreads)
-      Fn(I, I + 1 < N);
-}
-
-__device__ inline void load2(const Real *P, bool Two, Real &V0, Real &V1) {
-   if (Two && aligned16(P)) {
-      const double2 V = *reinterpret_cast<const double2 *>(P);
-      V0 = V.x, V1 = V.y;
-   } else {
-      V0 = P[0];
-      V1 = Two ? P[1] : 0.0;
-   }
-}
-
-__device__ inline void store2(Real *P, bool W0, bool W1, Real V0, Real V1) {
-   if (W0 && W1 && aligned16(P)) {
-      *reinterpret_cast<double2 *>(P) = make_double2(V0, V1);
-   } else {
-      if (W0)
-         P[0] = V0;
-      if (W1)
-         P[1] = V1;
-   }
-}
-
-/// (cell, level) of flat position I of a run of rows of pitch P, and of I + 1
-struct Pos2 {
-   int C0, K0, C1, K1;
-   __device__ Pos2(int I, int P) {
-      C0 = I / P;
-      K0 = I - C0 * P;
-      C1 = C0, K1 = K0 + 1;
-      if (K1 == P)
-         C1 += 1, K1 = 0;
-   }
-};
-
-/// Stage Nc columns of a [cell][P] array starting at row C0 into LDS rows of pitch LP.  Want(c, k) selects the values
-/// to keep (the loads are issued for whole pairs: both are inside the rows being read).
-template <class W>
-__device__ inline void loadTile(const Real *G, int P, int C0, int Nc, Real *L, int LP, W &&Want) {
-   const Real *Gt = G + (size_t)C0 * P;
-   forPairs(Nc * P, [&](int I, bool Two) {
-      const Pos2 Q(I, P);
-      Real V0, V1;
-      load2(Gt + I, Two, V0, V1);
-      if (Want(Q.C0, Q.K0))
-         L[Q.C0 * LP + Q.K0] = V0;
-      if (Two && Want(Q.C1, Q.K1))
-         L[Q.C1 * LP + Q.K1] = V1;
-   });
-}
-
-/// Write the LDS values (c, k) with Want(c, k) back to a [cell][P] array
-template <class W>
-__device__ inline void storeTile(Real *G, int P, int C0, int Nc, const Real *L, int LP, W &&Want) {
-   Real *Gt = G + (size_t)C0 * P;
-   forPairs(Nc * P, [&](int I, bool Two) {
-      const Pos2 Q(I, P);
-      const bool W0 = Want(Q.C0, Q.K0), W1 = Two && Want(Q.C1, Q.K1);
-      store2(Gt + I, W0, W1, W0 ? L[Q.C0 * LP + Q.K0] : 0.0, W1 ? L[Q.C1 * LP + Q.K1] : 0.0);
-   });
-}
 
 // ---- TEOS-10: the 75-term polynomial for specific volume of Roquet, Madec, McDougall and Barker (2015), "Accurate
 // polynomial expressions for the density and specific volume of seawater using the TEOS-10 standard", Ocean
@@ -203,20 +128,14 @@ template <unsigned M> __global__ __launch_bounds__(ColThreads) void columnKernel
 
    // per-column active range (all levels without one: the equation of state); a column outside
    // 0 <= KMin <= KMax < K is left untouched by the range stages
-   if (Tid < Nc) {
-      const I4 KMin = A.MinLayer ? A.MinLayer[C0 + Tid] : 0, KMax = A.MaxLayer ? A.MaxLayer[C0 + Tid] : K - 1;
-      const bool Ok = KMin >= 0 && KMin <= KMax && KMax < K;
-      Lo[Tid] = Ok ? KMin : 1;
-      Hi[Tid] = Ok ? KMax : -1;
-      if (Geo) {
-         Sc0[Tid] = A.Tidal ? A.Tidal[C0 + Tid] : 0.0;
-         Sc1[Tid] = A.SAL ? A.SAL[C0 + Tid] : 0.0;
-      }
+   stageRanges(A.MinLayer, A.MaxLayer, C0, Nc, K, Lo, Hi);
+   if (Geo && Tid < Nc) {
+      Sc0[Tid] = A.Tidal ? A.Tidal[C0 + Tid] : 0.0;
+      Sc1[Tid] = A.SAL ? A.SAL[C0 + Tid] : 0.0;
    }
    __syncthreads();
-   auto All      = [](int, int) { return true; };
-   auto Active   = [&](int C, int Kk) { return Kk >= Lo[C] && Kk <= Hi[C]; };
-   auto ActiveP1 = [&](int C, int Kk) { return Kk >= Lo[C] && Kk <= Hi[C] + 1; };
+   const AllLevels All;
+   const InRange Active{Lo, Hi}, ActiveP1{Lo, Hi, 1};
 
    // ---- stage the inputs
    if (Press || Zh)
@@ -396,16 +315,10 @@ constexpr unsigned FusedMask = StagePressure | StageSpecVol | StageZHeight | Sta
 
 void launchColumn(unsigned Mask, const ColumnArgs &A, hipStream_t S) {
    OMEGA_REQUIRE(A.NCells > 0 && A.K > 0, "column kernel: empty mesh or column");
-   // largest tile (columns per workgroup) whose LDS fits 64 KiB
    const int LP = ldsPitch(A.Pitch), LP1 = ldsPitch(A.Pitch1);
-   int Tile = 16;
-   size_t Bytes = 0;
-   for (; Tile >= 2; Tile /= 2) {
-      Bytes = (size_t)ColLayout(Mask, Tile, LP, LP1).End * sizeof(Real);
-      if (Bytes <= 65536)
-         break;
-   }
+   const int Tile = pickColumnTile([&](int T) { return ColLayout(Mask, T, LP, LP1).End; });
    OMEGA_REQUIRE(Tile >= 2, "column kernel: NVertLayers " + std::to_string(A.K) + " is too long for the LDS tile");
+   const size_t Bytes = (size_t)ColLayout(Mask, Tile, LP, LP1).End * sizeof(Real);
    switch (Mask) {
    case StagePressure: launchMask<StagePressure>(A, Tile, Bytes, S); break;
    case StageSpecVol: launchMask<StageSpecVol>(A, Tile, Bytes, S); break;

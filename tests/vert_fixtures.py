@@ -1,6 +1,6 @@
 """Shared rigs of the vertical-column GPU tests (VertCoord / Eos: `Col`; VertMix: `Mix`), the layer-range generators
-they draw from, and Python restatements of the launch rules of kernels/ColumnKernels.hip and
-kernels/VertMixKernels.hip (which tile, how many columns per workgroup, how many right-hand sides per pass, how much
+they draw from, and Python restatements of the launch rules of kernels/ColumnKernels.hip, kernels/VertAdvKernels.hip
+(its column launch) and kernels/VertMixKernels.hip (which tile, how many columns per workgroup, how many right-hand sides per pass, how much
 LDS), so that a shape sweep can assert which branch each of its cases lands on."""
 import numpy as np
 
@@ -60,6 +60,28 @@ def column_limit(mask):
     """the largest NVertLayers a column launch of this stage mask accepts"""
     K = 1
     while column_tile(mask, K + 1) is not None:
+        K += 1
+    return K
+
+
+def vert_adv_lds_doubles(tile, K):
+    """VertAdvKernels.hip colLdsDoubles: three [tile][LP] buffers (tendency, reference thickness or nothing,
+    transport) and the per-column layer range (2 x tile ints = tile doubles)"""
+    return tile * (3 * lds_pitch(level_pitch(K)) + 1)
+
+
+def vert_adv_tile(K):
+    """vertAdvColumnTile: the largest of 16, 8, 4, 2 columns per workgroup whose LDS fits 64 KiB; None: refused"""
+    for tile in (16, 8, 4, 2):
+        if vert_adv_lds_doubles(tile, K) * 8 <= LDS_BYTES:
+            return tile
+    return None
+
+
+def vert_adv_limit():
+    """the largest NVertLayers the VertAdv column launch accepts (VertAdv::maxLayers)"""
+    K = 1
+    while vert_adv_tile(K + 1) is not None:
         K += 1
     return K
 
