@@ -39,6 +39,7 @@ typedef struct omg_vcoord omg_vcoord;   /* O/src/ocn/VertCoord.h class VertCoord
 typedef struct omg_eos omg_eos;         /* O/src/ocn/Eos.h       class Eos           */
 typedef struct omg_vertmix omg_vertmix; /* O/doc/design/VerticalMixingCoeff.md (design only) */
 typedef struct omg_pgrad omg_pgrad;     /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
+typedef struct omg_vertmix_step omg_vertmix_step; /* O/doc/design/OmegaV1GoverningEqns.md section 11 (design only) */
 typedef struct omg_vertadv omg_vertadv; /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
 
 enum { OMG_ON_CELL = 0, OMG_ON_EDGE = 1, OMG_ON_VERTEX = 2 }; /* O/src/base/Halo.h:45 MeshElement */
@@ -551,6 +552,52 @@ int omg_vertmix_apply_velocity(omg_vertmix *x, const double *layer_thickness_dev
 int omg_vertmix_copy_to_host(const omg_vertmix *x, const char *name, double *host, size_t n);
 int omg_vertmix_copy_to_device(omg_vertmix *x, const char *name, const double *host, size_t n);
 int omg_vertmix_device_ptr(const omg_vertmix *x, const char *name, double **dev, size_t *n);
+
+/* The forced solves (O/doc/design/OmegaV1GoverningEqns.md section 11, "Forcing at the top and bottom of the ocean";
+ * contract in omega_amd/csrc/VertMix.h).  surface_flux_dev: ntracers x NCellsSize values, tracer-major, tracer units *
+ * m/s, positive into the ocean, added to the top row's right-hand side (NULL: no flux). */
+int omg_vertmix_apply_tracers_forced(omg_vertmix *x, const double *layer_thickness_dev, double *tracers_dev, int ntracers,
+                                     double dt, const double *surface_flux_dev, void *stream);
+/* Wind stress normal_stress_dev [NEdgesSize] (Pa; NULL: none) as the top boundary condition, the linearised quadratic
+ * bottom drag bottom_drag_coeff * |u| with the speed from the edge's own normal and tangential velocity as the bottom
+ * one (tangential_velocity_dev [NEdgesSize][pitch], required iff bottom_drag_coeff != 0) and Rayleigh drag
+ * rayleigh_drag_coeff (1/s) on every level.  A negative coefficient fails; a zero one skips its term; with every
+ * term skipped the result is omg_vertmix_apply_velocity's bit for bit. */
+int omg_vertmix_apply_velocity_forced(omg_vertmix *x, const double *layer_thickness_dev, double *normal_velocity_dev,
+                                      double dt, double bottom_drag_coeff, double rayleigh_drag_coeff,
+                                      const double *normal_stress_dev, const double *tangential_velocity_dev,
+                                      void *stream);
+
+/* ---- VertMixStep: the whole mixing sequence of a step as one call (omega_amd/csrc/VertMixStep.h): the displaced column
+ * pass (temperature at tracer 0, salinity at 1), N2, the tangential velocity, the coefficients, the forced tracer solve
+ * and the forced velocity solve, equal bit for bit to those six calls made one by one.  The object keeps pointers to x,
+ * v and e: destroy it before them.  It allocates in create only. ---- */
+/* fails for a host-only mesh, x / v / e NULL or of another mesh or layer count, ntracers < 2 and more than 1008 layers
+ * (the fused column pass's limit) */
+int omg_vertmix_step_create(const omg_mesh *m, omg_vertmix *x, omg_vcoord *v, omg_eos *e, int ntracers,
+                            omg_vertmix_step **out);
+int omg_vertmix_step_destroy(omg_vertmix_step *ms);
+/* the coefficients of the velocity solve (>= 0; both 0 at creation) and whether NormalStressEdge is applied (off) */
+int omg_vertmix_step_set_boundary(omg_vertmix_step *ms, double bottom_drag_coeff, double rayleigh_drag_coeff,
+                                  int use_wind_stress);
+/* layer_thickness_dev [NCellsSize][pitch]; normal_velocity_dev [NEdgesSize][pitch] and tracers_dev
+ * [ntracers][NCellsSize][pitch] are mixed in place */
+int omg_vertmix_step_apply(omg_vertmix_step *ms, const double *layer_thickness_dev, double *normal_velocity_dev,
+                           double *tracers_dev, double dt, void *stream);
+/* the same on time level time_level of s and tracer_time_level of t */
+int omg_vertmix_step_apply_state(omg_vertmix_step *ms, const omg_state *s, int time_level, const omg_tracers *t,
+                                 int tracer_time_level, double dt, void *stream);
+/* "TangentialVelocity" ([NEdgesSize][K]), "NormalStressEdge" ([NEdgesSize]), "SurfaceTracerFlux" ([ntracers][NCellsSize]),
+ * "SurfacePressure", "TidalPotential", "SelfAttractionLoading" ([NCellsSize]); all zero at creation */
+int omg_vertmix_step_copy_to_host(const omg_vertmix_step *ms, const char *name, double *host, size_t n);
+int omg_vertmix_step_copy_to_device(omg_vertmix_step *ms, const char *name, const double *host, size_t n);
+int omg_vertmix_step_device_ptr(const omg_vertmix_step *ms, const char *name, double **dev, size_t *n);
+/* TimeStepper::attachVertMix: every omg_stepper_do_step runs the sequence on the new time level with dt = the time step,
+ * immediately before the time levels rotate (ms NULL: detach).  Fails for another mesh, layer or tracer count, and for
+ * a stepper whose halo has neighbours: multi-rank mixing needs the halo of the new level before and after the solve and
+ * is not built.  While attached RungeKutta4 runs its plain stage sequence and nothing is replayed as a graph.  Detach
+ * before destroying ms. */
+int omg_stepper_attach_vert_mix(omg_stepper *st, omg_vertmix_step *ms);
 
 /* ---- PressureGrad: the layered-ocean pressure-gradient force on edges, -(grad Phi) - alpha grad p along the layers
  * (O/doc/design/OmegaV1GoverningEqns.md, discrete momentum equation; the reference has no code for it).  Numerical

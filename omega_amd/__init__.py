@@ -2,7 +2,8 @@
 
 Thin ctypes plumbing used by tests/, bench.py and __graft_entry__.py: the product is the
 C++/HIP library under omega_amd/csrc (classes named after Omega's own: Decomp, Halo,
-HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, PressureGrad, VertAdv, Tendencies, TimeStepper).  There is no
+HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, VertMix, VertMixStep, PressureGrad, VertAdv, Tendencies,
+TimeStepper).  There is no
 Python or CPU implementation of the hot path here: if the shared library is missing,
 importing the binding raises, and without a HIP device every device call fails.
 """
@@ -943,6 +944,17 @@ def _cell_dev(x, rows: int, keep: list):
     return C.c_void_p(b.ptr)
 
 
+def _flat_dev(x, shape: tuple, keep: list):
+    """An array without a level index as a device pointer: an int device address or a numpy array of `shape`."""
+    if isinstance(x, (int, np.integer)):
+        return C.c_void_p(int(x))
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    assert a.shape == shape, f"expected shape {shape}, got {a.shape}"
+    b = DeviceBuffer(a)
+    keep.append(b)
+    return C.c_void_p(b.ptr)
+
+
 def tracer_rows_ptr(tracers: Tracers, index: int, time_level: int = 0) -> int:
     """Device address of the rows of tracer `index` ([NCellsSize][level_pitch(K)]) in the tracer array: a view
     with no copy, what Eos.compute_spec_vol takes for T and S."""
@@ -1114,24 +1126,81 @@ class VertMix(_Handle, _NamedArrays):
         if keep:
             device_synchronize()
 
-    def apply_tracers(self, layer_thickness, tracers, ntracers: int, dt: float, stream=None):
-        """Backward-Euler diffusion of tracers [ntracers][NCellsSize][K] with VertDiff, all in one pass"""
+    def apply_tracers(self, layer_thickness, tracers, ntracers: int, dt: float, stream=None, surface_flux=None):
+        """Backward-Euler diffusion of tracers [ntracers][NCellsSize][K] with VertDiff, all in one pass.  surface_flux
+        (a numpy array [ntracers][NCellsSize] or a device address; tracer units * m/s, positive into the ocean) goes
+        through the forced solve; None calls the unforced entry point."""
         keep, n = [], self.mesh.NCellsSize
         h = _level_dev(layer_thickness, n, self.K, keep)
         p, buf = _stage_levels(tracers, (int(ntracers), n), self.K)
-        _chk(lib().omg_vertmix_apply_tracers(self.h, h, p, int(ntracers), C.c_double(dt), _sh(stream)))
+        if surface_flux is None:
+            _chk(lib().omg_vertmix_apply_tracers(self.h, h, p, int(ntracers), C.c_double(dt), _sh(stream)))
+        else:
+            f = _flat_dev(surface_flux, (int(ntracers), n), keep)
+            _chk(lib().omg_vertmix_apply_tracers_forced(self.h, h, p, int(ntracers), C.c_double(dt), f, _sh(stream)))
+            if keep:
+                device_synchronize()
         return _read_back(buf, self.K, stream)
 
-    def apply_velocity(self, layer_thickness, normal_velocity, dt: float, stream=None):
-        """Backward-Euler diffusion of the normal velocity [NEdgesSize][K] with VertVisc averaged to the edges"""
+    def apply_velocity(self, layer_thickness, normal_velocity, dt: float, stream=None, boundary=None, stress=None,
+                       ut=None):
+        """Backward-Euler diffusion of the normal velocity [NEdgesSize][K] with VertVisc averaged to the edges.
+        boundary = (BottomDragCoeff, RayleighDragCoeff), stress [NEdgesSize] (Pa) and ut [NEdgesSize][K] (needed with a
+        bottom drag) go through the forced solve; with all three None the unforced entry point is called."""
         keep = []
         h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
         p, buf = _stage_levels(normal_velocity, (self.mesh.NEdgesSize,), self.K)
-        _chk(lib().omg_vertmix_apply_velocity(self.h, h, p, C.c_double(dt), _sh(stream)))
+        if boundary is None and stress is None and ut is None:
+            _chk(lib().omg_vertmix_apply_velocity(self.h, h, p, C.c_double(dt), _sh(stream)))
+        else:
+            cd, ra = boundary if boundary is not None else (0.0, 0.0)
+            ne = self.mesh.NEdgesSize
+            t = None if stress is None else _flat_dev(stress, (ne,), keep)
+            v = None if ut is None else _level_dev(ut, ne, self.K, keep)
+            _chk(lib().omg_vertmix_apply_velocity_forced(self.h, h, p, C.c_double(dt), C.c_double(cd), C.c_double(ra),
+                                                         t, v, _sh(stream)))
+            if keep:
+                device_synchronize()
         return _read_back(buf, self.K, stream)
 
     def _shape(self, name):
         return (self.mesh.NCellsSize, self.K)
+
+
+class VertMixStep(_Handle, _NamedArrays):
+    """VertMixStep (omega_amd/csrc/VertMixStep.h): the displaced column pass, N^2, the tangential velocity, the
+    coefficients and the forced tracer and velocity solves as one call.  Its arrays (TangentialVelocity,
+    NormalStressEdge, SurfaceTracerFlux, SurfacePressure, TidalPotential, SelfAttractionLoading) are zero at creation
+    and set with `set`; the coefficients and the wind-stress switch with `set_boundary`."""
+    _destroy, _arrays = "omg_vertmix_step_destroy", "omg_vertmix_step"
+
+    def __init__(self, mesh: HorzMesh, vert_mix: "VertMix | None", vcoord: "VertCoord | None", eos: "Eos | None",
+                 ntracers: int):
+        self.mesh, self.vert_mix, self.vcoord, self.eos, self.NT = mesh, vert_mix, vcoord, eos, int(ntracers)
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self._create("omg_vertmix_step_create", mesh.h, vert_mix.h if vert_mix is not None else None,
+                     vcoord.h if vcoord is not None else None, eos.h if eos is not None else None, int(ntracers))
+
+    def set_boundary(self, bottom_drag_coeff: float = 0.0, rayleigh_drag_coeff: float = 0.0,
+                     use_wind_stress: bool = False):
+        _chk(lib().omg_vertmix_step_set_boundary(self.h, C.c_double(bottom_drag_coeff), C.c_double(rayleigh_drag_coeff),
+                                                 int(use_wind_stress)))
+
+    def apply(self, layer_thickness: int, normal_velocity: int, tracers: int, dt: float, stream=None):
+        """On device addresses: thickness [NCellsSize][pitch]; velocity [NEdgesSize][pitch] and tracers
+        [NT][NCellsSize][pitch] are mixed in place, asynchronously on `stream`."""
+        _chk(lib().omg_vertmix_step_apply(self.h, C.c_void_p(int(layer_thickness)), C.c_void_p(int(normal_velocity)),
+                                          C.c_void_p(int(tracers)), C.c_double(dt), _sh(stream)))
+
+    def apply_state(self, state: OceanState, tracers: Tracers, dt: float, time_level: int = 0,
+                    tracer_time_level: int = 0, stream=None):
+        _chk(lib().omg_vertmix_step_apply_state(self.h, state.h, int(time_level), tracers.h, int(tracer_time_level),
+                                                C.c_double(dt), _sh(stream)))
+
+    def _shape(self, name):
+        m = self.mesh
+        return {"TangentialVelocity": (m.NEdgesSize, self.K), "NormalStressEdge": (m.NEdgesSize,),
+                "SurfaceTracerFlux": (self.NT, m.NCellsSize)}.get(name, (m.NCellsSize,))
 
 
 PGRAD_ARRAYS = ("SurfacePressure", "TidalPotential", "SelfAttractionLoading")
@@ -1373,6 +1442,12 @@ class TimeStepper(_Handle):
         self.refs = (tend, aux, mesh, halo, tracers)
         self._create("omg_stepper_create", kind.encode(), C.c_double(dt), tend.h, aux.h, mesh.h, halo.h if halo else None,
                      tracers.h)
+
+    def attach_vert_mix(self, vert_mix_step: "VertMixStep | None"):
+        """TimeStepper::attachVertMix: every do_step runs the mixing sequence on the new time level before the time
+        levels rotate (None detaches); raises for another mesh, layer or tracer count and for a halo with neighbours."""
+        _chk(lib().omg_stepper_attach_vert_mix(self.h, vert_mix_step.h if vert_mix_step is not None else None))
+        self._vert_mix_step = vert_mix_step  # the library keeps a pointer to it
 
     def do_step(self, state: OceanState, stream=None):
         _chk(lib().omg_stepper_do_step(self.h, state.h, _sh(stream)))

@@ -1,6 +1,7 @@
 // TimeStepper.cpp -- see TimeStepper.h.
 #include "TimeStepper.h"
 #include "Pacer.h"
+#include "VertMixStep.h"
 
 #include <cfloat>
 #include <cmath>
@@ -221,6 +222,25 @@ void TimeStepper::finalizeInit() {
                              Tend->NTracers);
 }
 
+void TimeStepper::attachVertMix(VertMixStep *Mix) {
+   if (Mix) {
+      OMEGA_REQUIRE(Tend && Mesh && Trc, "TimeStepper::attachVertMix: attachData first");
+      OMEGA_REQUIRE(Mix->Mesh == Mesh && Mix->NVertLayers == Tend->LayerThicknessTend.Ext[1],
+                    "TimeStepper::attachVertMix: the VertMixStep was built for another mesh or layer count");
+      OMEGA_REQUIRE(Mix->NTracers == Trc->NTracers,
+                    "TimeStepper::attachVertMix: the VertMixStep was built for another tracer count");
+      OMEGA_REQUIRE(!MeshHalo || MeshHalo->NNghbr == 0,
+                    "TimeStepper::attachVertMix: this stepper's halo has neighbours: multi-rank mixing needs the halo of "
+                    "the new level before and after the solve and is not built");
+   }
+   VMixStep = Mix;
+}
+
+void TimeStepper::mixNewLevel(OceanState *State, hipStream_t S) const {
+   if (VMixStep)
+      VMixStep->apply(State, 1, Trc, 1, TimeStepSeconds, S);
+}
+
 // ---- update kernels ----
 void TimeStepper::updateThicknessByTend(OceanState *S1, int L1, OceanState *S2, int L2, R8 C, hipStream_t S) const {
    Array2DReal H1, H2;
@@ -310,6 +330,7 @@ void ForwardBackwardStepper::doStep(OceanState *State, hipStream_t S) {
    Tend->ModelTime = T0 + Dt;
    Tend->computeVelocityTendencies(State, AuxState, NextLevel, CurLevel, S);
    updateVelocityByTend(State, NextLevel, State, CurLevel, Dt, S);
+   mixNewLevel(State, S);
    updateTimeLevels(State, S);
    ++NStepsDone;
 }
@@ -331,6 +352,7 @@ void RungeKutta2Stepper::doStep(OceanState *State, hipStream_t S) {
    Tend->computeAllTendencies(State, AuxState, NextTracerArray, NextLevel, NextLevel, S);
    updateStateByTend(State, NextLevel, State, CurLevel, Full, S);
    updateTracersByTend(NextTracerArray, CurTracerArray, State, NextLevel, State, CurLevel, Full, S);
+   mixNewLevel(State, S);
    updateTimeLevels(State, S);
    ++NStepsDone;
 }
@@ -412,6 +434,8 @@ void RungeKutta4Stepper::joinExchange(hipStream_t S) {
 }
 
 bool RungeKutta4Stepper::doStepFused(OceanState *State, hipStream_t S) {
+   if (VMixStep) // the mixing sequence follows the plain stage sequence; nothing of it goes into a graph
+      return false;
    const int CurLevel = 0, NextLevel = 1;
    const int NT = Trc->NTracers;
    const int K  = Tend->LayerThicknessTend.Ext[1];
@@ -562,6 +586,7 @@ void RungeKutta4Stepper::doStep(OceanState *State, hipStream_t S) {
       }
    }
    finalizeTracersUpdate(NextTracerArray, State, NextLevel, S);
+   mixNewLevel(State, S);
    updateTimeLevels(State, S);
    ++NStepsDone;
 }

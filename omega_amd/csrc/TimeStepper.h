@@ -21,6 +21,8 @@
 
 namespace OMEGA {
 
+class VertMixStep;
+
 enum class TimeStepperType { ForwardBackward, RungeKutta4, RungeKutta2, Invalid };
 
 class TimeStepper {
@@ -46,6 +48,15 @@ class TimeStepper {
    /// after attachData: creates whatever a step needs, so that doStep allocates nothing (base: the halo's job tables
    /// and message buffers for the end-of-step exchange of h, u and the tracers)
    virtual void finalizeInit();
+
+   /// Opt-in (after attachData): every doStep runs Mix->apply on the NEW time level (thickness, velocity, tracers) with
+   /// Dt = TimeStepSeconds immediately before the time levels rotate; nullptr detaches.  Refuses (OmegaError) a
+   /// VertMixStep of another mesh, layer count or tracer count, and a stepper whose Halo has neighbours: multi-rank
+   /// mixing needs the halo of the new level before and after the solve and is not built.  While attached
+   /// RungeKutta4 runs its plain stage sequence and nothing is captured into a graph; a step still creates no device
+   /// buffer, stream or event.
+   void attachVertMix(VertMixStep *Mix);
+   VertMixStep *vertMix() const { return VMixStep; }
 
    /// advance State (and the attached tracers) by one step on stream S
    virtual void doStep(OceanState *State, hipStream_t S) = 0;
@@ -125,6 +136,8 @@ class TimeStepper {
    /// end-of-step: halo exchange of the new level, then rotate (State->updateTimeLevels();
    /// Tracers::updateTimeLevels()) -- h, u and tracers travel in one message per neighbour
    void updateTimeLevels(OceanState *State, hipStream_t S) const;
+   /// the attached VertMixStep, if any, on the new time level (called right before updateTimeLevels)
+   void mixNewLevel(OceanState *State, hipStream_t S) const;
    /// first thing in every doStep: a peer-wire wait of an EARLIER step that gave up is reported now (the status word is
    /// host memory: no synchronisation); the halo of that step was left untouched and the state is not to be trusted
    void requireHealthyWire() const;
@@ -133,6 +146,7 @@ class TimeStepper {
    const HorzMesh *Mesh     = nullptr;
    Halo *MeshHalo           = nullptr;
    TracerStore *Trc         = nullptr;
+   VertMixStep *VMixStep    = nullptr;
 };
 
 class ForwardBackwardStepper : public TimeStepper {

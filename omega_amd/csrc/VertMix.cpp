@@ -105,6 +105,51 @@ void VertMix::applyVelocityVertMix(const OceanState *State, int Level, Real Dt, 
    applyVelocityVertMix(H, U, Dt, S);
 }
 
+void VertMix::requireBoundary(const VertMixBoundary &B) {
+   OMEGA_REQUIRE(B.BottomDragCoeff >= 0.0, "VertMix: BottomDragCoeff = " + std::to_string(B.BottomDragCoeff) +
+                                               " is negative: drag coefficients must be >= 0");
+   OMEGA_REQUIRE(B.RayleighDragCoeff >= 0.0, "VertMix: RayleighDragCoeff = " + std::to_string(B.RayleighDragCoeff) +
+                                                 " is negative: drag coefficients must be >= 0");
+}
+
+void VertMix::applyTracerVertMix(const Array2DReal &H, const Array3DReal &Tr, int NTracers, Real Dt,
+                                 const Array2DReal &Flux, hipStream_t S) {
+   requireLevelArray("VertMix", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
+   OMEGA_REQUIRE(NTracers >= 0 && NTracers <= Tr.Ext[0], "VertMix::applyTracerVertMix: NTracers = " +
+                                                              std::to_string(NTracers) + " is outside 0 .. " +
+                                                              std::to_string(Tr.Ext[0]));
+   if (NTracers == 0)
+      return;
+   requireLevelArray("VertMix", Tr, NTracers, Mesh->NCellsSize, NVertLayers, "Tracers", "NCellsSize");
+   OMEGA_REQUIRE(Flux.Ptr == nullptr ||
+                     (Flux.Ext[0] >= NTracers && Flux.Ext[1] == Mesh->NCellsSize && Flux.Pitch == Mesh->NCellsSize),
+                 "VertMix: SurfaceTracerFlux must be [NTracers][NCellsSize]");
+   Pacer::Range Timer("VertMix:applyTracerVertMixForced", 1);
+   launchTracerVertMixForced(Mesh->NCellsOwned, NVertLayers, VCoord->MinLayerCell.Ptr, VCoord->MaxLayerCell.Ptr, H.Ptr,
+                             VertDiff.Ptr, Tr.Ptr, NTracers, Tr.Ext[1], Dt, Flux.Ptr, (size_t)Mesh->NCellsSize, S);
+}
+
+void VertMix::applyVelocityVertMix(const Array2DReal &H, const Array2DReal &U, Real Dt, const VertMixBoundary &B,
+                                   const Array1DReal &Stress, const Array2DReal &Ut, hipStream_t S) {
+   requireBoundary(B);
+   requireLevelArray("VertMix", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
+   requireLevelArray("VertMix", U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
+   OMEGA_REQUIRE(Stress.Ptr == nullptr || Stress.Ext[0] == Mesh->NEdgesSize,
+                 "VertMix: NormalStressEdge must be [NEdgesSize]");
+   if (B.BottomDragCoeff != 0.0) {
+      OMEGA_REQUIRE(Ut.Ptr != nullptr, "VertMix: BottomDragCoeff != 0 needs the tangential velocity");
+      requireLevelArray("VertMix", Ut, Mesh->NEdgesSize, NVertLayers, "TangentialVelocity");
+   }
+   Pacer::Range Timer("VertMix:applyVelocityVertMixForced", 1);
+   VelocityForcingArgs F;
+   F.DtBottomDrag = Dt * B.BottomDragCoeff, F.DtRayleigh = Dt * B.RayleighDragCoeff;
+   F.Rho0   = VCoord->Rho0;
+   F.Stress = Stress.Ptr, F.EdgeMask = Mesh->EdgeMask1D.Ptr;
+   F.Ut     = B.BottomDragCoeff != 0.0 ? Ut.Ptr : nullptr;
+   launchVelocityVertMixForced(Mesh->NEdgesOwned, NVertLayers, Mesh->CellsOnEdge.Ptr, VCoord->MinLayerEdgeBot.Ptr,
+                               VCoord->MaxLayerEdgeTop.Ptr, H.Ptr, VertVisc.Ptr, U.Ptr, Dt, F, S);
+}
+
 void VertMix::copyToHost() {
    HIP_CHECK(hipDeviceSynchronize());
    OMEGA::copyToHost(VertDiffH.data(), VertDiff);

@@ -35,7 +35,37 @@
 //      hE[k] = 0.5 * (h[c1][k] + h[c2][k]); nuE[k] = 0.5 * (VertVisc[c1][k] + VertVisc[c2][k])
 //      H_i = hE[k]; G_i = (nuE[k+1] * Dt) / ((hE[k+1] + hE[k]) / 2), G_{n-1} = 0; X_i = hE[k] * u[k]
 //
+// The forced solves (the overloads with a VertMixBoundary / a SurfaceTracerFlux) put the reference's "forcing at the
+// top and bottom of the ocean" (components/omega/doc/design/OmegaV1GoverningEqns.md section 11) into the same
+// backward-Euler systems: wind stress as the top boundary condition, bottom drag as the bottom boundary condition,
+// Rayleigh drag on every row, surface tracer fluxes on the top row.  Same precision rules (FP64, no contraction, IEEE
+// division and sqrt, every chain in the order written); restated in tests/vert_mix_forcing_reference.py.
+//  - applyVelocityVertMix(h, u, Dt, Boundary, NormalStressEdge, Ut): owned edges with a non-empty range Lo .. Hi,
+//    n = Hi-Lo+1, row i = level k = Lo+i; hE[k], nuE[k] and G_i exactly as above:
+//      D_i = hE[k]
+//      if RayleighDragCoeff != 0:             D_i = D_i + (Dt*RayleighDragCoeff)*hE[k]
+//      if i == n-1 and BottomDragCoeff != 0:  Speed = sqrt((u[e][Hi]*u[e][Hi]) + (Ut[e][Hi]*Ut[e][Hi]))   (u before the solve)
+//                                             D_i = D_i + (Dt*BottomDragCoeff)*Speed
+//      X_i = hE[k]*u[e][k]
+//      if i == 0 and a stress array is given: X_i = X_i + (Dt*EdgeMask[e])*(NormalStressEdge[e]/Rho0)
+//      u[e][Lo..Hi] <- the PCRDiffusionSolver arithmetic on (G, D, X): D stands where H stood
+//    NormalStressEdge is [NEdgesSize] in Pa (an empty array: no stress); Ut is [NEdgesSize][pitch], required iff
+//    BottomDragCoeff != 0.  n == 1 takes both boundary terms on its one row (the 1x1 solve).  A term whose
+//    coefficient is zero, or whose array is absent, is skipped; with all terms skipped the result equals the unforced
+//    call bit for bit.  Negative coefficients are refused.  An edge with an empty range is left alone whatever its
+//    stress.
+//  - applyTracerVertMix(h, Tracers, NTracers, Dt, SurfaceTracerFlux): SurfaceTracerFlux holds NTracers x NCellsSize
+//    values, tracer-major, in tracer units * m/s, positive into the ocean (an empty array: no flux).  For an owned
+//    cell, with rows as in applyTracerVertMix:
+//      X_0 = (h[KMin]*phi[KMin]) + Dt*SurfaceTracerFlux[L][c]
+//    Every other row, G and H are unchanged, so the once-per-column recursion is still shared by all tracers.
+//  - Both write nothing outside what the unforced calls write.
+//  - Freshwater as a mass flux (a thickness source) is out of scope: only tracer fluxes through a fixed surface.
+//
 // Deviations from the design document:
+//  - Bottom drag: the linearised implicit form Cd |u^n| u^{n+1} on the bottom row's diagonal, stable for any Dt*Cd,
+//    with the speed from the edge's own normal and tangential velocity (the governing-equation document's u|u|), not
+//    from the cell kinetic energies that Omega-0's explicit BottomDragOnEdge averages to the edge.
 //  - N2 form: the document writes N2 = g rho0 (rho_DD - rho) / (z(k-1) - z(k)), which has the wrong sign for stable
 //    water and units other than s^-2; the form above is the document's with g / rho0 and the sign that makes N2 > 0
 //    for stable water (lighter above), with rho = 1 / SpecVol.  It lives on VertMix, not in the equation of state.
@@ -73,6 +103,12 @@ struct VertMixConfig {
    Real ConvectiveTriggerBVF  = 0.0;
 };
 
+/// Coefficients of the forced velocity solve; both >= 0 (refused otherwise), 0 switches the term off
+struct VertMixBoundary {
+   Real BottomDragCoeff   = 0; ///< dimensionless Cd of the quadratic bottom drag
+   Real RayleighDragCoeff = 0; ///< s^-1
+};
+
 class VertMix : public Registry<VertMix> {
  public:
    /// Refuses (OmegaError) negative viscosities or diffusivities, NVertLayers above the tridiagonal limit (1024), a
@@ -99,6 +135,15 @@ class VertMix : public Registry<VertMix> {
                              hipStream_t S);
    /// thickness and normal velocity of State at time level Level
    void applyVelocityVertMix(const OceanState *State, int Level, Real Dt, hipStream_t S);
+   /// The forced solves (contract above).  SurfaceTracerFlux [>= NTracers][NCellsSize]; NormalStressEdge [NEdgesSize];
+   /// TangentialVelocity [NEdgesSize][levelPitch].  An empty array (Ptr == nullptr) is an absent one.
+   void applyTracerVertMix(const Array2DReal &LayerThickness, const Array3DReal &Tracers, int NTracers, Real Dt,
+                           const Array2DReal &SurfaceTracerFlux, hipStream_t S);
+   void applyVelocityVertMix(const Array2DReal &LayerThickness, const Array2DReal &NormalVelocity, Real Dt,
+                             const VertMixBoundary &Boundary, const Array1DReal &NormalStressEdge,
+                             const Array2DReal &TangentialVelocity, hipStream_t S);
+   /// Refuses (OmegaError) a negative coefficient
+   static void requireBoundary(const VertMixBoundary &Boundary);
 
    // ---- the reference's style of signature: on this object's `Stream` (default: the null stream)
    hipStream_t Stream = nullptr;

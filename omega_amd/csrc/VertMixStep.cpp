@@ -1,0 +1,63 @@
+// VertMixStep.cpp -- see VertMixStep.h.
+#include "VertMixStep.h"
+#include "HorzOperators.h"
+#include "Pacer.h"
+
+namespace OMEGA {
+
+VertMixStep::VertMixStep(const std::string &Name_, const HorzMesh *Mesh_, VertMix *VMix_, VertCoord *VCoord_,
+                         Eos *EqState_, int NTracers_)
+    : NVertLayers(0), NTracers(NTracers_), Mesh(Mesh_), VMix(VMix_), VCoord(VCoord_), EqState(EqState_), Name(Name_) {
+   OMEGA_REQUIRE(Mesh != nullptr, "VertMixStep: mesh is NULL");
+   OMEGA_REQUIRE(NTracers >= 2, "VertMixStep: NTracers = " + std::to_string(NTracers) +
+                                    " is below 2: the column pass needs temperature (0) and salinity (1)");
+   OMEGA_REQUIRE(!Mesh->HostOnly,
+                 "VertMixStep: the mesh was created host-only: no device arrays, compute is unavailable");
+   OMEGA_REQUIRE(VMix != nullptr, "VertMixStep: VertMix is NULL");
+   OMEGA_REQUIRE(VCoord != nullptr, "VertMixStep: VertCoord is NULL");
+   OMEGA_REQUIRE(EqState != nullptr, "VertMixStep: Eos is NULL");
+   OMEGA_REQUIRE(VMix->Mesh == Mesh && VMix->VCoord == VCoord && VCoord->Mesh == Mesh && EqState->Mesh == Mesh,
+                 "VertMixStep: the VertMix, VertCoord or Eos was built for another mesh");
+   OMEGA_REQUIRE(VMix->NVertLayers == VCoord->NVertLayers && EqState->NVertLayers == VCoord->NVertLayers,
+                 "VertMixStep: the VertMix, VertCoord and Eos have different layer counts");
+   NVertLayers = VCoord->NVertLayers;
+   OMEGA_REQUIRE(NVertLayers <= MaxLayers, "VertMixStep: NVertLayers = " + std::to_string(NVertLayers) +
+                                               " is above the fused column pass's limit of " +
+                                               std::to_string(MaxLayers));
+   TangentialVelocity    = Array2DReal::levels("TangentialVelocity", Mesh->NEdgesSize, NVertLayers);
+   NormalStressEdge      = Array1DReal("NormalStressEdge", Mesh->NEdgesSize);
+   SurfaceTracerFlux     = Array2DReal("SurfaceTracerFlux", NTracers, Mesh->NCellsSize);
+   SurfacePressure       = Array1DReal("SurfacePressure", Mesh->NCellsSize);
+   TidalPotential        = Array1DReal("TidalPotential", Mesh->NCellsSize);
+   SelfAttractionLoading = Array1DReal("SelfAttractionLoading", Mesh->NCellsSize);
+}
+
+void VertMixStep::apply(const Array2DReal &H, const Array2DReal &U, const Array3DReal &Tr, Real Dt, hipStream_t S) {
+   requireLevelArray("VertMixStep", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
+   requireLevelArray("VertMixStep", U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
+   requireLevelArray("VertMixStep", Tr, NTracers, Mesh->NCellsSize, NVertLayers, "Tracers", "NCellsSize");
+   VertMix::requireBoundary(Boundary);
+   Pacer::Range Timer("VertMixStep:apply", 1);
+   VCoord->computeColumn(H, Tr, *EqState, SurfacePressure, TidalPotential, SelfAttractionLoading, true, 1, S);
+   VMix->computeBruntVaisalaFreqSq(*EqState, S);
+   const TangentialReconOnEdge TangentialRecon(Mesh);
+   TangentialRecon(TangentialVelocity, U, S);
+   VMix->computeVertMix(U, TangentialVelocity, VMix->BruntVaisalaFreqSq, S);
+   VMix->applyTracerVertMix(H, Tr, NTracers, Dt, SurfaceTracerFlux, S);
+   VMix->applyVelocityVertMix(H, U, Dt, Boundary, UseWindStress ? NormalStressEdge : Array1DReal(), TangentialVelocity,
+                              S);
+}
+
+void VertMixStep::apply(const OceanState *State, int Level, const TracerStore *Tracers, int TrLevel, Real Dt,
+                        hipStream_t S) {
+   OMEGA_REQUIRE(State != nullptr && Tracers != nullptr, "VertMixStep::apply: state or tracers is NULL");
+   OMEGA_REQUIRE(Tracers->NTracers == NTracers, "VertMixStep::apply: the tracer store has another tracer count");
+   Array2DReal H, U;
+   OMEGA_REQUIRE(State->getLayerThickness(H, Level) == 0 && State->getNormalVelocity(U, Level) == 0,
+                 "VertMixStep::apply: bad time level");
+   Array3DReal Tr;
+   OMEGA_REQUIRE(Tracers->getAll(Tr, TrLevel) == 0, "VertMixStep::apply: bad tracer time level");
+   apply(H, U, Tr, Dt, S);
+}
+
+} // namespace OMEGA

@@ -1,0 +1,74 @@
+// VertMixStep.h -- the whole vertical-mixing sequence of one time step as one call: the displaced column pass, N^2, the
+// tangential velocity, the mixing coefficients, and the forced implicit solves of the tracers and the normal velocity
+// (VertMix.h), in the order a host would otherwise have to issue them after every step.  TimeStepper::attachVertMix
+// makes the three schemes call it on the new time level at the end of a step.
+//
+// apply(LayerThickness, NormalVelocity, Tracers, Dt, S) runs on S, in this order:
+//   1. VCoord->computeColumn(h, Tracers, Eos, SurfacePressure, TidalPotential, SelfAttractionLoading,
+//      Displaced = true, KDisp = 1, S)                    (temperature at tracer index 0, salinity at 1)
+//   2. VMix->computeBruntVaisalaFreqSq(Eos, S)
+//   3. TangentialReconOnEdge: NormalVelocity -> TangentialVelocity (every edge < NEdgesAll)
+//   4. VMix->computeVertMix(NormalVelocity, TangentialVelocity, VMix->BruntVaisalaFreqSq, S)
+//   5. VMix->applyTracerVertMix(h, Tracers, NTracers, Dt, SurfaceTracerFlux, S)
+//   6. VMix->applyVelocityVertMix(h, u, Dt, Boundary, NormalStressEdge if UseWindStress, TangentialVelocity, S)
+// The result equals these six public calls made by hand, bit for bit.  Step 6 takes the bottom speed from the velocity
+// before the solve and the tangential velocity of step 3.
+//
+// One rank only as a stepper hook: the shear of step 4 and the tangential velocity read halo edges, so mixing inside a
+// multi-rank step needs the halo of the new level before the sequence and again after the solves; that path is not
+// built and TimeStepper::attachVertMix refuses a halo with neighbours.  A host that exchanges the halo itself may
+// still call apply() on every rank.
+#ifndef OMEGA_AMD_VERTMIXSTEP_H
+#define OMEGA_AMD_VERTMIXSTEP_H
+
+#include "Base.h"
+#include "Eos.h"
+#include "HorzMesh.h"
+#include "OceanState.h"
+#include "VertCoord.h"
+#include "VertMix.h"
+
+namespace OMEGA {
+
+class VertMixStep : public Registry<VertMixStep> {
+ public:
+   /// The largest layer count of the fused column pass with the displaced volume (the LDS tile)
+   static constexpr int MaxLayers = 1008;
+
+   /// Refuses (OmegaError) a null or host-only mesh, a null VertMix / VertCoord / Eos or one of another mesh or layer
+   /// count, NTracers < 2 (temperature and salinity) and more than MaxLayers layers.  Everything is allocated here;
+   /// no call allocates.
+   VertMixStep(const std::string &Name, const HorzMesh *Mesh, VertMix *VMix, VertCoord *VCoord, Eos *EqState,
+               int NTracers);
+
+   I4 NVertLayers;
+   I4 NTracers;
+   /// Zero at construction; the caller's to overwrite
+   Array2DReal TangentialVelocity;                                      ///< [NEdgesSize][levelPitch]: rewritten by apply
+   Array1DReal NormalStressEdge;                                        ///< [NEdgesSize], Pa
+   Array2DReal SurfaceTracerFlux;                                       ///< [NTracers][NCellsSize]
+   Array1DReal SurfacePressure, TidalPotential, SelfAttractionLoading; ///< [NCellsSize]: the column pass's forcing
+
+   VertMixBoundary Boundary;
+   bool UseWindStress = false; ///< pass NormalStressEdge to the velocity solve
+
+   void apply(const Array2DReal &LayerThickness, const Array2DReal &NormalVelocity, const Array3DReal &Tracers, Real Dt,
+              hipStream_t S);
+   /// thickness and normal velocity of State at time level Level, the tracers of Tracers at TrLevel
+   void apply(const OceanState *State, int Level, const TracerStore *Tracers, int TrLevel, Real Dt, hipStream_t S);
+
+   // ---- the reference's style of signature: on this object's `Stream` (default: the null stream)
+   hipStream_t Stream = nullptr;
+   void apply(const Array2DReal &LayerThickness, const Array2DReal &NormalVelocity, const Array3DReal &Tracers, Real Dt) {
+      apply(LayerThickness, NormalVelocity, Tracers, Dt, Stream);
+   }
+
+   const HorzMesh *Mesh;
+   VertMix *VMix;
+   VertCoord *VCoord;
+   Eos *EqState;
+   std::string Name;
+};
+
+} // namespace OMEGA
+#endif

@@ -23,6 +23,7 @@
 #include "VertMix.h"
 #include "PressureGrad.h"
 #include "VertAdv.h"
+#include "VertMixStep.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -73,6 +74,9 @@ struct omg_eos {
 };
 struct omg_vertmix {
    std::unique_ptr<VertMix> X;
+};
+struct omg_vertmix_step {
+   std::unique_ptr<VertMixStep> M;
 };
 struct omg_pgrad {
    std::unique_ptr<PressureGrad> P;
@@ -1615,6 +1619,40 @@ int omg_vertmix_apply_velocity(omg_vertmix *x, const double *layer_thickness, do
                               dt, (hipStream_t)stream);
    OMG_CATCH
 }
+/// a raw device array [ntracers][rows] of the caller's (NULL: empty, an absent array)
+static Array2DReal fluxView(const double *Dev, int NTracers, int Rows) {
+   Array2DReal A;
+   A.Ptr    = const_cast<Real *>(Dev);
+   A.Ext[0] = Dev ? NTracers : 0, A.Ext[1] = Dev ? Rows : 0;
+   A.Pitch  = Rows;
+   return A;
+}
+int omg_vertmix_apply_tracers_forced(omg_vertmix *x, const double *layer_thickness, double *tracers, int ntracers,
+                                     double dt, const double *surface_flux, void *stream) {
+   OMG_TRY
+   OMG_ARG(x && layer_thickness && ntracers >= 0 && (tracers || ntracers == 0));
+   const HorzMesh *M = x->X->Mesh;
+   const int K       = x->X->NVertLayers;
+   x->X->applyTracerVertMix(levelView(layer_thickness, M->NCellsSize, K), tracerView(tracers, ntracers, M->NCellsSize, K),
+                            ntracers, dt, fluxView(surface_flux, ntracers, M->NCellsSize), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertmix_apply_velocity_forced(omg_vertmix *x, const double *layer_thickness, double *normal_velocity, double dt,
+                                      double bottom_drag_coeff, double rayleigh_drag_coeff, const double *normal_stress,
+                                      const double *tangential_velocity, void *stream) {
+   OMG_TRY
+   VertMixBoundary B;
+   B.BottomDragCoeff = bottom_drag_coeff, B.RayleighDragCoeff = rayleigh_drag_coeff;
+   VertMix::requireBoundary(B); // the coefficients first: they need no object to be judged
+   OMG_ARG(x && layer_thickness && normal_velocity);
+   const HorzMesh *M = x->X->Mesh;
+   const int K       = x->X->NVertLayers;
+   x->X->applyVelocityVertMix(levelView(layer_thickness, M->NCellsSize, K), levelView(normal_velocity, M->NEdgesSize, K),
+                              dt, B, cellView(normal_stress, M->NEdgesSize),
+                              tangential_velocity ? levelView(tangential_velocity, M->NEdgesSize, K) : Array2DReal(),
+                              (hipStream_t)stream);
+   OMG_CATCH
+}
 static ArrRef vertMixLookup(const VertMix &X, const char *Name) {
    return findNamed<ArrRef>({{"VertDiff", arrRef(X.VertDiff)},
                              {"VertVisc", arrRef(X.VertVisc)},
@@ -1623,6 +1661,67 @@ static ArrRef vertMixLookup(const VertMix &X, const char *Name) {
 }
 OMG_NAMED_ARRAYS(omg_vertmix_copy_to_host, omg_vertmix_copy_to_device, omg_vertmix_device_ptr, omg_vertmix, x,
                  vertMixLookup(*x->X, name))
+
+// ---- VertMixStep (VertMixStep.h)
+int omg_vertmix_step_create(const omg_mesh *m, omg_vertmix *x, omg_vcoord *v, omg_eos *e, int ntracers,
+                            omg_vertmix_step **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   newHandle(out, [&](omg_vertmix_step &R) {
+      R.M.reset(new VertMixStep("Default", m->M.get(), x ? x->X.get() : nullptr, v ? v->V.get() : nullptr,
+                                e ? e->E.get() : nullptr, ntracers));
+   });
+   OMG_CATCH
+}
+int omg_vertmix_step_destroy(omg_vertmix_step *ms) {
+   delete ms;
+   return 0;
+}
+int omg_vertmix_step_set_boundary(omg_vertmix_step *ms, double bottom_drag_coeff, double rayleigh_drag_coeff,
+                                  int use_wind_stress) {
+   OMG_TRY
+   OMG_ARG(ms);
+   VertMixBoundary B;
+   B.BottomDragCoeff = bottom_drag_coeff, B.RayleighDragCoeff = rayleigh_drag_coeff;
+   VertMix::requireBoundary(B);
+   ms->M->Boundary      = B;
+   ms->M->UseWindStress = use_wind_stress != 0;
+   OMG_CATCH
+}
+int omg_vertmix_step_apply(omg_vertmix_step *ms, const double *layer_thickness, double *normal_velocity, double *tracers,
+                           double dt, void *stream) {
+   OMG_TRY
+   OMG_ARG(ms && layer_thickness && normal_velocity && tracers);
+   const HorzMesh *M = ms->M->Mesh;
+   const int K       = ms->M->NVertLayers;
+   ms->M->apply(levelView(layer_thickness, M->NCellsSize, K), levelView(normal_velocity, M->NEdgesSize, K),
+                tracerView(tracers, ms->M->NTracers, M->NCellsSize, K), dt, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vertmix_step_apply_state(omg_vertmix_step *ms, const omg_state *s, int time_level, const omg_tracers *t,
+                                 int tracer_time_level, double dt, void *stream) {
+   OMG_TRY
+   OMG_ARG(ms && s && t);
+   ms->M->apply(s->S.get(), time_level, t->T.get(), tracer_time_level, dt, (hipStream_t)stream);
+   OMG_CATCH
+}
+static ArrRef vertMixStepLookup(const VertMixStep &M, const char *Name) {
+   return findNamed<ArrRef>({{"TangentialVelocity", arrRef(M.TangentialVelocity)},
+                             {"NormalStressEdge", arrRef(M.NormalStressEdge)},
+                             {"SurfaceTracerFlux", arrRef(M.SurfaceTracerFlux)},
+                             {"SurfacePressure", arrRef(M.SurfacePressure)},
+                             {"TidalPotential", arrRef(M.TidalPotential)},
+                             {"SelfAttractionLoading", arrRef(M.SelfAttractionLoading)}},
+                            Name, "VertMixStep: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_vertmix_step_copy_to_host, omg_vertmix_step_copy_to_device, omg_vertmix_step_device_ptr,
+                 omg_vertmix_step, ms, vertMixStepLookup(*ms->M, name))
+int omg_stepper_attach_vert_mix(omg_stepper *st, omg_vertmix_step *ms) {
+   OMG_TRY
+   OMG_ARG(st);
+   st->St->attachVertMix(ms ? ms->M.get() : nullptr);
+   OMG_CATCH
+}
 
 // ---- PressureGrad (PressureGrad.h)
 int omg_pgrad_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, omg_pgrad **out) {

@@ -40,5 +40,24 @@ void launchVelocityVertMix(int NEdgesOwned, int K, const I4 *CellsOnEdge, const 
                            const I4 *MaxLayerEdgeTop, const Real *H, const Real *VertVisc, Real *U, Real Dt,
                            hipStream_t S);
 
+/// launchTracerVertMix with a surface flux (VertMix.h, the forced tracer solve): row 0 of tracer L of column c takes
+/// Dt * SurfaceFlux[L * FluxStride + c] on its right-hand side.  SurfaceFlux == nullptr: no term (the unforced bits).
+void launchTracerVertMixForced(int NCellsOwned, int K, const I4 *MinLayer, const I4 *MaxLayer, const Real *H,
+                               const Real *VertDiff, Real *Tracers, int NTracers, int TrRows, Real Dt,
+                               const Real *SurfaceFlux, size_t FluxStride, hipStream_t S);
+
+/// The boundary terms of one forced velocity solve (VertMix.h).  A zero coefficient or a null array skips its term.
+struct VelocityForcingArgs {
+   Real DtBottomDrag = 0, DtRayleigh = 0; ///< Dt * BottomDragCoeff, Dt * RayleighDragCoeff
+   Real Rho0         = 1;
+   const Real *Stress = nullptr, *EdgeMask = nullptr; ///< [edge]: NormalStressEdge (Pa), EdgeMask
+   const Real *Ut     = nullptr;                      ///< [edge][Pitch]: read at the bottom row if DtBottomDrag != 0
+};
+/// launchVelocityVertMix with wind stress on the top row, linearised quadratic drag on the bottom row and Rayleigh drag
+/// on every row (VertMix.h, the forced velocity solve)
+void launchVelocityVertMixForced(int NEdgesOwned, int K, const I4 *CellsOnEdge, const I4 *MinLayerEdgeBot,
+                                 const I4 *MaxLayerEdgeTop, const Real *H, const Real *VertVisc, Real *U, Real Dt,
+                                 const VelocityForcingArgs &F, hipStream_t S);
+
 } // namespace OMEGA
 #endif

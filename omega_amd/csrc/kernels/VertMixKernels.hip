@@ -10,6 +10,9 @@
 // (kernels/TriDiagKernels.h): the G / H recursion, and with it every division except the last, is done once per
 // column instead of once per tracer.  Columns of one workgroup have different depths: the workgroup loops to the
 // largest level count among them and each lane stops updating after its own.
+//
+// The forced solves (VertMix.h) are further instantiations of the same kernel: the boundary terms change one diagonal
+// entry and one right-hand-side entry per column, read by the lane of row 0 or row N-1; nothing is added per level.
 #include "TriDiagKernels.h"
 #include "VertMixKernels.h"
 
@@ -106,9 +109,16 @@ struct MixArgs {
    int NRhs = 0;
    size_t RhsStride = 0;
    Real Dt = 0;
+   // ---- read by the Forced instantiations only
+   const Real *Flux = nullptr; ///< cells: [rhs][FluxStride] surface flux, or null
+   size_t FluxStride = 0;
+   VelocityForcingArgs F;      ///< edges
 };
 
-template <int Chunk, bool OnEdge>
+/// Forced: the boundary terms of VertMix.h's forced solves -- one lane per column each (row 0: the surface flux or
+/// the wind stress on X; row N-1: the bottom drag on the diagonal) and the Rayleigh drag on every row's diagonal.
+/// The diagonal goes to the solver where H stood; X = Hr * value keeps the thickness.
+template <int Chunk, bool OnEdge, bool Forced>
 __global__ void __launch_bounds__(TriDiagMaxRows) implicitMixKernel(MixArgs A, int SysPerBlock, int Rows) {
    extern __shared__ Real Lds[];
    __shared__ int NLevShared;
@@ -153,9 +163,51 @@ __global__ void __launch_bounds__(TriDiagMaxRows) implicitMixKernel(MixArgs A, i
    }
    Real *X        = A.X + (size_t)Col * A.Pitch + Lev;
    const size_t R = A.RhsStride;
-   pcrDiffSolveRowMulti<Chunk>(
-       Act, I, N, NLevWg, G, Hr, A.NRhs, [=](int Tr) { return Hr * X[Tr * R]; },
-       [=](int Tr, Real V) { X[Tr * R] = V; }, Lds + S * A.K, Rows);
+   if constexpr (!Forced) {
+      pcrDiffSolveRowMulti<Chunk>(
+          Act, I, N, NLevWg, G, Hr, A.NRhs, [=](int Tr) { return Hr * X[Tr * R]; },
+          [=](int Tr, Real V) { X[Tr * R] = V; }, Lds + S * A.K, Rows);
+   } else if constexpr (OnEdge) {
+      Real D = Hr, Top = 0;
+      bool HasTop = false;
+      if (Act) {
+         if (A.F.DtRayleigh != 0)
+            D = D + A.F.DtRayleigh * Hr;
+         if (I == N - 1 && A.F.DtBottomDrag != 0) {
+            const Real Ub = X[0], Vb = A.F.Ut[(size_t)Col * A.Pitch + Lev]; // u before the solve
+            D             = D + A.F.DtBottomDrag * sqrt((Ub * Ub) + (Vb * Vb));
+         }
+         if (I == 0 && A.F.Stress != nullptr) {
+            Top    = (A.Dt * A.F.EdgeMask[Col]) * (A.F.Stress[Col] / A.F.Rho0);
+            HasTop = true;
+         }
+      }
+      pcrDiffSolveRowMulti<Chunk>(
+          Act, I, N, NLevWg, G, D, A.NRhs,
+          [=](int Tr) {
+             const Real V = Hr * X[Tr * R];
+             return HasTop ? V + Top : V;
+          },
+          [=](int Tr, Real V) { X[Tr * R] = V; }, Lds + S * A.K, Rows);
+   } else {
+      // One lane per column (row 0) reads the flux, once per tracer.  The lane keeps the byte offset of its column in a
+      // flux row (NoFlux: no term), added to the uniform row address: one VGPR and no 64-bit address arithmetic.
+      constexpr unsigned NoFlux = ~0u;
+      const unsigned FluxOff    = (Act && I == 0 && A.Flux != nullptr) ? (unsigned)Col * (unsigned)sizeof(Real) : NoFlux;
+      const Real *const Flux    = A.Flux;
+      const unsigned Fs         = (unsigned)A.FluxStride; // a row of cells: 32 bits hold it
+      const Real Dt             = A.Dt;
+      pcrDiffSolveRowMulti<Chunk>(
+          Act, I, N, NLevWg, G, Hr, A.NRhs,
+          [=](int Tr) {
+             const Real V = Hr * X[Tr * R];
+             if (FluxOff == NoFlux)
+                return V;
+             const char *Row = reinterpret_cast<const char *>(Flux + (size_t)((unsigned)Tr * Fs));
+             return V + Dt * *reinterpret_cast<const Real *>(Row + FluxOff);
+          },
+          [=](int Tr, Real V) { X[Tr * R] = V; }, Lds + S * A.K, Rows);
+   }
 }
 
 /// Columns per workgroup and the lanes they occupy (as the PCR array launcher)
@@ -179,7 +231,7 @@ int mixChunk(int NRhs, int Rows) {
    return C;
 }
 
-template <bool OnEdge> void launchMix(const MixArgs &A, hipStream_t Str) {
+template <bool OnEdge, bool Forced> void launchMix(const MixArgs &A, hipStream_t Str) {
    OMEGA_REQUIRE(A.K >= 1 && A.K <= TriDiagMaxRows, "VertMix: NVertLayers = " + std::to_string(A.K) +
                                                         " is outside the supported 1 <= NVertLayers <= " +
                                                         std::to_string(TriDiagMaxRows));
@@ -190,11 +242,11 @@ template <bool OnEdge> void launchMix(const MixArgs &A, hipStream_t Str) {
    const dim3 Grid((A.NCols + P.Sys - 1) / P.Sys);
    const size_t Bytes = (size_t)(4 + 2 * Chunk) * P.Rows * sizeof(Real);
    switch (Chunk) {
-   case 1: hipLaunchKernelGGL((implicitMixKernel<1, OnEdge>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   case 2: hipLaunchKernelGGL((implicitMixKernel<2, OnEdge>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   case 4: hipLaunchKernelGGL((implicitMixKernel<4, OnEdge>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   case 6: hipLaunchKernelGGL((implicitMixKernel<6, OnEdge>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   default: hipLaunchKernelGGL((implicitMixKernel<8, OnEdge>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows);
+   case 1: hipLaunchKernelGGL((implicitMixKernel<1, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
+   case 2: hipLaunchKernelGGL((implicitMixKernel<2, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
+   case 4: hipLaunchKernelGGL((implicitMixKernel<4, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
+   case 6: hipLaunchKernelGGL((implicitMixKernel<6, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
+   default: hipLaunchKernelGGL((implicitMixKernel<8, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows);
    }
    HIP_CHECK(hipGetLastError());
 }
@@ -228,7 +280,7 @@ void launchTracerVertMix(int NCellsOwned, int K, const I4 *MinLayer, const I4 *M
    A.Lo = MinLayer, A.Hi = MaxLayer;
    A.H = H, A.Coef = VertDiff, A.X = Tracers;
    A.NRhs = NTracers, A.RhsStride = (size_t)TrRows * A.Pitch, A.Dt = Dt;
-   launchMix<false>(A, S);
+   launchMix<false, false>(A, S);
 }
 
 void launchVelocityVertMix(int NEdgesOwned, int K, const I4 *CellsOnEdge, const I4 *MinLayerEdgeBot,
@@ -239,7 +291,37 @@ void launchVelocityVertMix(int NEdgesOwned, int K, const I4 *CellsOnEdge, const 
    A.Lo = MinLayerEdgeBot, A.Hi = MaxLayerEdgeTop, A.CellsOnEdge = CellsOnEdge;
    A.H = H, A.Coef = VertVisc, A.X = U;
    A.NRhs = 1, A.RhsStride = 0, A.Dt = Dt;
-   launchMix<true>(A, S);
+   launchMix<true, false>(A, S);
+}
+
+void launchTracerVertMixForced(int NCellsOwned, int K, const I4 *MinLayer, const I4 *MaxLayer, const Real *H,
+                               const Real *VertDiff, Real *Tracers, int NTracers, int TrRows, Real Dt,
+                               const Real *SurfaceFlux, size_t FluxStride, hipStream_t S) {
+   MixArgs A;
+   A.NCols = NCellsOwned, A.K = K, A.Pitch = levelPitch(K);
+   A.Lo = MinLayer, A.Hi = MaxLayer;
+   A.H = H, A.Coef = VertDiff, A.X = Tracers;
+   A.NRhs = NTracers, A.RhsStride = (size_t)TrRows * A.Pitch, A.Dt = Dt;
+   // the kernel addresses a flux row with 32-bit offsets (values across the tracers, bytes within a row)
+   OMEGA_REQUIRE(SurfaceFlux == nullptr || ((size_t)NCellsOwned <= FluxStride && FluxStride <= 0x1FFFFFFFu &&
+                                            (size_t)NTracers * FluxStride <= 0xFFFFFFFFu),
+                 "VertMix: the surface flux array is too large for the forced tracer solve");
+   A.Flux = SurfaceFlux, A.FluxStride = FluxStride;
+   launchMix<false, true>(A, S);
+}
+
+void launchVelocityVertMixForced(int NEdgesOwned, int K, const I4 *CellsOnEdge, const I4 *MinLayerEdgeBot,
+                                 const I4 *MaxLayerEdgeTop, const Real *H, const Real *VertVisc, Real *U, Real Dt,
+                                 const VelocityForcingArgs &F, hipStream_t S) {
+   OMEGA_REQUIRE(F.DtBottomDrag == 0 || F.Ut != nullptr, "VertMix: bottom drag needs the tangential velocity");
+   OMEGA_REQUIRE(F.Stress == nullptr || F.EdgeMask != nullptr, "VertMix: a stress array needs the edge mask");
+   MixArgs A;
+   A.NCols = NEdgesOwned, A.K = K, A.Pitch = levelPitch(K);
+   A.Lo = MinLayerEdgeBot, A.Hi = MaxLayerEdgeTop, A.CellsOnEdge = CellsOnEdge;
+   A.H = H, A.Coef = VertVisc, A.X = U;
+   A.NRhs = 1, A.RhsStride = 0, A.Dt = Dt;
+   A.F = F;
+   launchMix<true, true>(A, S);
 }
 
 } // namespace OMEGA
