@@ -41,6 +41,7 @@ typedef struct omg_vertmix omg_vertmix; /* O/doc/design/VerticalMixingCoeff.md (
 typedef struct omg_pgrad omg_pgrad;     /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
 typedef struct omg_vertmix_step omg_vertmix_step; /* O/doc/design/OmegaV1GoverningEqns.md section 11 (design only) */
 typedef struct omg_vertadv omg_vertadv; /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
+typedef struct omg_btr omg_btr;         /* O/doc/design/TimeStepping.md, OmegaV1GoverningEqns.md section 1 (design only) */
 
 enum { OMG_ON_CELL = 0, OMG_ON_EDGE = 1, OMG_ON_VERTEX = 2 }; /* O/src/base/Halo.h:45 MeshElement */
 
@@ -656,6 +657,35 @@ int omg_vertadv_copy_to_host(const omg_vertadv *a, const char *name, double *hos
  * group calls use VerticalTransport as it stands; the Runge-Kutta stage updates run as separate kernels and nothing is
  * replayed as a graph.  Detach before destroying a. */
 int omg_tend_attach_vert_adv(omg_tend *t, omg_vertadv *a);
+
+/* ---- BarotropicMode: the vertical split of the edge velocity into its thickness-weighted mean and the baroclinic
+ * remainder, and forward-backward sub-cycling of the 2-D (SSH, barotropic velocity) system (O/doc/design/
+ * TimeStepping.md names the scheme, OmegaV1GoverningEqns.md section 1 the split step; the reference has no code for
+ * them).  Numerical contract: omega_amd/csrc/BarotropicMode.h.  Arrays are level-indexed device arrays as above.  Every
+ * call is asynchronous on stream and allocates nothing.  The object keeps a pointer to v: destroy it before v. ---- */
+/* gravity: 9.80616 is VertCoord's.  Fails for a host-only mesh, a VertCoord that is NULL or of another mesh or layer
+ * count, and more layers than omg_btr_max_layers */
+int omg_btr_create(const omg_mesh *m, const omg_vcoord *v, double gravity, omg_btr **out);
+int omg_btr_destroy(omg_btr *b);
+int omg_btr_max_layers(int *n);
+/* BtrThickEdge, BtrVelocity, BclVelocity from layer_thickness_dev [NCellsSize][pitch] and normal_velocity_dev
+ * [NEdgesSize][pitch]; with_ssh != 0 also runs omg_btr_compute_ssh in the same launch */
+int omg_btr_split_velocity(omg_btr *b, const double *layer_thickness_dev, const double *normal_velocity_dev, int with_ssh,
+                           void *stream);
+/* BtrForcing: the thickness-weighted vertical mean of velocity_tend_dev [NEdgesSize][pitch] */
+int omg_btr_compute_forcing(omg_btr *b, const double *layer_thickness_dev, const double *velocity_tend_dev, void *stream);
+/* SSH = column sum of layer_thickness_dev - BottomDepth (the VertCoord's) */
+int omg_btr_compute_ssh(omg_btr *b, const double *layer_thickness_dev, void *stream);
+/* normal_velocity_dev [NEdgesSize][pitch] = BclVelocity + BtrVelocity on each edge's level range */
+int omg_btr_recombine(omg_btr *b, double *normal_velocity_dev, void *stream);
+/* nsub forward-backward sub-steps of dt_btr seconds on SSH and BtrVelocity under BtrForcing; BtrFluxMean is the mean
+ * edge flux of the sub-steps.  Fails for nsub < 1 and a dt_btr that is not finite and positive */
+int omg_btr_subcycle(omg_btr *b, int nsub, double dt_btr, void *stream);
+/* "BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean" ([NEdgesSize]), "SSH" ([NCellsSize]), "BclVelocity"
+ * ([NEdgesSize][NVertLayers]); all zero at creation */
+int omg_btr_device_ptr(const omg_btr *b, const char *name, double **dev, size_t *n);
+int omg_btr_copy_to_device(omg_btr *b, const char *name, const double *host, size_t n);
+int omg_btr_copy_to_host(const omg_btr *b, const char *name, double *host, size_t n);
 
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at

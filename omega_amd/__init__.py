@@ -1305,6 +1305,68 @@ class VertAdv(_Handle, _NamedArrays):
         return (self.mesh.NCellsSize, self.K)
 
 
+BTR_ARRAYS = {"BtrVelocity": "E", "BtrThickEdge": "E", "BtrForcing": "E", "BtrFluxMean": "E", "SSH": "C",
+              "BclVelocity": "EK"}
+
+
+class BarotropicMode(_Handle, _NamedArrays):
+    """BarotropicMode (omega_amd/csrc/BarotropicMode.h): the split of the edge velocity into its thickness-weighted
+    vertical mean (BtrVelocity) and the baroclinic remainder (BclVelocity), the sea-surface height of the columns, and
+    forward-backward sub-cycling of the 2-D (SSH, BtrVelocity) system under BtrForcing.  Level-indexed inputs are numpy
+    arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles; every call is one library call,
+    asynchronous on `stream` when it is given device addresses."""
+    _destroy, _arrays = "omg_btr_destroy", "omg_btr"
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", gravity: float = 9.80616):
+        self.mesh, self.vcoord, self.gravity = mesh, vcoord, float(gravity)
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self._create("omg_btr_create", mesh.h, vcoord.h if vcoord is not None else None, C.c_double(gravity))
+
+    @staticmethod
+    def max_layers() -> int:
+        n = C.c_int()
+        _chk(lib().omg_btr_max_layers(C.byref(n)))
+        return n.value
+
+    def _edge_call(self, symbol, layer_thickness, edge_field, *args, stream=None):
+        keep = []
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        u = _level_dev(edge_field, self.mesh.NEdgesSize, self.K, keep)
+        _chk(getattr(lib(), symbol)(self.h, h, u, *args, _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def split_velocity(self, layer_thickness, normal_velocity, with_ssh: bool = False, stream=None):
+        """BtrThickEdge, BtrVelocity and BclVelocity; with_ssh: also compute_ssh, in the same launch"""
+        self._edge_call("omg_btr_split_velocity", layer_thickness, normal_velocity, int(bool(with_ssh)), stream=stream)
+
+    def compute_forcing(self, layer_thickness, velocity_tend, stream=None):
+        self._edge_call("omg_btr_compute_forcing", layer_thickness, velocity_tend, stream=stream)
+
+    def compute_ssh(self, layer_thickness, stream=None):
+        keep = []
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        _chk(lib().omg_btr_compute_ssh(self.h, h, _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def recombine(self, normal_velocity, stream=None):
+        """normal_velocity = BclVelocity + BtrVelocity on each edge's level range, in place: a device address, or a
+        numpy array (staged, computed, returned)"""
+        p, buf = _stage_levels(normal_velocity, (self.mesh.NEdgesSize,), self.K)
+        _chk(lib().omg_btr_recombine(self.h, p, _sh(stream)))
+        return _read_back(buf, self.K, stream)
+
+    def subcycle(self, nsub: int, dt_btr: float, stream=None):
+        _chk(lib().omg_btr_subcycle(self.h, int(nsub), C.c_double(dt_btr), _sh(stream)))
+
+    def _shape(self, name):
+        s = BTR_ARRAYS.get(name, "E")  # (an unknown name: the library says so)
+        if s == "C":
+            return (self.mesh.NCellsSize,)
+        return (self.mesh.NEdgesSize, self.K) if s == "EK" else (self.mesh.NEdgesSize,)
+
+
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""

@@ -24,6 +24,7 @@
 #include "PressureGrad.h"
 #include "VertAdv.h"
 #include "VertMixStep.h"
+#include "BarotropicMode.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -83,6 +84,9 @@ struct omg_pgrad {
 };
 struct omg_vertadv {
    std::unique_ptr<VertAdv> A;
+};
+struct omg_btr {
+   std::unique_ptr<BarotropicMode> B;
 };
 
 static thread_local std::string LastError;
@@ -1844,6 +1848,76 @@ int omg_tend_attach_vert_adv(omg_tend *t, omg_vertadv *a) {
    t->T->attachVertAdv(a ? a->A.get() : nullptr);
    OMG_CATCH
 }
+
+// ---- BarotropicMode (BarotropicMode.h)
+int omg_btr_create(const omg_mesh *m, const omg_vcoord *v, double gravity, omg_btr **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   BarotropicConfig Cfg;
+   Cfg.Gravity = gravity;
+   newHandle(out, [&](omg_btr &R) { R.B.reset(new BarotropicMode("Default", m->M.get(), v ? v->V.get() : nullptr, Cfg)); });
+   OMG_CATCH
+}
+int omg_btr_destroy(omg_btr *b) {
+   delete b;
+   return 0;
+}
+int omg_btr_max_layers(int *n) {
+   OMG_TRY
+   OMG_ARG(n);
+   *n = BarotropicMode::maxLayers();
+   OMG_CATCH
+}
+int omg_btr_split_velocity(omg_btr *b, const double *layer_thickness, const double *normal_velocity, int with_ssh,
+                           void *stream) {
+   OMG_TRY
+   OMG_ARG(b && layer_thickness && normal_velocity);
+   const HorzMesh *M = b->B->Mesh;
+   const int K       = b->B->NVertLayers;
+   const Array2DReal H = levelView(layer_thickness, M->NCellsSize, K), U = levelView(normal_velocity, M->NEdgesSize, K);
+   if (with_ssh)
+      b->B->splitVelocityAndSSH(H, U, (hipStream_t)stream);
+   else
+      b->B->splitVelocity(H, U, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_btr_compute_forcing(omg_btr *b, const double *layer_thickness, const double *velocity_tend, void *stream) {
+   OMG_TRY
+   OMG_ARG(b && layer_thickness && velocity_tend);
+   const HorzMesh *M = b->B->Mesh;
+   const int K       = b->B->NVertLayers;
+   b->B->computeForcing(levelView(layer_thickness, M->NCellsSize, K), levelView(velocity_tend, M->NEdgesSize, K),
+                        (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_btr_compute_ssh(omg_btr *b, const double *layer_thickness, void *stream) {
+   OMG_TRY
+   OMG_ARG(b && layer_thickness);
+   b->B->computeSSH(levelView(layer_thickness, b->B->Mesh->NCellsSize, b->B->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_btr_recombine(omg_btr *b, double *normal_velocity, void *stream) {
+   OMG_TRY
+   OMG_ARG(b && normal_velocity);
+   b->B->recombine(levelView(normal_velocity, b->B->Mesh->NEdgesSize, b->B->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_btr_subcycle(omg_btr *b, int nsub, double dt_btr, void *stream) {
+   OMG_TRY
+   OMG_ARG(b);
+   b->B->subcycle(nsub, dt_btr, (hipStream_t)stream);
+   OMG_CATCH
+}
+static ArrRef btrLookup(const BarotropicMode &B, const char *Name) {
+   return findNamed<ArrRef>({{"BtrVelocity", arrRef(B.BtrVelocity)},
+                             {"BtrThickEdge", arrRef(B.BtrThickEdge)},
+                             {"BtrForcing", arrRef(B.BtrForcing)},
+                             {"BtrFluxMean", arrRef(B.BtrFluxMean)},
+                             {"SSH", arrRef(B.SSH)},
+                             {"BclVelocity", arrRef(B.BclVelocity)}},
+                            Name, "BarotropicMode: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_btr_copy_to_host, omg_btr_copy_to_device, omg_btr_device_ptr, omg_btr, b, btrLookup(*b->B, name))
 
 // ---- batched tridiagonal solvers (TriDiagSolvers.h)
 /// a caller's [nbatch][nrow] device array of row pitch row_pitch (0: nrow) as the solvers' Array2DReal
