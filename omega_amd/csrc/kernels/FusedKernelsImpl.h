@@ -1,7 +1,7 @@
 // FusedKernelsImpl.h -- the bodies of the fused right-hand side and the template that launches them (launchFusedT).
 // Included by FusedKernels.hip (the dispatcher, which only DECLARES the instantiations it calls: `extern template`) and by
-// the FusedInst*.hip translation units, each of which instantiates a few of them -- so that the 17 instantiations of a
-// 600-line launcher over ~2000 lines of kernel bodies compile in parallel (as one translation unit: 4-5 minutes).
+// the FusedInst*.hip translation units, each of which instantiates a few of them -- so that the 17 instantiations of the
+// launcher over ~2000 lines of kernel bodies compile in parallel (as one translation unit: 4-5 minutes).
 #ifndef OMEGA_AMD_FUSEDKERNELSIMPL_H
 #define OMEGA_AMD_FUSEDKERNELSIMPL_H
 // Tendencies::computeAllTendencies as a fused RHS (the text below describes the dependency levels; DESIGN.md section 4 the current bodies).
@@ -27,7 +27,6 @@
 #include "../Pacer.h"
 
 #include <cstdlib>
-#include <functional>
 #include <type_traits>
 
 // tuning knobs of the tracer cell kernels (VGPR budget / levels per thread)
@@ -2167,31 +2166,90 @@ static inline bool isDefaultTermSet(const TendParams &P) {
           P.TracerHyperDiffTendencyEnable && !P.FluxThicknessUpwind && !P.FluxTracerUpwind;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The launcher.  launchFusedT builds a context (FusedCtx: the one place each body's aggregate is written) and the
+// decisions (FusedPlan), then runs the levels one after the other.  Which structure a mesh / stage takes, and the test
+// that drives it (options: Tuning.h):
+//
+//   structure                                   selected by                                          driven by
+//   ------------------------------------------  ---------------------------------------------------  ------------------------------
+//   L1 merged (FusedCellL1PVBody)               CellPVOK, CellL1OK, PV term on, MergeL1 = 1           test_gpu_parity (every mesh)
+//   L1 as three kernels                         any of those off; 8-wide tables, non-default terms   multirank child MergeL1=0,Pair=0;
+//                                                                                                    child KeepMaxEdges=1
+//   L1/L2/L3 wide-cell lists (TW-slot bodies)   narrow view (HW): NWideCells > 0                     fib1500 cases; child NarrowTables=0
+//                                                                                                    for the one-table form
+//   L1/L2 bad-cell lists (generic bodies)       NBadCells > 0                                        the *_perm* cases
+//   L2 paired (ring cell + vertex, one launch)  Del2RingOK, Del2VertOK, del4 on, Pair = 1            test_gpu_parity (every mesh)
+//   L2 one launch each / generic bodies         a flag off, Pair = 0                                 child ForceGeneric=1; Pair=0
+//   L3 side-0 / final lists of rarer valences   NRingCellsM1 / M2 > 0 (pentagons, ...)               ico3, ico4, ico3pad8, fib1500
+//   L3 plain RHS, one thread (FuseL3)           Fast, CellPVFinalOK, NT > 0, no stage, Pair = 1      test_gpu_parity, TracerPatch 1 / 0:
+//      + lists folded into the sweep (FoldL3)     wide cells or other-valence cells                    test_both_forms_of_the_level3_...
+//      + irregular edges folded (FoldChain)       one table width, NIrregularEdges > 0               the coast cases, test_coast.py
+//   L3 stage pair (CellPVFinalBody+Cell3)       the same with a stage                                 RK4 cases with fused stages
+//      band / interior split, AfterBand           Stage->AfterBand, NBandCells > 0                   test_00_multirank_gpu: overlapped,
+//      send band, shrunk sweeps                   SendBand, ShrinkSweeps, BandOnComm                 send-band, shrunk-sweep cases
+//   L3 unpaired (final sweep, then tracers)     NT = 0, Pair = 0, CellPVFinalOK off                   NT = 0 cases; child Pair=0
+//   L3 side 1 + EdgeFinalBody                   cell-centric, not Fast (or CellPVFinalOK off)         the non-default term sets
+//   L3 irregular-edge list (chain, INV)         NIrregularEdges > 0, not folded                      coast cases in stages; child
+//                                                                                                    KeepMaxEdges=1 (ico3pad8)
+//   L3 edge-centric chain / FusedEdgeBody       CellPVOK off: PVChainOK / neither                    child ForceGeneric=1
+// ---------------------------------------------------------------------------------------------------------------
+
+/// The compile-time shape of an instantiation of the launcher.
 /// ND = the valence the full sweeps of the cell-centric PV kernels are instantiated for: TME, or TME-1 when most
 /// cells have one edge fewer than the widest (hexagons with a few heptagons).  NA = the other of the two; cells of
 /// valence NA and TME-2 go through list launches.
 /// HW: M is the NARROW view of a mesh with wider cells (*Wide the full-width one); without, the cell bodies of the sweeps
 /// carry neither list selects nor width tests (FL above).
-template <int TME, bool Fast, int ND = TME, bool HW = false>
-void launchFusedT(const MeshView &M, int K, int NT, const TendParams &P, const AuxPtrs &A, Real *HTend,
-                         Real *UTend, Real *TrTend, const Real *H, const Real *U, const Real *Tr, hipStream_t S,
-                         hipEvent_t *Ev, Real *EdgeScratch, const StageUpdate *Stage, const MeshView *Wide = nullptr) {
+template <int TME, int ND, bool HW> struct FusedShape {
    // Wide != nullptr: M is the mesh's NARROW view (cell tables TME wide) and *Wide the full-width one; the cells with
    // TW = TME+1 edges (Wide->WideCells: the heptagons of a hexagon mesh) are skipped by every sweep over M and run
    // through list launches of the TW-slot bodies on *Wide, level by level.
-   constexpr int TW       = TME < 8 ? TME + 1 : TME;
-   constexpr bool CanWide = HW && ND == TME && TME < 8;
-   constexpr int FLS      = HW ? 2 : 0; // flags of a full sweep: no list; width test only next to wider cells
-   constexpr int FLL      = HW ? 3 : 1; // ... of a body that may also run over band / interior lists
-   const I4 NWide         = (CanWide && Wide) ? Wide->NWideCells : 0;
-   constexpr int NA     = ND == TME ? TME - 1 : TME;
-   const I4 NMain       = ND == TME ? M.NRingCellsM0 : M.NRingCellsM1; // cells of the sweeps' valence
-   const I4 NOther      = ND == TME ? M.NRingCellsM1 : M.NRingCellsM0; // cells of valence NA (list launches)
-   const I4 *OtherCells = ND == TME ? M.RingCellsM1 : M.RingCellsM0;
+   static constexpr int TW       = TME < 8 ? TME + 1 : TME;
+   static constexpr bool CanWide = HW && ND == TME && TME < 8;
+   static constexpr int FLS      = HW ? 2 : 0; // flags of a full sweep: no list; width test only next to wider cells
+   static constexpr int FLL      = HW ? 3 : 1; // ... of a body that may also run over band / interior lists
+   static constexpr int NA       = ND == TME ? TME - 1 : TME;
+   // the rarer valences (MaxEdges-1, MaxEdges-2: e.g. the pentagons of a mesh stored with
+   // maxEdges = 6 or 7) run the same ring code, instantiated for their size, over cell lists
+   static constexpr int NM1 = NA, NM2 = TME >= 6 ? TME - 2 : TME - 1; // (NM1: "the other big valence")
+};
+
+/// f(std::true_type{}) in a Runge-Kutta stage whose update is folded into the tendency-producing kernels (Fast term set
+/// only), f(std::false_type{}) otherwise; with Fast = false the stage form is not instantiated
+template <bool Fast, class F> inline void withEpi(const StageUpdate *Stage, F &&f) {
+   if constexpr (Fast) {
+      if (Stage) {
+         f(std::true_type{});
+         return;
+      }
+   }
+   f(std::false_type{});
+}
+
+/// What every body of one RHS evaluation is built from, and the one place each body's aggregate is written.
+/// The factories take the mesh view (M or *Wide) and the element list (nullptr: a full sweep); W is the table width.
+template <bool Fast> struct FusedCtx {
+   const MeshView &M;
+   const MeshView *Wide;
+   int K, NT;
+   const TendParams &P;
+   const AuxPtrs &A;
+   const Real *H, *U, *Tr;
+   Real *HTend, *UTend, *TrTend;
+   Real *EdgeScratch;
+   int DoDel2Tr;
+   hipStream_t S;
+   hipEvent_t *Ev;
+   const StageUpdate *Stage;
    // Runge-Kutta stage update folded into the tendency-producing kernels (Fast term set only;
    // launchFusedRHS has checked that this mesh takes the cell-centric PV path)
-   [[maybe_unused]] StageEpi EH, EU, ET;
-   if (Stage) {
+   StageEpi EH{}, EU{}, ET{};
+   bool BandForked = false;
+
+   void setStage() {
+      if (!Stage)
+         return;
       EH.CB = EU.CB = ET.CB = Stage->CB, EH.CA = EU.CA = ET.CA = Stage->CA;
       EH.First = EU.First = ET.First = Stage->First, EH.Last = EU.Last = ET.Last = Stage->Last;
       EH.StoreTend = EU.StoreTend = ET.StoreTend = Stage->StoreTend;
@@ -2200,32 +2258,13 @@ void launchFusedT(const MeshView &M, int K, int NT, const TendParams &P, const A
       ET.Next = Stage->NextTr, ET.Cur = Stage->CurTr, ET.Prov = Stage->ProvTr;
       ET.CurH = Stage->CurH, ET.ProvH = Stage->ProvH, ET.NextH = Stage->NextH;
    }
-   auto Mark = [&](int I) {
+   void mark(int I) const {
       if (Ev)
          (void)hipEventRecord(Ev[I], S);
-   };
-   // L1: replaces AuxState:vertexAuxState1, cellAuxState1, edgeAuxState1/2 (flux thickness), cellAuxState4 (Del2Tracers),
-   // Tend:thicknessFluxDiv and the cell-0 half of Tend:potientialVortHAdv
-   Pacer::start("Tend:fused:L1[AuxState:vertexAuxState1,cellAuxState1,edgeAuxState2,cellAuxState4;Tend:thicknessFluxDiv]", 2);
-   Mark(0);
-   // the vertex kernel stores RelVort and 1/LayerThickVertex; the two normalised vorticities are rebuilt from
-   // them where they are consumed; without the cell-centric tables the edge kernels read the reference's arrays
-   const TuningOptions &Tn = tuning();
-   // the band of an overlapped stage: without the halo cells whose results the exchange replaces (Kernels.h)
-   const bool SendOnly =
-       Tn.SendBand && Stage && Stage->AfterBand && Stage->HaloOutputsReplaced && !Stage->StoreTend && M.NBandSendCells > 0;
-   const I4 *const BandList = SendOnly ? M.BandSendCells : M.BandCells;
-   const int NBandList      = SendOnly ? M.NBandSendCells : M.NBandCells;
-   // sweep lengths of a stage (Kernels.h: StageUpdate::NCellsL1 / NCellsVel / NCellsTr)
-   auto SweepLen = [&](I4 Want) {
-      return (Tn.ShrinkSweeps && Stage && !Stage->StoreTend && Want > 0 && Want < M.NCellsAll) ? Want : M.NCellsAll;
-   };
-   const int NSweepL1 = SweepLen(Stage ? Stage->NCellsL1 : 0), NSweepVel = SweepLen(Stage ? Stage->NCellsVel : 0),
-             NSweepTr = SweepLen(Stage ? Stage->NCellsTr : 0);
-   // the stream of the band launches (Kernels.h: StageUpdate::BandStream); forked from S at the first use
-   bool BandForked = false;
-   auto BandS      = [&]() -> hipStream_t {
-      if (!(Stage && Stage->BandStream && Stage->BandReady && Tn.BandOnComm))
+   }
+   /// the stream of the band launches (Kernels.h: StageUpdate::BandStream); forked from S at the first use
+   hipStream_t bandStream() {
+      if (!(Stage && Stage->BandStream && Stage->BandReady && tuning().BandOnComm))
          return S;
       if (!BandForked) {
          HIP_CHECK(hipEventRecord(Stage->BandReady, S));
@@ -2233,558 +2272,487 @@ void launchFusedT(const MeshView &M, int K, int NT, const TendParams &P, const A
          BandForked = true;
       }
       return Stage->BandStream;
+   }
+   const MeshView &full() const { return Wide ? *Wide : M; } // (the mesh of the helper launches)
+
+   // ---- level 1
+   template <int W, bool EP> auto cell1(const MeshView &Mesh, const I4 *List) const {
+      return FusedCell1Body<W, Fast, EP>{Mesh, K, NT, P, DoDel2Tr, H, U, Tr, A.KineticEnergyCell, A.VelocityDivCell,
+                                         HTend, A.Del2TracersCell, EH, List};
+   }
+   template <int W, bool EP, int NR, bool INLO, int FL> auto cellL1PV(const MeshView &Mesh, const I4 *List) const {
+      return FusedCellL1PVBody<W, Fast, EP, NR, INLO, FL>{Mesh, K, NT, P, DoDel2Tr, H, U, Tr, A.KineticEnergyCell,
+                                                          A.VelocityDivCell, HTend, A.Del2TracersCell, A.RelVortVertex,
+                                                          A.InvThickVertex, EdgeScratch, EH, List};
+   }
+   // ---- level 2
+   template <int W, int FL> auto del2Ring(const MeshView &Mesh, const I4 *List) const {
+      return Del2CellRingBody<W, FL>{Mesh, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell, List};
+   }
+   auto del2Cell(const I4 *List) const {
+      return FusedDel2CellBody{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell, List};
+   }
+   auto del2VertexSel() const { return Del2VertexSelBody{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2RelVortVertex}; }
+   auto del2Vertex() const { return FusedDel2VertexBody{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2RelVortVertex}; }
+   // ---- level 3, cell-centric
+   template <int W, int Side, int NR> auto pvSide(const MeshView &Mesh, const I4 *List) const {
+      return CellPVBody<W, Fast, Side, NR>{Mesh, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch, List};
+   }
+   template <int W, int NR, bool EP> auto pvFinal(const MeshView &Mesh, const I4 *List) const {
+      return CellPVFinalBody<W, NR, EP>{Mesh, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch, A.RelVortVertex,
+                                        A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell, A.Del2RelVortVertex, UTend,
+                                        List, EU};
+   }
+   template <int W, int NR, int FL> auto pvFinalTracer(const MeshView &Mesh, const I4 *List) const {
+      return CellPVFinalTracerBody<W, NR, FL>{Mesh, K, NT, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
+                                              A.RelVortVertex, A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell,
+                                              A.Del2RelVortVertex, UTend, Tr, A.Del2TracersCell, TrTend, List};
+   }
+   /// the edge-centric chain over an edge list, vorticities rebuilt from RelVort and 1/LayerThickVertex (INV)
+   template <int W, bool EP> auto chain(const MeshView &Mesh, const I4 *List) const {
+      return FusedEdgeChainBody<W, Fast, EP, true>{Mesh, K, P, H, U, A.RelVortVertex, A.InvThickVertex, nullptr,
+                                                   A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell,
+                                                   A.Del2RelVortVertex, A.NormalStressEdge, UTend, List, EU};
+   }
+   template <int W, bool EP, int FL> auto cell3(const MeshView &Mesh, const I4 *List) const {
+      return FusedCell3Body<W, Fast, EP, FL>{Mesh, K, NT, P, H, U, Tr, A.Del2TracersCell, TrTend, ET, List};
+   }
+   auto edgeFinal() const {
+      return EdgeFinalBody<Fast>{M, K, P, H, U, EdgeScratch, A.RelVortVertex, A.KineticEnergyCell, A.VelocityDivCell,
+                                 A.Del2DivCell, A.Del2RelVortVertex, A.NormalStressEdge, UTend};
+   }
+   // ---- level 3, edge-centric fallbacks (they read the reference's normalised vorticities)
+   template <int W> auto chainAllEdges() const {
+      return FusedEdgeChainBody<W, Fast>{M, K, P, H, U, A.RelVortVertex, A.NormRelVortVertex, A.NormPlanetVortVertex,
+                                         A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell, A.Del2RelVortVertex,
+                                         A.NormalStressEdge, UTend, nullptr};
+   }
+   auto edgeGeneric() const {
+      return FusedEdgeBody{M, K, P, H, U, A.RelVortVertex, A.NormRelVortVertex, A.NormPlanetVortVertex,
+                           A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell, A.Del2RelVortVertex, A.NormalStressEdge,
+                           UTend};
+   }
+};
+
+/// The decisions of one RHS evaluation: pure functions of mesh, options and stage, computed once (planFused)
+struct FusedPlan {
+   I4 NWide;             // wide cells served by list launches on *Wide (0: one set of tables)
+   I4 NMain;             // cells of the sweeps' valence
+   I4 NOther;            // cells of valence NA (list launches)
+   const I4 *OtherCells; // ... their list
+   I4 NM2;               // cells of valence TME-2 (list launches over M.RingCellsM2)
+   bool SendOnly;        // the band of an overlapped stage: without the halo cells whose results the exchange replaces
+   const I4 *BandList;   // the band cells of an overlapped stage
+   int NBandList;
+   int NSweepL1, NSweepVel, NSweepTr; // sweep lengths of a stage (Kernels.h: StageUpdate::NCellsL1 / NCellsVel / NCellsTr)
+   bool HyperDiff;   // level 2 runs at all (only the del4 term consumes it)
+   bool PVOn;        // the PV term
+   bool CellCentric; // PV sums per cell into EdgeScratch; else the edge-centric fallbacks
+   bool MergeL1;     // vertex pass and side-0 PV sums inside the L1 cell kernel
+   bool InlineOther; // ... which also takes the side-0 sums of the cells with one edge fewer (INLO)
+   bool PairL2;      // level 2: cell and vertex sweep in one launch
+   bool PVFinal;     // level 3: side 1 and the velocity tendency in one cell kernel (CellPVFinalBody); else side 1 + EdgeFinalBody
+   bool Overlap;     // the full sweeps of level 3 are split into band and interior lists around Stage->AfterBand
+   bool PairL3;      // level 3: velocity and tracer sweep in one launch
+   bool FuseL3;      // ... in one thread (plain RHS)
+   bool FoldL3;      // ... with the wide cells' and the other valence's lists in the same launch
+   bool FoldChain;   // ... and the irregular-edge list
+   bool SplitTr;     // the tracer launches are split into band and interior, AfterBand between them
+   int NIrr;         // irregular edges of the list launch
+};
+
+template <int TME, bool Fast, int ND, bool HW> FusedPlan planFused(const FusedCtx<Fast> &C) {
+   using Sh                = FusedShape<TME, ND, HW>;
+   const MeshView &M       = C.M;
+   const TendParams &P     = C.P;
+   const StageUpdate *St   = C.Stage;
+   const TuningOptions &Tn = tuning();
+   FusedPlan D{};
+   D.NWide      = (Sh::CanWide && C.Wide) ? C.Wide->NWideCells : 0;
+   D.NMain      = ND == TME ? M.NRingCellsM0 : M.NRingCellsM1; // cells of the sweeps' valence
+   D.NOther     = ND == TME ? M.NRingCellsM1 : M.NRingCellsM0; // cells of valence NA (list launches)
+   D.OtherCells = ND == TME ? M.RingCellsM1 : M.RingCellsM0;
+   D.NM2        = TME >= 6 ? M.NRingCellsM2 : 0;
+   // the band of an overlapped stage: without the halo cells whose results the exchange replaces (Kernels.h)
+   D.SendOnly  = Tn.SendBand && St && St->AfterBand && St->HaloOutputsReplaced && !St->StoreTend && M.NBandSendCells > 0;
+   D.BandList  = D.SendOnly ? M.BandSendCells : M.BandCells;
+   D.NBandList = D.SendOnly ? M.NBandSendCells : M.NBandCells;
+   // sweep lengths of a stage (Kernels.h: StageUpdate::NCellsL1 / NCellsVel / NCellsTr)
+   auto SweepLen = [&](I4 Want) {
+      return (Tn.ShrinkSweeps && St && !St->StoreTend && Want > 0 && Want < M.NCellsAll) ? Want : M.NCellsAll;
    };
-   const bool CellCentric     = M.CellPVOK && EdgeScratch;
+   D.NSweepL1  = SweepLen(St ? St->NCellsL1 : 0);
+   D.NSweepVel = SweepLen(St ? St->NCellsVel : 0);
+   D.NSweepTr  = SweepLen(St ? St->NCellsTr : 0);
+   D.HyperDiff = P.VelHyperDiffTendencyEnable != 0;
+   D.PVOn      = P.PVTendencyEnable != 0;
+   // the vertex kernel stores RelVort and 1/LayerThickVertex; the two normalised vorticities are rebuilt from
+   // them where they are consumed; without the cell-centric tables the edge kernels read the reference's arrays
+   D.CellCentric = M.CellPVOK && C.EdgeScratch;
    // vertex pass and side-0 PV sums inside the L1 cell kernel (option MergeL1 = 0: the three separate kernels)
-   const int MergeL1Env = Tn.MergeL1;
-   const bool MergeL1 = CellCentric && M.CellL1OK && P.PVTendencyEnable && MergeL1Env != 0 &&
-                        (Fast || TME <= 7); // (8 edge slots with run-time option flags would spill registers)
-   FusedKernelNames[0]        = MergeL1 ? "" : "VortVertexBody";
-   FusedKernelNames[1]        = MergeL1 ? "FusedCellL1PVBody" : "FusedCell1Body";
-   if (!MergeL1)
-      launchVertexAuxState1(Wide ? *Wide : M, K, A, H, U, S, /*StoreNorm*/ !CellCentric, /*StoreInv*/ CellCentric);
-   Mark(1);
-   const int DoDel2Tr = (NT > 0 && P.TracerHyperDiffTendencyEnable) ? 1 : 0;
-   bool Cell1Done = false;
+   D.MergeL1 = D.CellCentric && M.CellL1OK && P.PVTendencyEnable && Tn.MergeL1 != 0 &&
+               (Fast || TME <= 7); // (8 edge slots with run-time option flags would spill registers)
    // the merged kernel can take the side-0 sums of the cells with one edge fewer than the sweep's valence along (INLO)
-   const bool InlineOther = MergeL1 && ND == TME && NOther > 0;
-   if (MergeL1) {
-      auto LaunchL1x = [&](auto Epi, auto Inl) {
-         constexpr bool EP = decltype(Epi)::value, IL = decltype(Inl)::value && ND == TME;
-         FusedCellL1PVBody<TME, Fast, EP, ND, IL, FLS> B{M,  K,  NT,    P,      DoDel2Tr,        H,
-                                            U,  Tr, A.KineticEnergyCell, A.VelocityDivCell, HTend, A.Del2TracersCell,
-                                            A.RelVortVertex, A.InvThickVertex, EdgeScratch, EH};
-         if constexpr (CanWide) {
-            if (NWide > 0) { // the wide cells' level-1 work rides along: same body, TW slots, wide tables, cell list
-               FusedCellL1PVBody<TW, Fast, EP, TW, false, 1> Bw{*Wide, K,  NT,    P,      DoDel2Tr,        H,
-                                                       U,     Tr, A.KineticEnergyCell, A.VelocityDivCell, HTend, A.Del2TracersCell,
-                                                       A.RelVortVertex, A.InvThickVertex, EdgeScratch, EH};
-               Bw.List = Wide->WideCells;
-               launchTileV(K, S, B, NSweepL1, Bw, NWide);
-               return;
-            }
-         }
-         B.SkipBad = M.NBadCells > 0;
-         if (M.NBadCells > 0) {
-            // the cells outside the ring tables: the generic level-1 cell body over their list, in the sweep's launch
-            // (their edges are on the irregular-edge list); the vertices no good cell stores through the vertex kernel
-            FusedCell1Body<TME, Fast, EP> Bb{M, K, NT, P, DoDel2Tr, H, U, Tr, A.KineticEnergyCell, A.VelocityDivCell,
-                                             HTend, A.Del2TracersCell, EH};
-            Bb.List = M.BadCells;
-            launchTileV(K, S, B, NSweepL1, Bb, M.NBadCells);
-            launchVertexAuxState1List(M, K, A, H, U, S, M.OrphanVertices, M.NOrphanVertices);
-            return;
-         }
-         launchTile(B, NSweepL1, K, S);
-      };
-      auto LaunchL1 = [&](auto Epi) {
-         if (InlineOther)
-            LaunchL1x(Epi, std::true_type{});
-         else
-            LaunchL1x(Epi, std::false_type{});
-      };
-      if constexpr (Fast) {
-         if (Stage)
-            LaunchL1(std::true_type{});
-         else
-            LaunchL1(std::false_type{});
-      } else {
-         LaunchL1(std::false_type{});
-      }
-      Cell1Done = true;
-   }
-   if constexpr (Fast) {
-      if (Stage && !Cell1Done) {
-         FusedCell1Body<TME, true, true> B{M, K, NT, P, DoDel2Tr, H, U, Tr, A.KineticEnergyCell, A.VelocityDivCell,
-                                           HTend, A.Del2TracersCell, EH};
-         launchTile(B, M.NCellsAll, K, S);
-         Cell1Done = true;
-      }
-   }
-   if (!Cell1Done) {
-      FusedCell1Body<TME, Fast> B{M, K, NT, P, DoDel2Tr, H, U, Tr, A.KineticEnergyCell, A.VelocityDivCell, HTend,
-                                  A.Del2TracersCell};
-      launchTile(B, M.NCellsAll, K, S);
-   }
-   if constexpr (CanWide) {
-      if (NWide > 0 && !MergeL1) { // the wide cells' level-1 work (merged kernel: launched together with the sweep above)
-         auto WideL1 = [&](auto Epi) {
-            constexpr bool EP = decltype(Epi)::value;
-            FusedCell1Body<TW, Fast, EP> B{*Wide, K, NT, P, DoDel2Tr, H, U, Tr, A.KineticEnergyCell, A.VelocityDivCell,
-                                           HTend, A.Del2TracersCell, EH};
-            B.List = Wide->WideCells;
-            launchTile(B, NWide, K, S);
-         };
-         if constexpr (Fast) {
-            if (Stage)
-               WideL1(std::true_type{});
-            else
-               WideL1(std::false_type{});
-         } else {
-            WideL1(std::false_type{});
-         }
-      }
-   }
-   if (P.WindForcingTendencyEnable)
-      launchEdgeAuxState1(Wide ? *Wide : M, A, P.WindInterpIsotropic, S);
-   Pacer::stop("Tend:fused:L1", 2);
-   // L2 (only the del4 term consumes it): replaces AuxState:edgeAuxState3 (Del2Edge), cellAuxState2, vertexAuxState2
-   Pacer::start("Tend:fused:L2[AuxState:vertexAuxState2,cellAuxState2]", 2);
-   Mark(2);
+   D.InlineOther = D.MergeL1 && ND == TME && D.NOther > 0;
    // independent sweeps share a launch (KernelCommon.h: tileKernel2); option Pair = 0 launches them one by one
-   const int PairEnv = Tn.Pair;
-   const bool PairL2        = PairEnv && P.VelHyperDiffTendencyEnable && M.Del2RingOK && M.Del2VertOK;
-   bool WideL2Done = false, BadL2Done = false;
-   FusedKernelNames[2] = FusedKernelNames[3] = "";
-   if (PairL2) {
-      FusedKernelNames[2] = "Del2CellRingBody+Del2VertexSelBody";
-      Del2CellRingBody<TME, FLS> BC{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell};
-      Del2VertexSelBody BV{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2RelVortVertex};
-      bool Launched = false;
-      if constexpr (CanWide) {
-         if (NWide > 0) {
-            Del2CellRingBody<TW, 1> BW{*Wide, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell};
-            BW.List = Wide->WideCells;
-            launchTileV(K, S, BC, M.NCellsAll, BV, M.NVerticesAll, BW, NWide);
-            Launched = WideL2Done = true;
-         }
-      }
-      if (!Launched && M.NBadCells > 0) { // (the cells outside the ring tables ride along: generic body over their list)
-         FusedDel2CellBody Bb{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell, M.BadCells};
-         launchTileV(K, S, BC, M.NCellsAll, BV, M.NVerticesAll, Bb, M.NBadCells);
-         Launched = BadL2Done = true;
-      }
-      if (!Launched)
-         launchTile2(BC, M.NCellsAll, BV, M.NVerticesAll, K, S);
-   } else if (P.VelHyperDiffTendencyEnable) {
-      FusedKernelNames[2] = M.Del2RingOK ? "Del2CellRingBody" : "FusedDel2CellBody";
-      if (M.Del2RingOK) {
-         Del2CellRingBody<TME, FLS> BC{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell};
-            launchTile(BC, M.NCellsAll, K, S);
-      } else {
-         FusedDel2CellBody BC{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell};
-         launchTile(BC, M.NCellsAll, K, S);
-      }
-   }
-   Mark(3);
-   if (P.VelHyperDiffTendencyEnable && !PairL2) {
-      FusedKernelNames[3] = M.Del2VertOK ? "Del2VertexSelBody" : "FusedDel2VertexBody";
-      if (M.Del2VertOK) {
-         Del2VertexSelBody BV{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2RelVortVertex};
-         launchTile(BV, M.NVerticesAll, K, S);
-      } else {
-         FusedDel2VertexBody BV{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2RelVortVertex};
-         launchTile(BV, M.NVerticesAll, K, S);
-      }
-   }
-   if constexpr (CanWide) {
-      if (NWide > 0 && P.VelHyperDiffTendencyEnable && !WideL2Done) { // (a narrow view implies the ring form)
-         Del2CellRingBody<TW, 1> BC{*Wide, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell};
-         BC.List = Wide->WideCells;
-         launchTile(BC, NWide, K, S);
-      }
-   }
-   if (P.VelHyperDiffTendencyEnable && M.Del2RingOK && M.NBadCells > 0 && !BadL2Done) { // the cells outside the ring tables
-      FusedDel2CellBody Bb{M, K, A.VelocityDivCell, A.RelVortVertex, A.Del2DivCell, M.BadCells};
-      launchTile(Bb, M.NBadCells, K, S);
-   }
-   Pacer::stop("Tend:fused:L2", 2);
-   // L3: replaces Tend:potientialVortHAdv, KEGrad, SSHGrad, velocityDiffusion, velocityHyperDiff, windForcing, bottomDrag,
-   // AuxState:edgeAuxState4 (HTracersEdge) and Tend:tracerHorzAdv, tracerDiffusion, tracerHyperDiff
-   Pacer::start("Tend:fused:L3[Tend:potientialVortHAdv,KEGrad,SSHGrad,velocityDiffusion,velocityHyperDiff,tracerHorzAdv,"
-                "tracerDiffusion,tracerHyperDiff]", 2);
-   Mark(4);
-   bool Marked5        = false;
-   std::function<void()> LaunchFinalInterior; // set when the side-1 sweep is split for an overlapped exchange
-   FusedKernelNames[4] = "FusedEdgeChainBody", FusedKernelNames[5] = "";
+   D.PairL2  = Tn.Pair && P.VelHyperDiffTendencyEnable && M.Del2RingOK && M.Del2VertOK;
+   D.PVFinal = D.CellCentric && D.PVOn && Fast && M.CellPVFinalOK;
+   // Overlap == true: the full sweep is split into the band list now and the interior list after
+   // the exchange has been started (Stage->AfterBand), see Kernels.h: StageUpdate
+   D.Overlap = St && St->AfterBand && M.NBandCells > 0;
    // the side-1 PV + velocity kernel and the tracer kernel are independent: their main sweeps share a launch
-   const bool PairL3 = PairEnv && Fast && M.CellPVOK && EdgeScratch && P.PVTendencyEnable && M.CellPVFinalOK && NT > 0 &&
-                       NMain > 0;
+   D.PairL3 = Tn.Pair && Fast && M.CellPVOK && C.EdgeScratch && P.PVTendencyEnable && M.CellPVFinalOK && C.NT > 0 &&
+              D.NMain > 0;
    // the plain RHS does both in ONE thread per (cell, levels): h and u gathered once (CellPVFinalTracerBody)
-   const bool FuseL3 = PairL3 && !Stage;
+   D.FuseL3 = D.PairL3 && !St;
    // narrow tables, plain RHS: the wide cells' level-3 work (one thread does velocity + tracers, as the sweep's) and the
    // final pass of the other valence's list join the sweep's launch instead of being launches of their own
    // (measured on a QU240-sized sphere, 12 pentagons: their final-pass list inside the sweep's launch: RHS 109 -> 102 us;
    // the same for the stage pair, as a third body, and the side-0 list folded into the level-2 launch: both slower)
-   const bool FoldL3 = FuseL3 && ((CanWide && NWide > 0) || NOther > 0);
+   D.FoldL3 = D.FuseL3 && ((Sh::CanWide && D.NWide > 0) || D.NOther > 0);
    // plain RHS, one table width: the irregular-edge list (coast lines; the masked rim of a partition's halo) joins the
    // sweep's launch too (an eighth of the QU30-sized mesh with its halo: one launch of ~10 us less per RHS)
-   const bool FoldChain = FuseL3 && !Wide && M.NIrregularEdges > 0;
-   if (M.CellPVOK && EdgeScratch) {
-      const bool PVOn = P.PVTendencyEnable != 0;
-      bool Finished   = false;
-      FusedKernelNames[4] = "";
-      if (PVOn) {
-         // the rarer valences (MaxEdges-1, MaxEdges-2: e.g. the pentagons of a mesh stored with
-         // maxEdges = 6 or 7) run the same ring code, instantiated for their size, over cell lists
-         constexpr int NM1 = NA, NM2 = TME >= 6 ? TME - 2 : TME - 1; // (NM1: "the other big valence")
-         CellPVBody<TME, Fast, 0, ND> B0{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch};
-         if (NMain > 0 && !MergeL1) // (merged: done by the L1 kernel; only the rarer valences remain)
-            launchTile(B0, M.NCellsAll, K, S);
-         FusedKernelNames[4] =
-             (!MergeL1 || (NOther > 0 && !InlineOther) || (TME >= 6 && M.NRingCellsM2 > 0)) ? "CellPVBody<side 0>" : "";
-         if (NOther > 0 && !InlineOther) {
-            CellPVBody<TME, Fast, 0, NM1> Bm{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                             OtherCells};
-            launchTile(Bm, NOther, K, S);
-         }
-         if (TME >= 6 && M.NRingCellsM2 > 0) {
-            CellPVBody<TME, Fast, 0, NM2> Bm{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                             M.RingCellsM2};
-            launchTile(Bm, M.NRingCellsM2, K, S);
-         }
-         if constexpr (CanWide) {
-            if (NWide > 0 && !MergeL1) {
-               CellPVBody<TW, Fast, 0, TW> Bw{*Wide, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                              Wide->WideCells};
-               launchTile(Bw, NWide, K, S);
-            }
-         }
-         Mark(5);
-         Marked5 = true;
-         if (Fast && M.CellPVFinalOK) {
-            // Overlap == true: the full sweep is split into the band list now and the interior list after
-            // the exchange has been started (Stage->AfterBand), see Kernels.h: StageUpdate
-            const bool Overlap = Stage && Stage->AfterBand && M.NBandCells > 0;
-            auto LaunchFinal = [&](auto Epi) {
-               constexpr bool EP = decltype(Epi)::value;
-               CellPVFinalBody<TME, ND, EP> B1{M,
-                                                K,
-                                                P,
-                                                H,
-                                                U,
-                                                A.RelVortVertex,
-                                                A.InvThickVertex,
-                                                EdgeScratch,
-                                                A.RelVortVertex,
-                                                A.KineticEnergyCell,
-                                                A.VelocityDivCell,
-                                                A.Del2DivCell,
-                                                A.Del2RelVortVertex,
-                                                UTend,
-                                                nullptr,
-                                                EU};
-               if (NMain > 0 && !PairL3) { // (paired: launched together with the tracer kernel below)
-                  if (Overlap) {
-                     B1.List = BandList;
-                     launchTile(B1, NBandList, K, BandS());
-                  } else {
-                     launchTile(B1, EP ? NSweepVel : M.NCellsAll, K, S);
-                  }
-               }
-               if (NOther > 0 && !FoldL3) {
-                  CellPVFinalBody<TME, NM1, EP> Bm{B1.M,       B1.K,   B1.P,    B1.H,       B1.U,
-                                                   B1.RelVortV, B1.InvThickV, B1.Partial, B1.RelVort, B1.KE,
-                                                   B1.Div,     B1.Del2Div, B1.Del2RelVort, B1.Tend, OtherCells, EU};
-                  launchTile(Bm, NOther, K, S);
-               }
-               if (TME >= 6 && M.NRingCellsM2 > 0) {
-                  CellPVFinalBody<TME, NM2, EP> Bm{B1.M,       B1.K,   B1.P,    B1.H,       B1.U,
-                                                   B1.RelVortV, B1.InvThickV, B1.Partial, B1.RelVort, B1.KE,
-                                                   B1.Div,     B1.Del2Div, B1.Del2RelVort, B1.Tend, M.RingCellsM2, EU};
-                  launchTile(Bm, M.NRingCellsM2, K, S);
-               }
-               if constexpr (CanWide) {
-                  if (NWide > 0 && !FoldL3) {
-                     CellPVFinalBody<TW, TW, EP> Bw{*Wide,      B1.K,   B1.P,    B1.H,       B1.U,
-                                                    B1.RelVortV, B1.InvThickV, B1.Partial, B1.RelVort, B1.KE,
-                                                    B1.Div,     B1.Del2Div, B1.Del2RelVort, B1.Tend, Wide->WideCells, EU};
-                     launchTile(Bw, NWide, K, S);
-                  }
-               }
-            };
-            // the interior part of the split sweep, launched at the end of the L3 phase
-            LaunchFinalInterior = [&, Overlap]() {
-               (void)Overlap;
-               if constexpr (Fast) {
-                  if (Overlap && NMain > 0 && M.NInteriorCells > 0 && !PairL3) {
-                     CellPVFinalBody<TME, ND, true> B1{M,
-                                                        K,
-                                                        P,
-                                                        H,
-                                                        U,
-                                                        A.RelVortVertex,
-                                                        A.InvThickVertex,
-                                                        EdgeScratch,
-                                                        A.RelVortVertex,
-                                                        A.KineticEnergyCell,
-                                                        A.VelocityDivCell,
-                                                        A.Del2DivCell,
-                                                        A.Del2RelVortVertex,
-                                                        UTend,
-                                                        M.InteriorCells,
-                                                        EU};
-                     launchTile(B1, M.NInteriorCells, K, S);
-                  }
-               }
-            };
-            if (Stage)
-               LaunchFinal(std::true_type{});
-            else
-               LaunchFinal(std::false_type{});
-            Finished            = true;
-            // (paired: the main sweep runs in slot 6 together with the tracer kernel; only the list launches of the
-            // rarer valences remain here)
-            FusedKernelNames[5] = !PairL3 ? "CellPVFinalBody"
-                                          : ((NOther > 0 || (TME >= 6 && M.NRingCellsM2 > 0)) ? "CellPVFinalBody (rarer valences)" : "");
-         } else {
-            CellPVBody<TME, Fast, 1, ND> B1{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch};
-            if (NMain > 0)
-               launchTile(B1, M.NCellsAll, K, S);
-            if (NOther > 0) {
-               CellPVBody<TME, Fast, 1, NM1> Bm{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                                OtherCells};
-               launchTile(Bm, NOther, K, S);
-            }
-            if (TME >= 6 && M.NRingCellsM2 > 0) {
-               CellPVBody<TME, Fast, 1, NM2> Bm{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                                M.RingCellsM2};
-               launchTile(Bm, M.NRingCellsM2, K, S);
-            }
-            if constexpr (CanWide) {
-               if (NWide > 0) {
-                  CellPVBody<TW, Fast, 1, TW> Bw{*Wide, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                                 Wide->WideCells};
-                  launchTile(Bw, NWide, K, S);
-               }
-            }
-         }
-      }
-      if (!Finished) {
-         FusedKernelNames[5] = "CellPVBody<side 1>+EdgeFinalBody";
-         EdgeFinalBody<Fast> BF{M,
-                                K,
-                                P,
-                                H,
-                                U,
-                                EdgeScratch,
-                                A.RelVortVertex,
-                                A.KineticEnergyCell,
-                                A.VelocityDivCell,
-                                A.Del2DivCell,
-                                A.Del2RelVortVertex,
-                                A.NormalStressEdge,
-                                UTend};
-         launchTile(BF, M.NEdgesAll, K, S);
-      }
-      // (a stage whose halo outputs the exchange replaces: the owned irregular edges -- a coast -- only, not the masked
-      // edges of the halo rim)
-      // (... and a stage whose velocity sweep stops after halo layer 3 finishes the edges of the cells through layer 2)
-      const int NIrr = SendOnly ? M.NIrregularOwned : (NSweepVel < M.NCellsAll ? M.NIrregularInner : M.NIrregularEdges);
-      if (NIrr > 0 && !FoldChain) {
-         auto LaunchList = [&](auto Epi) {
-            constexpr bool EP = decltype(Epi)::value;
-            if constexpr (CanWide) {
-               if (Wide) { // (the chain tables are per edge and MaxEdges of the WIDE view wide)
-                  FusedEdgeChainBody<TW, Fast, EP, true> B{*Wide, K, P, H, U, A.RelVortVertex, A.InvThickVertex, nullptr,
-                                                           A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell,
-                                                           A.Del2RelVortVertex, A.NormalStressEdge, UTend,
-                                                           M.IrregularEdges, EU};
-                  launchTile(B, NIrr, K, S);
-                  return;
-               }
-            }
-            FusedEdgeChainBody<TME, Fast, EP, true> B{M,
-                                                      K,
-                                                      P,
-                                                      H,
-                                                      U,
-                                                      A.RelVortVertex,
-                                                      A.InvThickVertex,
-                                                      nullptr,
-                                                      A.KineticEnergyCell,
-                                                A.VelocityDivCell,
-                                                A.Del2DivCell,
-                                                A.Del2RelVortVertex,
-                                                A.NormalStressEdge,
-                                                UTend,
-                                                M.IrregularEdges,
-                                                EU};
-            launchTile(B, NIrr, K, S);
-         };
-         if (Stage)
-            LaunchList(std::true_type{});
-         else
-            LaunchList(std::false_type{});
-      }
-   } else if (M.PVChainOK) {
-      FusedEdgeChainBody<TME, Fast> B{M,
-                                      K,
-                                      P,
-                                      H,
-                                      U,
-                                      A.RelVortVertex,
-                                      A.NormRelVortVertex,
-                                      A.NormPlanetVortVertex,
-                                      A.KineticEnergyCell,
-                                      A.VelocityDivCell,
-                                      A.Del2DivCell,
-                                      A.Del2RelVortVertex,
-                                      A.NormalStressEdge,
-                                      UTend,
-                                      nullptr};
-      launchTile(B, M.NEdgesAll, K, S);
+   D.FoldChain = D.FuseL3 && !C.Wide && M.NIrregularEdges > 0;
+   // (a stage splits its tracer launches exactly when it splits its velocity sweep)
+   D.SplitTr = Fast && D.Overlap && C.NT > 0;
+   // (a stage whose halo outputs the exchange replaces: the owned irregular edges -- a coast -- only, not the masked
+   // edges of the halo rim)
+   // (... and a stage whose velocity sweep stops after halo layer 3 finishes the edges of the cells through layer 2)
+   D.NIrr = D.SendOnly ? M.NIrregularOwned : (D.NSweepVel < M.NCellsAll ? M.NIrregularInner : M.NIrregularEdges);
+   return D;
+}
+
+/// FusedKernelNames[0..6]: the kernel behind each timed slot ("" = none), Kernels.h
+template <bool Fast> void nameFusedKernels(const FusedCtx<Fast> &C, const FusedPlan &D) {
+   const MeshView &M = C.M;
+   const bool Rarer  = D.NOther > 0 || D.NM2 > 0;
+   const char **N    = FusedKernelNames;
+   N[0]              = D.MergeL1 ? "" : "VortVertexBody";
+   N[1]              = D.MergeL1 ? "FusedCellL1PVBody" : "FusedCell1Body";
+   N[2]              = D.PairL2        ? "Del2CellRingBody+Del2VertexSelBody"
+                       : !D.HyperDiff  ? ""
+                       : M.Del2RingOK  ? "Del2CellRingBody"
+                                       : "FusedDel2CellBody";
+   N[3] = (D.PairL2 || !D.HyperDiff) ? "" : M.Del2VertOK ? "Del2VertexSelBody" : "FusedDel2VertexBody";
+   if (D.CellCentric) {
+      const bool Side0 = D.PVOn && (!D.MergeL1 || (D.NOther > 0 && !D.InlineOther) || D.NM2 > 0);
+      N[4]             = Side0 ? "CellPVBody<side 0>" : "";
+      // (paired: the main sweep runs in slot 6 together with the tracer kernel; only the list launches of the
+      // rarer valences remain in slot 5)
+      N[5] = !D.PVFinal  ? "CellPVBody<side 1>+EdgeFinalBody"
+             : !D.PairL3 ? "CellPVFinalBody"
+             : Rarer     ? "CellPVFinalBody (rarer valences)"
+                         : "";
    } else {
-      FusedKernelNames[4] = "FusedEdgeBody";
-      FusedEdgeBody B{M,       K,           P,           H,           U,
-                      A.RelVortVertex, A.NormRelVortVertex, A.NormPlanetVortVertex, A.KineticEnergyCell, A.VelocityDivCell,
-                      A.Del2DivCell,   A.Del2RelVortVertex, A.NormalStressEdge,     UTend};
-      launchTile(B, M.NEdgesAll, K, S);
+      N[4] = M.PVChainOK ? "FusedEdgeChainBody" : "FusedEdgeBody";
+      N[5] = "";
    }
-   if (!Marked5)
-      Mark(5);
-   Mark(6);
-   FusedKernelNames[6]        = FuseL3   ? "CellPVFinalTracerBody"
-                                : PairL3 ? "CellPVFinalBody+FusedCell3Body"
-                                         : (NT > 0 ? "FusedCell3Body" : "");
-   if constexpr (CanWide) {
-      if (NWide > 0 && NT > 0 && !FoldL3) {
-         auto WideTr = [&](auto Epi) {
-            constexpr bool EP = decltype(Epi)::value;
-            FusedCell3Body<TW, Fast, EP, 1> B{*Wide, K, NT, P, H, U, Tr, A.Del2TracersCell, TrTend, ET};
-            B.List = Wide->WideCells;
-            launchTile(B, NWide, K, S);
-         };
-         if constexpr (Fast) {
-            if (Stage)
-               WideTr(std::true_type{});
-            else
-               WideTr(std::false_type{});
-         } else {
-            WideTr(std::false_type{});
-         }
+   N[6] = D.FuseL3 ? "CellPVFinalTracerBody" : D.PairL3 ? "CellPVFinalBody+FusedCell3Body" : (C.NT > 0 ? "FusedCell3Body" : "");
+}
+
+/// the merged level-1 kernel: the sweep, with the wide cells' or the bad cells' list in the same launch
+template <int TME, bool Fast, int ND, bool HW, bool EP, bool INL>
+void fusedLevel1Merged(const FusedCtx<Fast> &C, const FusedPlan &D) {
+   using Sh          = FusedShape<TME, ND, HW>;
+   const MeshView &M = C.M;
+   auto B            = C.template cellL1PV<TME, EP, ND, INL && ND == TME, Sh::FLS>(M, nullptr);
+   if constexpr (Sh::CanWide) {
+      if (D.NWide > 0) { // the wide cells' level-1 work rides along: same body, TW slots, wide tables, cell list
+         launchTileV(C.K, C.S, B, D.NSweepL1, C.template cellL1PV<Sh::TW, EP, Sh::TW, false, 1>(*C.Wide, C.Wide->WideCells),
+                     D.NWide);
+         return;
       }
    }
-   bool AfterBandCalled = false;
-   if (PairL3) {
-      if constexpr (Fast) {
-         auto Go = [&](auto Epi) {
-            constexpr bool EP = decltype(Epi)::value;
-            CellPVFinalBody<TME, ND, EP> B1{M,
-                                             K,
-                                             P,
-                                             H,
-                                             U,
-                                             A.RelVortVertex,
-                                             A.InvThickVertex,
-                                             EdgeScratch,
-                                             A.RelVortVertex,
-                                             A.KineticEnergyCell,
-                                             A.VelocityDivCell,
-                                             A.Del2DivCell,
-                                             A.Del2RelVortVertex,
-                                             UTend,
-                                             nullptr,
-                                             EU};
-            FusedCell3Body<TME, true, EP, FLL> B3{M, K, NT, P, H, U, Tr, A.Del2TracersCell, TrTend, ET};
-            if constexpr (!EP) {
-               { // plain RHS (FuseL3): one thread per (cell, levels) does both, h and u gathered once
-                  CellPVFinalTracerBody<TME, ND, FLS> BF{M, K, NT, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                                A.RelVortVertex, A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell,
-                                                A.Del2RelVortVertex, UTend, Tr, A.Del2TracersCell, TrTend};
-                  // the sweep's body Bs -- plain or with the tracer loop through LDS tile patches -- alone or with the lists
-                  // that ride along in its launch
-                  auto LaunchSweep = [&](const auto &Bs) {
-                  if constexpr (CanWide) {
-                        if (FoldL3 && NWide > 0) {
-                           CellPVFinalTracerBody<TW, TW, 1> BW{*Wide, K, NT, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                                            A.RelVortVertex, A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell,
-                                                            A.Del2RelVortVertex, UTend, Tr, A.Del2TracersCell, TrTend};
-                           BW.List = Wide->WideCells;
-                           constexpr int NM1f = ND == TME ? TME - 1 : TME;
-                           CellPVFinalBody<TME, NM1f, false> Bm{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                                                 A.RelVortVertex, A.KineticEnergyCell, A.VelocityDivCell,
-                                                                 A.Del2DivCell, A.Del2RelVortVertex, UTend, OtherCells, EU};
-                           launchTileV(K, S, Bs, M.NCellsAll, BW, NWide, Bm, NOther);
-                           return;
-                        }
-                     }
-                     if (FoldL3 || FoldChain) { // (no wide cells: the sweep, the other valence's final pass, the irregular edges)
-                        constexpr int NM1f = ND == TME ? TME - 1 : TME;
-                        CellPVFinalBody<TME, NM1f, false> Bm{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, EdgeScratch,
-                                                              A.RelVortVertex, A.KineticEnergyCell, A.VelocityDivCell,
-                                                              A.Del2DivCell, A.Del2RelVortVertex, UTend, OtherCells, EU};
-                        FusedEdgeChainBody<TME, Fast, false, true> Bc{M, K, P, H, U, A.RelVortVertex, A.InvThickVertex, nullptr,
-                                                                      A.KineticEnergyCell, A.VelocityDivCell, A.Del2DivCell,
-                                                                      A.Del2RelVortVertex, A.NormalStressEdge, UTend,
-                                                                      M.IrregularEdges, EU};
-                        const int NO = FoldL3 ? NOther : 0, NC = FoldChain ? M.NIrregularEdges : 0;
-                        if (NO > 0 && NC > 0)
-                           launchTileV(K, S, Bs, M.NCellsAll, Bm, NO, Bc, NC);
-                        else if (NC > 0)
-                           launchTileV(K, S, Bs, M.NCellsAll, Bc, NC);
-                        else
-                           launchTileV(K, S, Bs, M.NCellsAll, Bm, NO);
-                        return;
-                     }
-                     launchTile(Bs, M.NCellsAll, K, S);
-                     return;
-                  };
-                  if constexpr (TME <= 7) {
-                     // option TracerPatch: the tracer loop's neighbour values through LDS tile patches (16-byte accesses,
-                     // line-wide thread geometry and a tile size the mesh has patch tables for); the lists keep their bodies
-                     const int NList = (CanWide && FoldL3 ? NWide : 0) + (FoldL3 ? NOther : 0) + (FoldChain ? M.NIrregularEdges : 0);
-                     const Geom Gp   = makeGeom(M.NCellsAll + NList, K, 2, levelPitch(K), NT <= 8 ? 16 : 0);
-                     const int Slot  = MeshView::patchSlot(Gp.Tile);
-                     // (from 4 tracers on: with 2 the transfers' set-up and the barriers cost more than they save --
-                     // EC30to60-sized, 2 tracers: level 3 +1.7 %, QU240-sized +7 %; an eighth of QU30, 6 tracers: -2.3 %)
-                     if (Tn.TracerPatch && NT >= 4 && Gp.W == 2 && Gp.Block.x == 8 && Slot >= 0 && (int)Gp.Block.y == Gp.Tile) {
-                        CellPVFinalTracerPatchBody<TME, ND, FLS> BP{{BF}, M.PatchRows[Slot], M.PatchIdx[Slot], M.PatchOK[Slot],
-                                                                   M.PatchNP[Slot], Gp.Tile};
-                        LaunchSweep(BP);
-                        return;
-                     }
-                  }
-                  LaunchSweep(BF);
-                  return;
-               }
-            } else if (Stage->AfterBand && M.NBandCells > 0) { // RK4 stages: the two bodies as a paired launch
-               B1.List = B3.List = BandList;
-               launchTile2(B1, NBandList, B3, NBandList, K, BandS());
-               Stage->AfterBand(Stage->AfterBandCtx); // u, h and the tracers of every sent element are final
-               AfterBandCalled = true;
+   B.SkipBad = M.NBadCells > 0;
+   if (M.NBadCells > 0) {
+      // the cells outside the ring tables: the generic level-1 cell body over their list, in the sweep's launch
+      // (their edges are on the irregular-edge list); the vertices no good cell stores through the vertex kernel
+      launchTileV(C.K, C.S, B, D.NSweepL1, C.template cell1<TME, EP>(M, M.BadCells), M.NBadCells);
+      launchVertexAuxState1List(M, C.K, C.A, C.H, C.U, C.S, M.OrphanVertices, M.NOrphanVertices);
+   } else {
+      launchTile(B, D.NSweepL1, C.K, C.S);
+   }
+}
+
+/// L1: replaces AuxState:vertexAuxState1, cellAuxState1, edgeAuxState1/2 (flux thickness), cellAuxState4 (Del2Tracers),
+/// Tend:thicknessFluxDiv and the cell-0 half of Tend:potientialVortHAdv
+template <int TME, bool Fast, int ND, bool HW> void fusedLevel1(const FusedCtx<Fast> &C, const FusedPlan &D) {
+   using Sh          = FusedShape<TME, ND, HW>;
+   const MeshView &M = C.M;
+   if (!D.MergeL1)
+      launchVertexAuxState1(C.full(), C.K, C.A, C.H, C.U, C.S, /*StoreNorm*/ !D.CellCentric, /*StoreInv*/ D.CellCentric);
+   C.mark(1);
+   withEpi<Fast>(C.Stage, [&](auto Epi) {
+      constexpr bool EP = decltype(Epi)::value;
+      if (D.MergeL1 && D.InlineOther) {
+         fusedLevel1Merged<TME, Fast, ND, HW, EP, true>(C, D);
+      } else if (D.MergeL1) {
+         fusedLevel1Merged<TME, Fast, ND, HW, EP, false>(C, D);
+      } else {
+         launchTile(C.template cell1<TME, EP>(M, nullptr), M.NCellsAll, C.K, C.S);
+         if constexpr (Sh::CanWide) {
+            if (D.NWide > 0) // the wide cells' level-1 work (merged kernel: launched together with the sweep above)
+               launchTile(C.template cell1<Sh::TW, EP>(*C.Wide, C.Wide->WideCells), D.NWide, C.K, C.S);
+         }
+      }
+   });
+   if (C.P.WindForcingTendencyEnable)
+      launchEdgeAuxState1(C.full(), C.A, C.P.WindInterpIsotropic, C.S);
+}
+
+/// L2 (only the del4 term consumes it): replaces AuxState:edgeAuxState3 (Del2Edge), cellAuxState2, vertexAuxState2.
+///   paired  : ring cell sweep + vertex sweep (+ the wide cells' list, else + the bad cells' list) in one launch
+///   unpaired: cell sweep, vertex sweep, the wide cells' list: a launch each
+/// and the bad cells' list as a launch of its own wherever it did not ride along.
+template <int TME, bool Fast, int ND, bool HW> void fusedLevel2(const FusedCtx<Fast> &C, const FusedPlan &D) {
+   using Sh            = FusedShape<TME, ND, HW>;
+   const MeshView &M   = C.M;
+   const bool BadRides = D.PairL2 && D.NWide == 0 && M.NBadCells > 0;
+   if (D.PairL2) {
+      const auto BC = C.template del2Ring<TME, Sh::FLS>(M, nullptr);
+      const auto BV = C.del2VertexSel();
+      if (BadRides) { // (the cells outside the ring tables ride along: generic body over their list)
+         launchTileV(C.K, C.S, BC, M.NCellsAll, BV, M.NVerticesAll, C.del2Cell(M.BadCells), M.NBadCells);
+      } else if (D.NWide == 0) {
+         launchTile2(BC, M.NCellsAll, BV, M.NVerticesAll, C.K, C.S);
+      } else if constexpr (Sh::CanWide) {
+         launchTileV(C.K, C.S, BC, M.NCellsAll, BV, M.NVerticesAll, C.template del2Ring<Sh::TW, 1>(*C.Wide, C.Wide->WideCells),
+                     D.NWide);
+      }
+   } else if (D.HyperDiff) {
+      if (M.Del2RingOK)
+         launchTile(C.template del2Ring<TME, Sh::FLS>(M, nullptr), M.NCellsAll, C.K, C.S);
+      else
+         launchTile(C.del2Cell(nullptr), M.NCellsAll, C.K, C.S);
+   }
+   C.mark(3);
+   if (D.HyperDiff && !D.PairL2) {
+      if (M.Del2VertOK)
+         launchTile(C.del2VertexSel(), M.NVerticesAll, C.K, C.S);
+      else
+         launchTile(C.del2Vertex(), M.NVerticesAll, C.K, C.S);
+      if constexpr (Sh::CanWide) {
+         if (D.NWide > 0) // (a narrow view implies the ring form)
+            launchTile(C.template del2Ring<Sh::TW, 1>(*C.Wide, C.Wide->WideCells), D.NWide, C.K, C.S);
+      }
+   }
+   if (D.HyperDiff && M.Del2RingOK && M.NBadCells > 0 && !BadRides) // the cells outside the ring tables
+      launchTile(C.del2Cell(M.BadCells), M.NBadCells, C.K, C.S);
+}
+
+/// one side of the cell-centric PV sums: the sweep (side 0 of a merged level 1: done there) and the lists of the rarer
+/// valences and of the wide cells
+template <int TME, bool Fast, int ND, bool HW, int Side>
+void fusedPVSide(const FusedCtx<Fast> &C, const FusedPlan &D, bool Sweep, bool OtherList, bool WideList) {
+   using Sh          = FusedShape<TME, ND, HW>;
+   const MeshView &M = C.M;
+   if (Sweep)
+      launchTile(C.template pvSide<TME, Side, ND>(M, nullptr), M.NCellsAll, C.K, C.S);
+   if (OtherList)
+      launchTile(C.template pvSide<TME, Side, Sh::NM1>(M, D.OtherCells), D.NOther, C.K, C.S);
+   if (D.NM2 > 0)
+      launchTile(C.template pvSide<TME, Side, Sh::NM2>(M, M.RingCellsM2), D.NM2, C.K, C.S);
+   if constexpr (Sh::CanWide) {
+      if (WideList)
+         launchTile(C.template pvSide<Sh::TW, Side, Sh::TW>(*C.Wide, C.Wide->WideCells), D.NWide, C.K, C.S);
+   }
+}
+
+/// the interior part of a final sweep that was split for an overlapped exchange: launched after Stage->AfterBand
+template <int TME, bool Fast, int ND> void fusedFinalInterior(const FusedCtx<Fast> &C, const FusedPlan &D) {
+   if constexpr (Fast) {
+      if (D.PVFinal && D.Overlap && D.NMain > 0 && C.M.NInteriorCells > 0 && !D.PairL3)
+         launchTile(C.template pvFinal<TME, ND, true>(C.M, C.M.InteriorCells), C.M.NInteriorCells, C.K, C.S);
+   }
+}
+
+/// L3, velocity: replaces Tend:potientialVortHAdv, KEGrad, SSHGrad, velocityDiffusion, velocityHyperDiff, windForcing,
+/// bottomDrag.  Records event 5 after the side-0 launches (without them: at the end, together with 6).
+template <int TME, bool Fast, int ND, bool HW> void fusedLevel3Velocity(FusedCtx<Fast> &C, const FusedPlan &D) {
+   using Sh          = FusedShape<TME, ND, HW>;
+   const MeshView &M = C.M;
+   if (!D.CellCentric) {
+      if (M.PVChainOK)
+         launchTile(C.template chainAllEdges<TME>(), M.NEdgesAll, C.K, C.S);
+      else
+         launchTile(C.edgeGeneric(), M.NEdgesAll, C.K, C.S);
+      C.mark(5);
+      return;
+   }
+   if (D.PVOn) {
+      // (merged level 1: side 0 of the sweep and of the inlined other valence is done; only the rarer valences remain)
+      fusedPVSide<TME, Fast, ND, HW, 0>(C, D, D.NMain > 0 && !D.MergeL1, D.NOther > 0 && !D.InlineOther,
+                                        D.NWide > 0 && !D.MergeL1);
+      C.mark(5);
+   }
+   if (D.PVFinal) {
+      withEpi<Fast>(C.Stage, [&](auto Epi) {
+         constexpr bool EP = decltype(Epi)::value;
+         if (D.NMain > 0 && !D.PairL3) { // (paired: launched together with the tracer kernel, fusedLevel3Tracers)
+            if (D.Overlap)
+               launchTile(C.template pvFinal<TME, ND, EP>(M, D.BandList), D.NBandList, C.K, C.bandStream());
+            else
+               launchTile(C.template pvFinal<TME, ND, EP>(M, nullptr), EP ? D.NSweepVel : M.NCellsAll, C.K, C.S);
+         }
+         if (D.NOther > 0 && !D.FoldL3)
+            launchTile(C.template pvFinal<TME, Sh::NM1, EP>(M, D.OtherCells), D.NOther, C.K, C.S);
+         if (D.NM2 > 0)
+            launchTile(C.template pvFinal<TME, Sh::NM2, EP>(M, M.RingCellsM2), D.NM2, C.K, C.S);
+         if constexpr (Sh::CanWide) {
+            if (D.NWide > 0 && !D.FoldL3)
+               launchTile(C.template pvFinal<Sh::TW, Sh::TW, EP>(*C.Wide, C.Wide->WideCells), D.NWide, C.K, C.S);
+         }
+      });
+   } else {
+      if (D.PVOn)
+         fusedPVSide<TME, Fast, ND, HW, 1>(C, D, D.NMain > 0, D.NOther > 0, D.NWide > 0);
+      launchTile(C.edgeFinal(), M.NEdgesAll, C.K, C.S);
+   }
+   if (D.NIrr > 0 && !D.FoldChain) {
+      withEpi<Fast>(C.Stage, [&](auto Epi) {
+         constexpr bool EP = decltype(Epi)::value;
+         if constexpr (Sh::CanWide) {
+            if (C.Wide) { // (the chain tables are per edge and MaxEdges of the WIDE view wide)
+               launchTile(C.template chain<Sh::TW, EP>(*C.Wide, M.IrregularEdges), D.NIrr, C.K, C.S);
+               return;
+            }
+         }
+         launchTile(C.template chain<TME, EP>(M, M.IrregularEdges), D.NIrr, C.K, C.S);
+      });
+   }
+   if (!D.PVOn)
+      C.mark(5);
+}
+
+/// L3 of the plain RHS with tracers (FuseL3): one thread per (cell, levels) does velocity and tracers, h and u gathered
+/// once; the lists of FoldL3 / FoldChain ride along in the sweep's launch
+template <int TME, bool Fast, int ND, bool HW> void fusedLevel3Plain(const FusedCtx<Fast> &C, const FusedPlan &D) {
+   using Sh                = FusedShape<TME, ND, HW>;
+   const MeshView &M       = C.M;
+   const TuningOptions &Tn = tuning();
+   const int K = C.K, NT = C.NT;
+   const auto BF = C.template pvFinalTracer<TME, ND, Sh::FLS>(M, nullptr);
+   // the sweep's body Bs -- plain or with the tracer loop through LDS tile patches -- alone or with the lists
+   // that ride along in its launch
+   auto LaunchSweep = [&](const auto &Bs) {
+      if (!D.FoldL3 && !D.FoldChain) {
+         launchTile(Bs, M.NCellsAll, K, C.S);
+         return;
+      }
+      const auto Bm = C.template pvFinal<TME, Sh::NM1, false>(M, D.OtherCells);
+      if constexpr (Sh::CanWide) {
+         if (D.FoldL3 && D.NWide > 0) {
+            launchTileV(K, C.S, Bs, M.NCellsAll, C.template pvFinalTracer<Sh::TW, Sh::TW, 1>(*C.Wide, C.Wide->WideCells),
+                        D.NWide, Bm, D.NOther);
+            return;
+         }
+      }
+      // (no wide cells: the sweep, the other valence's final pass, the irregular edges)
+      const auto Bc = C.template chain<TME, false>(M, M.IrregularEdges);
+      const int NO = D.FoldL3 ? D.NOther : 0, NC = D.FoldChain ? M.NIrregularEdges : 0;
+      if (NO > 0 && NC > 0)
+         launchTileV(K, C.S, Bs, M.NCellsAll, Bm, NO, Bc, NC);
+      else if (NC > 0)
+         launchTileV(K, C.S, Bs, M.NCellsAll, Bc, NC);
+      else
+         launchTileV(K, C.S, Bs, M.NCellsAll, Bm, NO);
+   };
+   if constexpr (TME <= 7) {
+      // option TracerPatch: the tracer loop's neighbour values through LDS tile patches (16-byte accesses,
+      // line-wide thread geometry and a tile size the mesh has patch tables for); the lists keep their bodies
+      const int NList = (Sh::CanWide && D.FoldL3 ? D.NWide : 0) + (D.FoldL3 ? D.NOther : 0) + (D.FoldChain ? M.NIrregularEdges : 0);
+      const Geom Gp   = makeGeom(M.NCellsAll + NList, K, 2, levelPitch(K), NT <= 8 ? 16 : 0);
+      const int Slot  = MeshView::patchSlot(Gp.Tile);
+      // (from 4 tracers on: with 2 the transfers' set-up and the barriers cost more than they save --
+      // EC30to60-sized, 2 tracers: level 3 +1.7 %, QU240-sized +7 %; an eighth of QU30, 6 tracers: -2.3 %)
+      if (Tn.TracerPatch && NT >= 4 && Gp.W == 2 && Gp.Block.x == 8 && Slot >= 0 && (int)Gp.Block.y == Gp.Tile) {
+         CellPVFinalTracerPatchBody<TME, ND, Sh::FLS> BP{{BF}, M.PatchRows[Slot], M.PatchIdx[Slot], M.PatchOK[Slot],
+                                                         M.PatchNP[Slot], Gp.Tile};
+         LaunchSweep(BP);
+         return;
+      }
+   }
+   LaunchSweep(BF);
+}
+
+/// L3, tracers: replaces AuxState:edgeAuxState4 (HTracersEdge) and Tend:tracerHorzAdv, tracerDiffusion, tracerHyperDiff;
+/// paired, the velocity sweep is in the same launch.  An overlapped stage launches the band first, calls
+/// Stage->AfterBand (once), then the interior: velocity before tracers.
+template <int TME, bool Fast, int ND, bool HW> void fusedLevel3Tracers(FusedCtx<Fast> &C, const FusedPlan &D) {
+   using Sh                = FusedShape<TME, ND, HW>;
+   const MeshView &M       = C.M;
+   const StageUpdate *St   = C.Stage;
+   const int K             = C.K;
+   const hipStream_t S     = C.S;
+   if constexpr (Sh::CanWide) {
+      if (D.NWide > 0 && C.NT > 0 && !D.FoldL3)
+         withEpi<Fast>(St, [&](auto Epi) {
+            launchTile(C.template cell3<Sh::TW, decltype(Epi)::value, 1>(*C.Wide, C.Wide->WideCells), D.NWide, K, S);
+         });
+   }
+   if (D.FuseL3) {
+      if constexpr (Fast)
+         fusedLevel3Plain<TME, Fast, ND, HW>(C, D);
+   } else if (C.NT > 0) {
+      withEpi<Fast>(St, [&](auto Epi) {
+         constexpr bool EP = decltype(Epi)::value;
+         auto B3           = C.template cell3<TME, EP, Sh::FLL>(M, nullptr);
+         if constexpr (!EP) {
+            launchTile(B3, M.NCellsAll, K, S);
+         } else if (D.PairL3) { // RK4 stages: the two bodies as a paired launch
+            auto B1 = C.template pvFinal<TME, ND, true>(M, nullptr);
+            if (D.SplitTr) {
+               B1.List = B3.List = D.BandList;
+               launchTile2(B1, D.NBandList, B3, D.NBandList, K, C.bandStream());
+               St->AfterBand(St->AfterBandCtx); // u, h and the tracers of every sent element are final
                B1.List = B3.List = M.InteriorCells;
                launchTile2(B1, M.NInteriorCells, B3, M.NInteriorCells, K, S);
             } else {
-               launchTile2(B1, NSweepVel, B3, NSweepTr, K, S);
+               launchTile2(B1, D.NSweepVel, B3, D.NSweepTr, K, S);
             }
-         };
-         if (Stage)
-            Go(std::true_type{});
-         else
-            Go(std::false_type{});
-      }
-   } else if (NT > 0) {
-      bool Done = false;
-      if constexpr (Fast) {
-         if (Stage) {
-            FusedCell3Body<TME, true, true, FLL> B{M, K, NT, P, H, U, Tr, A.Del2TracersCell, TrTend, ET};
-            if (Stage->AfterBand && M.NBandCells > 0) {
-               B.List = BandList;
-               launchTile(B, NBandList, K, BandS());
-               Stage->AfterBand(Stage->AfterBandCtx); // u, h and the tracers of every sent element are final
-               AfterBandCalled = true;
-               if (LaunchFinalInterior)
-                  LaunchFinalInterior();
-               B.List = M.InteriorCells;
-               launchTile(B, M.NInteriorCells, K, S);
-            } else {
-               launchTile(B, NSweepTr, K, S);
-            }
-            Done = true;
+         } else if (D.SplitTr) {
+            B3.List = D.BandList;
+            launchTile(B3, D.NBandList, K, C.bandStream());
+            St->AfterBand(St->AfterBandCtx); // u, h and the tracers of every sent element are final
+            fusedFinalInterior<TME, Fast, ND>(C, D);
+            B3.List = M.InteriorCells;
+            launchTile(B3, M.NInteriorCells, K, S);
+         } else {
+            launchTile(B3, D.NSweepTr, K, S);
          }
-      }
-      if (!Done) {
-         FusedCell3Body<TME, Fast, false, FLL> B{M, K, NT, P, H, U, Tr, A.Del2TracersCell, TrTend};
-         launchTile(B, M.NCellsAll, K, S);
-      }
+      });
    }
-   if (Stage && Stage->AfterBand && !AfterBandCalled) { // no tracers (or no band): everything is final here
-      Stage->AfterBand(Stage->AfterBandCtx);
-      if (LaunchFinalInterior)
-         LaunchFinalInterior();
+   if (St && St->AfterBand && !D.SplitTr) { // no tracers (or no band): everything is final here
+      St->AfterBand(St->AfterBandCtx);
+      fusedFinalInterior<TME, Fast, ND>(C, D);
    }
-   Mark(7);
+}
+
+/// One evaluation of the fused RHS: template arguments as FusedShape; Fast = the Default.yml term set
+template <int TME, bool Fast, int ND = TME, bool HW = false>
+void launchFusedT(const MeshView &M, int K, int NT, const TendParams &P, const AuxPtrs &A, Real *HTend,
+                         Real *UTend, Real *TrTend, const Real *H, const Real *U, const Real *Tr, hipStream_t S,
+                         hipEvent_t *Ev, Real *EdgeScratch, const StageUpdate *Stage, const MeshView *Wide = nullptr) {
+   FusedCtx<Fast> C{M, Wide, K, NT, P, A, H, U, Tr, HTend, UTend, TrTend, EdgeScratch,
+                    (NT > 0 && P.TracerHyperDiffTendencyEnable) ? 1 : 0, S, Ev, Stage};
+   C.setStage();
+   const FusedPlan D = planFused<TME, Fast, ND, HW>(C);
+   nameFusedKernels(C, D);
+   Pacer::start("Tend:fused:L1[AuxState:vertexAuxState1,cellAuxState1,edgeAuxState2,cellAuxState4;Tend:thicknessFluxDiv]", 2);
+   C.mark(0);
+   fusedLevel1<TME, Fast, ND, HW>(C, D);
+   Pacer::stop("Tend:fused:L1", 2);
+   Pacer::start("Tend:fused:L2[AuxState:vertexAuxState2,cellAuxState2]", 2);
+   C.mark(2);
+   fusedLevel2<TME, Fast, ND, HW>(C, D);
+   Pacer::stop("Tend:fused:L2", 2);
+   Pacer::start("Tend:fused:L3[Tend:potientialVortHAdv,KEGrad,SSHGrad,velocityDiffusion,velocityHyperDiff,tracerHorzAdv,"
+                "tracerDiffusion,tracerHyperDiff]", 2);
+   C.mark(4);
+   fusedLevel3Velocity<TME, Fast, ND, HW>(C, D);
+   C.mark(6);
+   fusedLevel3Tracers<TME, Fast, ND, HW>(C, D);
+   C.mark(7);
    Pacer::stop("Tend:fused:L3", 2);
 }
 

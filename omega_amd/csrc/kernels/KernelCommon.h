@@ -14,7 +14,9 @@
 #ifndef OMEGA_AMD_KERNELCOMMON_H
 #define OMEGA_AMD_KERNELCOMMON_H
 
+#include <algorithm>
 #include <cstdlib>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <hip/hip_runtime.h>
@@ -477,73 +479,48 @@ template <class B> inline void prepBody(B &Body, int K) {
    if constexpr (BodyHasKLog<B>::V)
       Body.KLog = K;
 }
-} // namespace detail
-template <class B0, class B1> void launchTileV(int K, hipStream_t S, const B0 &A0, int N0, const B1 &A1, int N1) {
-   static_assert(BodyMaxW<B0>::V == BodyMaxW<B1>::V, "launchTileV: bodies must agree on the levels per thread");
-   static_assert(sizeof(B0) + sizeof(B1) + sizeof(SweepPlan) <= 3900, "launchTileV: kernel arguments exceed 4 KiB");
-   B0 X0 = A0;
-   B1 X1 = A1;
-   detail::prepBody(X0, K), detail::prepBody(X1, K);
-   const int Ns[2] = {N0 > 0 ? N0 : 0, N1 > 0 ? N1 : 0};
-   const int Ty0 = bodyMaxTY(X0), Ty1 = bodyMaxTY(X1);
-   Geom G = makeGeom(Ns[0] + Ns[1], K, BodyMaxW<B0>::V, X0.K, Ty0 > Ty1 ? Ty0 : Ty1);
+/// the bodies by value (the launch's own copies, which get pitch, level count and wavefront count), their lengths in NIn
+template <class B0, class... Bs>
+void launchSweeps(int K, hipStream_t S, const int (&NIn)[1 + sizeof...(Bs)], B0 X0, Bs... Xs) {
+   constexpr int NB = 1 + sizeof...(Bs);
+   static_assert(NB >= 2 && NB <= MaxSweeps, "launchTileV: two to MaxSweeps sweeps");
+   static_assert(((BodyMaxW<B0>::V == BodyMaxW<Bs>::V) && ...), "launchTileV: bodies must agree on the levels per thread");
+   static_assert(sizeof(B0) + (sizeof(Bs) + ...) + sizeof(SweepPlan) <= 3900, "launchTileV: kernel arguments exceed 4 KiB");
+   prepBody(X0, K), (prepBody(Xs, K), ...);
+   int NSum = 0;
+   for (int I = 0; I < NB; ++I)
+      NSum += NIn[I] > 0 ? NIn[I] : 0;
+   Geom G = makeGeom(NSum, K, BodyMaxW<B0>::V, X0.K, std::max({bodyMaxTY(X0), bodyMaxTY(Xs)...}));
    SweepPlan Pl{};
    Pl.TileStart[0] = 0;
-   for (int I = 0; I < 2; ++I) {
-      Pl.N[I]             = Ns[I];
-      Pl.TileStart[I + 1] = Pl.TileStart[I] + (Ns[I] + G.Tile - 1) / G.Tile;
+   for (int I = 0; I < NB; ++I) {
+      Pl.N[I]             = NIn[I] > 0 ? NIn[I] : 0;
+      Pl.TileStart[I + 1] = Pl.TileStart[I] + (Pl.N[I] + G.Tile - 1) / G.Tile;
    }
-   if (Pl.TileStart[2] == 0)
+   if (Pl.TileStart[NB] == 0)
       return;
-   setWaves(X0, G), setWaves(X1, G);
-   const size_t L0 = X0.ldsBytes(G.Tile), L1 = X1.ldsBytes(G.Tile), Lds = L0 > L1 ? L0 : L1;
-   const dim3 Grid(Pl.TileStart[2], G.TailSplit > 1 ? 1 : G.Grid.y, 1);
+   setWaves(X0, G), (setWaves(Xs, G), ...);
+   const size_t Lds = std::max({(size_t)X0.ldsBytes(G.Tile), (size_t)Xs.ldsBytes(G.Tile)...});
+   const dim3 Grid(Pl.TileStart[NB], G.TailSplit > 1 ? 1 : G.Grid.y, 1);
    if constexpr (BodyMaxW<B0>::V >= 2) {
       if (G.W == 2) {
-         hipLaunchKernelGGL((tileKernelV<dv2, B0, B1>), Grid, G.Block, Lds, S, Pl, G.KV, G.Tile, X0, X1);
+         hipLaunchKernelGGL((tileKernelV<dv2, B0, Bs...>), Grid, G.Block, Lds, S, Pl, G.KV, G.Tile, X0, Xs...);
          HIP_CHECK(hipGetLastError());
          return;
       }
    }
-   hipLaunchKernelGGL((tileKernelV<double, B0, B1>), Grid, G.Block, Lds, S, Pl, G.KV, G.Tile, X0, X1);
+   hipLaunchKernelGGL((tileKernelV<double, B0, Bs...>), Grid, G.Block, Lds, S, Pl, G.KV, G.Tile, X0, Xs...);
    HIP_CHECK(hipGetLastError());
 }
-template <class B0, class B1, class B2>
-void launchTileV(int K, hipStream_t S, const B0 &A0, int N0, const B1 &A1, int N1, const B2 &A2, int N2) {
-   static_assert(BodyMaxW<B0>::V == BodyMaxW<B1>::V && BodyMaxW<B0>::V == BodyMaxW<B2>::V,
-                 "launchTileV: bodies must agree on the levels per thread");
-   static_assert(sizeof(B0) + sizeof(B1) + sizeof(B2) + sizeof(SweepPlan) <= 3900, "launchTileV: kernel arguments exceed 4 KiB");
-   B0 X0 = A0;
-   B1 X1 = A1;
-   B2 X2 = A2;
-   detail::prepBody(X0, K), detail::prepBody(X1, K), detail::prepBody(X2, K);
-   const int Ns[3] = {N0 > 0 ? N0 : 0, N1 > 0 ? N1 : 0, N2 > 0 ? N2 : 0};
-   int Ty = bodyMaxTY(X0);
-   Ty     = bodyMaxTY(X1) > Ty ? bodyMaxTY(X1) : Ty;
-   Ty     = bodyMaxTY(X2) > Ty ? bodyMaxTY(X2) : Ty;
-   Geom G = makeGeom(Ns[0] + Ns[1] + Ns[2], K, BodyMaxW<B0>::V, X0.K, Ty);
-   SweepPlan Pl{};
-   Pl.TileStart[0] = 0;
-   for (int I = 0; I < 3; ++I) {
-      Pl.N[I]             = Ns[I];
-      Pl.TileStart[I + 1] = Pl.TileStart[I] + (Ns[I] + G.Tile - 1) / G.Tile;
-   }
-   if (Pl.TileStart[3] == 0)
-      return;
-   setWaves(X0, G), setWaves(X1, G), setWaves(X2, G);
-   size_t Lds = X0.ldsBytes(G.Tile);
-   Lds        = X1.ldsBytes(G.Tile) > Lds ? X1.ldsBytes(G.Tile) : Lds;
-   Lds        = X2.ldsBytes(G.Tile) > Lds ? X2.ldsBytes(G.Tile) : Lds;
-   const dim3 Grid(Pl.TileStart[3], G.TailSplit > 1 ? 1 : G.Grid.y, 1);
-   if constexpr (BodyMaxW<B0>::V >= 2) {
-      if (G.W == 2) {
-         hipLaunchKernelGGL((tileKernelV<dv2, B0, B1, B2>), Grid, G.Block, Lds, S, Pl, G.KV, G.Tile, X0, X1, X2);
-         HIP_CHECK(hipGetLastError());
-         return;
-      }
-   }
-   hipLaunchKernelGGL((tileKernelV<double, B0, B1, B2>), Grid, G.Block, Lds, S, Pl, G.KV, G.Tile, X0, X1, X2);
-   HIP_CHECK(hipGetLastError());
+/// Args = (body, n) pairs: the bodies are the even elements, their lengths the odd ones
+template <class Tup, size_t... I> void launchTilePairs(int K, hipStream_t S, const Tup &Args, std::index_sequence<I...>) {
+   const int Ns[] = {std::get<2 * I + 1>(Args)...};
+   launchSweeps(K, S, Ns, std::get<2 * I>(Args)...);
+}
+} // namespace detail
+template <class... Args> void launchTileV(int K, hipStream_t S, const Args &...BodyNPairs) {
+   static_assert(sizeof...(Args) % 2 == 0, "launchTileV: (body, n) pairs");
+   detail::launchTilePairs(K, S, std::forward_as_tuple(BodyNPairs...), std::make_index_sequence<sizeof...(Args) / 2>{});
 }
 
 } // namespace OMEGA

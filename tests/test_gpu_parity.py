@@ -214,6 +214,44 @@ def test_generic_flags_follow_the_environment():
         assert P.mesh.get_int(flag) == want, flag
 
 
+_L1, _L2 = "FusedCellL1PVBody", "Del2CellRingBody+Del2VertexSelBody"
+STRUCTURES = [
+    # (case, the fused RHS's kernels of a plain evaluation, slot by slot without the empty ones)
+    # hexagons only: merged level 1, paired level 2, level 3 in one kernel
+    ((16, 16, 30e3, 5, 2, {}), [_L1, _L2, "CellPVFinalTracerBody"]),
+    # 12 pentagons: side 0 inside the level-1 kernel; their final pass rides in the level-3 launch, named in its own slot
+    (("ico3", 0, 0, 12, 2, {}), [_L1, _L2, "CellPVFinalBody (rarer valences)", "CellPVFinalTracerBody"]),
+    # narrow tables: the heptagons on list launches inside the same kernels
+    (("fib1500", 0, 0, 10, 2, {}), [_L1, _L2, "CellPVFinalBody (rarer valences)", "CellPVFinalTracerBody"]),
+    # stored 8 wide, tables compacted to 6: as ico3
+    (("ico3pad8", 0, 0, 6, 1, {}), [_L1, _L2, "CellPVFinalBody (rarer valences)", "CellPVFinalTracerBody"]),
+    # cells outside the ring tables ride along as lists: the structure of the hexagon mesh
+    (("hex32x24_perm3", 0, 0, 8, 2, {}), [_L1, _L2, "CellPVFinalTracerBody"]),
+    # no tracers: the velocity sweep alone
+    (("ico3", 0, 0, 12, 0, {}), [_L1, _L2, "CellPVFinalBody"]),
+]
+
+
+@pytest.mark.parametrize("case,want", STRUCTURES, ids=[f"{c[0]}_NT{c[4]}" for c, _ in STRUCTURES])
+def test_fused_structure_names(case, want):
+    """Which kernel structure of the fused RHS each mesh class takes (the names the kernel timer records for one plain
+    evaluation).  Bit-exact parity cannot see a mesh rerouted to a slower structure; this can.  Under a non-default
+    structure option (the child runs of tests/test_00_multirank_gpu.py) the lists do not apply."""
+    defaults = {"MergeL1": 1, "Pair": 1, "ForceGeneric": 0, "KeepMaxEdges": 0, "NarrowTables": 1}
+    if any(oa.get_option(k) != v for k, v in defaults.items()):
+        pytest.skip("non-default kernel-structure options: parity only")
+    P = _mk(case)
+    P.tend.set_fused(True)
+    P.tend.kernel_timing(True)
+    try:
+        P.tend.compute_all_tendencies(P.state, P.aux, P.tracers)
+        oa.device_synchronize()
+        names = [k for k, _ in P.tend.collect_kernel_times()]
+    finally:
+        P.tend.kernel_timing(False)
+    assert names == want
+
+
 def test_group_tendencies_fb_path():
     """computeThicknessTendencies / computeTracerTendencies / computeVelocityTendencies
     (the ForwardBackward stepper's calls, Tendencies.cpp:488-575)."""
