@@ -427,7 +427,8 @@ int omg_tend_device_ptr(const omg_tend *t, int which, double **dev, size_t *n);
 
 /* ---- TimeStepper (O/src/timeStepping/TimeStepper.h:57-139 create/doStep;
  *      RungeKutta4Stepper.cpp:68-137, RungeKutta2Stepper.cpp:27-73, ForwardBackwardStepper.cpp:27-82).
- *      type: "Forward-Backward" | "RungeKutta4" | "RungeKutta2" (TimeStepper.h:64-75) ---- */
+ *      type: "Forward-Backward" | "RungeKutta4" | "RungeKutta2" (TimeStepper.h:64-75), or this library's
+ *      "Split-Explicit" (omg_stepper_attach_barotropic) ---- */
 int omg_stepper_create(const char *type, double time_step_seconds, omg_tend *t, omg_aux *a, const omg_mesh *m,
                        omg_halo *halo, omg_tracers *tr, omg_stepper **out);
 int omg_stepper_destroy(omg_stepper *st);
@@ -681,7 +682,25 @@ int omg_btr_recombine(omg_btr *b, double *normal_velocity_dev, void *stream);
 /* nsub forward-backward sub-steps of dt_btr seconds on SSH and BtrVelocity under BtrForcing; BtrFluxMean is the mean
  * edge flux of the sub-steps.  Fails for nsub < 1 and a dt_btr that is not finite and positive */
 int omg_btr_subcycle(omg_btr *b, int nsub, double dt_btr, void *stream);
-/* "BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean" ([NEdgesSize]), "SSH" ([NCellsSize]), "BclVelocity"
+/* The three calls of a split-explicit step (omega_amd/csrc/BarotropicMode.h has the contract).
+ * BtrTendMean = the thickness-weighted vertical mean of velocity_tend_dev; BtrForcing = BtrTendMean less the bracket of
+ * a sub-step (Coriolis sum and surface-height gradient) at SSH and BtrVelocity as they stand */
+int omg_btr_compute_residual_forcing(omg_btr *b, const double *layer_thickness_dev, const double *velocity_tend_dev,
+                                     void *stream);
+/* velocity_out_dev = BclVelocity + BtrFluxMean/BtrThickEdge on each edge's level range, velocity_old_dev on the other
+ * levels; all [NEdgesSize][pitch] */
+int omg_btr_transport_velocity(omg_btr *b, const double *velocity_old_dev, double *velocity_out_dev, void *stream);
+/* velocity_out_dev = (BclVelocity + dt*(velocity_tend_dev - BtrTendMean)) + BtrVelocity on each edge's level range,
+ * velocity_old_dev + dt*velocity_tend_dev on the other levels; velocity_out_dev may be velocity_old_dev.  Fails for a dt
+ * that is not finite and positive */
+int omg_btr_advance_velocity(omg_btr *b, const double *velocity_old_dev, const double *velocity_tend_dev, double dt,
+                             double *velocity_out_dev, void *stream);
+/* SplitExplicitStepper::attachBarotropic (omega_amd/csrc/SplitExplicitStepper.h): required before the first
+ * omg_stepper_do_step of a "Split-Explicit" stepper, which then carries the 2-D system through nsub sub-steps of
+ * BarotropicMode per step.  Fails for any other stepper type, a null b, one of another mesh or layer count, nsub < 1 and
+ * a stepper whose halo has neighbours (the sub-cycle knows no halo exchange).  The stepper keeps a pointer to b. */
+int omg_stepper_attach_barotropic(omg_stepper *st, omg_btr *b, int nsub);
+/* "BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean", "BtrTendMean" ([NEdgesSize]), "SSH" ([NCellsSize]), "BclVelocity"
  * ([NEdgesSize][NVertLayers]); all zero at creation */
 int omg_btr_device_ptr(const omg_btr *b, const char *name, double **dev, size_t *n);
 int omg_btr_copy_to_device(omg_btr *b, const char *name, const double *host, size_t n);

@@ -1305,8 +1305,8 @@ class VertAdv(_Handle, _NamedArrays):
         return (self.mesh.NCellsSize, self.K)
 
 
-BTR_ARRAYS = {"BtrVelocity": "E", "BtrThickEdge": "E", "BtrForcing": "E", "BtrFluxMean": "E", "SSH": "C",
-              "BclVelocity": "EK"}
+BTR_ARRAYS = {"BtrVelocity": "E", "BtrThickEdge": "E", "BtrForcing": "E", "BtrFluxMean": "E", "BtrTendMean": "E",
+              "SSH": "C", "BclVelocity": "EK"}
 
 
 class BarotropicMode(_Handle, _NamedArrays):
@@ -1359,6 +1359,22 @@ class BarotropicMode(_Handle, _NamedArrays):
 
     def subcycle(self, nsub: int, dt_btr: float, stream=None):
         _chk(lib().omg_btr_subcycle(self.h, int(nsub), C.c_double(dt_btr), _sh(stream)))
+
+    def compute_residual_forcing(self, layer_thickness, velocity_tend, stream=None):
+        """BtrTendMean (the vertical mean of velocity_tend) and BtrForcing = BtrTendMean less the sub-step's bracket at
+        SSH and BtrVelocity as they stand"""
+        self._edge_call("omg_btr_compute_residual_forcing", layer_thickness, velocity_tend, stream=stream)
+
+    def transport_velocity(self, velocity_old, velocity_out, stream=None):
+        """velocity_out = BclVelocity + BtrFluxMean/BtrThickEdge on each edge's level range, velocity_old elsewhere;
+        device addresses of [NEdgesSize][level_pitch(K)] doubles"""
+        _chk(lib().omg_btr_transport_velocity(self.h, C.c_void_p(velocity_old), C.c_void_p(velocity_out), _sh(stream)))
+
+    def advance_velocity(self, velocity_old, velocity_tend, dt: float, velocity_out, stream=None):
+        """velocity_out = (BclVelocity + dt*(velocity_tend - BtrTendMean)) + BtrVelocity on each edge's level range,
+        velocity_old + dt*velocity_tend elsewhere; device addresses, velocity_out may be velocity_old"""
+        _chk(lib().omg_btr_advance_velocity(self.h, C.c_void_p(velocity_old), C.c_void_p(velocity_tend), C.c_double(dt),
+                                            C.c_void_p(velocity_out), _sh(stream)))
 
     def _shape(self, name):
         s = BTR_ARRAYS.get(name, "E")  # (an unknown name: the library says so)
@@ -1510,6 +1526,12 @@ class TimeStepper(_Handle):
         levels rotate (None detaches); raises for another mesh, layer or tracer count and for a halo with neighbours."""
         _chk(lib().omg_stepper_attach_vert_mix(self.h, vert_mix_step.h if vert_mix_step is not None else None))
         self._vert_mix_step = vert_mix_step  # the library keeps a pointer to it
+
+    def attach_barotropic(self, btr: "BarotropicMode", nsub: int):
+        """SplitExplicitStepper::attachBarotropic: required before the first do_step of a "Split-Explicit" stepper;
+        raises on any other kind, for another mesh or layer count, nsub < 1 and a halo with neighbours."""
+        _chk(lib().omg_stepper_attach_barotropic(self.h, btr.h if btr is not None else None, int(nsub)))
+        self._barotropic = btr  # the library keeps a pointer to it
 
     def do_step(self, state: OceanState, stream=None):
         _chk(lib().omg_stepper_do_step(self.h, state.h, _sh(stream)))

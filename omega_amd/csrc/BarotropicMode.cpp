@@ -41,10 +41,11 @@ BarotropicMode::BarotropicMode(const std::string &Name_, const HorzMesh *Mesh_, 
    BtrThickEdge = Array1DReal("BtrThickEdge", NE);
    BtrForcing   = Array1DReal("BtrForcing", NE);
    BtrFluxMean  = Array1DReal("BtrFluxMean", NE);
+   BtrTendMean  = Array1DReal("BtrTendMean", NE);
    SSH          = Array1DReal("SSH", NC);
    BclVelocity  = Array2DReal::levels("BclVelocity", NE, NVertLayers);
    BtrVelocityH = HostArrayReal(NE), BtrThickEdgeH = HostArrayReal(NE), BtrForcingH = HostArrayReal(NE);
-   BtrFluxMeanH = HostArrayReal(NE), SSHH = HostArrayReal(NC), BclVelocityH = HostArrayReal(NE, NVertLayers);
+   BtrFluxMeanH = HostArrayReal(NE), BtrTendMeanH = HostArrayReal(NE), SSHH = HostArrayReal(NC), BclVelocityH = HostArrayReal(NE, NVertLayers);
    SSHNext         = Array1DReal("SSHNext", NC);
    BtrVelocityNext = Array1DReal("BtrVelocityNext", NE);
 
@@ -88,7 +89,7 @@ void BarotropicMode::columnLaunch(const Array2DReal &H, const Array2DReal *Field
    requireLevelArray("BarotropicMode", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
    if (Field)
       requireLevelArray("BarotropicMode", *Field, Mesh->NEdgesSize, NVertLayers,
-                        EdgeMode == BtrEdgeForcing ? "the velocity tendency" : "NormalVelocity");
+                        EdgeMode == BtrEdgeSplit ? "NormalVelocity" : "the velocity tendency");
    BtrColumnArgs A;
    A.NEdgesAll = Mesh->NEdgesAll, A.NCellsAll = Mesh->NCellsAll, A.NCellsSize = Mesh->NCellsSize, A.K = NVertLayers;
    A.CellsOnEdge     = Mesh->CellsOnEdge.Ptr;
@@ -96,7 +97,8 @@ void BarotropicMode::columnLaunch(const Array2DReal &H, const Array2DReal *Field
    A.MinLayerCell = VCoord->MinLayerCell.Ptr, A.MaxLayerCell = VCoord->MaxLayerCell.Ptr;
    A.BottomDepth = VCoord->BottomDepth.Ptr;
    A.LayerThick = H.Ptr, A.EdgeField = Field ? Field->Ptr : nullptr;
-   A.BtrThickEdge = BtrThickEdge.Ptr, A.BtrOut = EdgeMode == BtrEdgeForcing ? BtrForcing.Ptr : BtrVelocity.Ptr;
+   A.BtrThickEdge = BtrThickEdge.Ptr;
+   A.BtrOut = EdgeMode == BtrEdgeForcing ? BtrForcing.Ptr : EdgeMode == BtrEdgeTendMean ? BtrTendMean.Ptr : BtrVelocity.Ptr;
    A.BclVelocity = BclVelocity.Ptr, A.SSH = SSH.Ptr;
    launchBtrColumn(A, (BtrEdgeMode)EdgeMode, Cells, S);
 }
@@ -121,14 +123,62 @@ void BarotropicMode::splitVelocityAndSSH(const Array2DReal &H, const Array2DReal
    columnLaunch(H, &U, BtrEdgeSplit, true, S);
 }
 
-void BarotropicMode::recombine(const Array2DReal &U, hipStream_t S) const {
-   requireLevelArray("BarotropicMode", U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
-   Pacer::Range Timer("BarotropicMode:recombine", 1);
-   BtrRecombineArgs A;
-   A.NEdgesAll = Mesh->NEdgesAll, A.K = NVertLayers;
+void BarotropicMode::levelLaunch(int Op, const Array2DReal *VelOld, const Array2DReal *VelTend, Real Dt,
+                                 const Array2DReal &VelOut, hipStream_t S) const {
+   const char *OutName = Op == BtrLevelRecombine ? "NormalVelocity" : "the velocity written";
+   requireLevelArray("BarotropicMode", VelOut, Mesh->NEdgesSize, NVertLayers, OutName);
+   if (VelOld)
+      requireLevelArray("BarotropicMode", *VelOld, Mesh->NEdgesSize, NVertLayers, "the old velocity");
+   if (VelTend)
+      requireLevelArray("BarotropicMode", *VelTend, Mesh->NEdgesSize, NVertLayers, "the velocity tendency");
+   BtrLevelArgs A;
+   A.NEdgesAll = Mesh->NEdgesAll, A.K = NVertLayers, A.Dt = Dt;
    A.MinLayerEdgeBot = VCoord->MinLayerEdgeBot.Ptr, A.MaxLayerEdgeTop = VCoord->MaxLayerEdgeTop.Ptr;
-   A.BtrVelocity = BtrVelocity.Ptr, A.BclVelocity = BclVelocity.Ptr, A.NormalVelocity = U.Ptr;
-   launchBtrRecombine(A, S);
+   A.BtrVelocity = BtrVelocity.Ptr, A.BtrFluxMean = BtrFluxMean.Ptr, A.BtrThickEdge = BtrThickEdge.Ptr;
+   A.BtrTendMean = BtrTendMean.Ptr, A.BclVelocity = BclVelocity.Ptr;
+   A.VelOld = VelOld ? VelOld->Ptr : nullptr, A.VelTend = VelTend ? VelTend->Ptr : nullptr, A.VelOut = VelOut.Ptr;
+   launchBtrLevels(A, (BtrLevelOp)Op, S);
+}
+
+void BarotropicMode::recombine(const Array2DReal &U, hipStream_t S) const {
+   Pacer::Range Timer("BarotropicMode:recombine", 1);
+   levelLaunch(BtrLevelRecombine, nullptr, nullptr, 0.0, U, S);
+}
+
+void BarotropicMode::transportVelocity(const Array2DReal &UOld, const Array2DReal &UOut, hipStream_t S) const {
+   Pacer::Range Timer("BarotropicMode:transportVelocity", 1);
+   levelLaunch(BtrLevelTransport, &UOld, nullptr, 0.0, UOut, S);
+}
+
+void BarotropicMode::advanceVelocity(const Array2DReal &UOld, const Array2DReal &VelTend, Real Dt, const Array2DReal &UOut,
+                                     hipStream_t S) const {
+   OMEGA_REQUIRE(std::isfinite(Dt) && Dt > 0.0,
+                 "BarotropicMode: advanceVelocity: Dt = " + std::to_string(Dt) + " is not a finite, positive time step");
+   Pacer::Range Timer("BarotropicMode:advanceVelocity", 1);
+   levelLaunch(BtrLevelAdvance, &UOld, &VelTend, Dt, UOut, S);
+}
+
+/// the mesh tables and constants of the sub-step kernels; the fields are the caller's to set
+struct BarotropicMode::SubTables : BtrSubArgs {
+   explicit SubTables(const BarotropicMode &B) {
+      const HorzMesh *M = B.Mesh;
+      const MeshView &V = M->view();
+      NCellsAll = M->NCellsAll, NEdgesAll = M->NEdgesAll, MaxEdges = M->MaxEdges, MaxEdges2 = M->MaxEdges2;
+      Gravity      = B.Config.Gravity;
+      NEdgesOnCell = M->NEdgesOnCell.Ptr, EdgeSlot = B.EdgeSlot.Ptr, NbrSlot = B.NbrSlot.Ptr;
+      DvSignSlot = B.DvSignSlot.Ptr, InvAreaCell = V.InvAreaCell;
+      CellsOnEdge = M->CellsOnEdge.Ptr, EdgeMask = M->EdgeMask1D.Ptr, InvDcEdge = V.InvDcEdge;
+      NEdgesOnEdge = M->NEdgesOnEdge.Ptr, EoESlot = B.EoESlot.Ptr, CorSlot = B.CorSlot.Ptr;
+      BottomDepth = B.VCoord->BottomDepth.Ptr;
+   }
+};
+
+void BarotropicMode::computeResidualForcing(const Array2DReal &H, const Array2DReal &VelTend, hipStream_t S) const {
+   Pacer::Range Timer("BarotropicMode:computeResidualForcing", 1);
+   columnLaunch(H, &VelTend, BtrEdgeTendMean, false, S);
+   SubTables A(*this);
+   A.SSH = SSH.Ptr, A.Vel = BtrVelocity.Ptr;
+   launchBtrResidual(A, BtrTendMean.Ptr, BtrForcing.Ptr, S);
 }
 
 void BarotropicMode::subcycle(int NSub, Real DtBtr, hipStream_t S) const {
@@ -136,15 +186,8 @@ void BarotropicMode::subcycle(int NSub, Real DtBtr, hipStream_t S) const {
    OMEGA_REQUIRE(std::isfinite(DtBtr) && DtBtr > 0.0,
                  "BarotropicMode: DtBtr = " + std::to_string(DtBtr) + " is not a finite, positive time step");
    Pacer::Range Timer("BarotropicMode:subcycle", 1);
-   const MeshView &V = Mesh->view();
-   BtrSubArgs A;
-   A.NCellsAll = Mesh->NCellsAll, A.NEdgesAll = Mesh->NEdgesAll, A.MaxEdges = Mesh->MaxEdges, A.MaxEdges2 = Mesh->MaxEdges2;
-   A.Dt = DtBtr, A.Gravity = Config.Gravity;
-   A.NEdgesOnCell = Mesh->NEdgesOnCell.Ptr, A.EdgeSlot = EdgeSlot.Ptr, A.NbrSlot = NbrSlot.Ptr;
-   A.DvSignSlot = DvSignSlot.Ptr, A.InvAreaCell = V.InvAreaCell;
-   A.CellsOnEdge = Mesh->CellsOnEdge.Ptr, A.EdgeMask = Mesh->EdgeMask1D.Ptr, A.InvDcEdge = V.InvDcEdge;
-   A.NEdgesOnEdge = Mesh->NEdgesOnEdge.Ptr, A.EoESlot = EoESlot.Ptr, A.CorSlot = CorSlot.Ptr;
-   A.BottomDepth = VCoord->BottomDepth.Ptr, A.Forcing = BtrForcing.Ptr, A.FluxSum = BtrFluxMean.Ptr;
+   SubTables A(*this);
+   A.Dt = DtBtr, A.Forcing = BtrForcing.Ptr, A.FluxSum = BtrFluxMean.Ptr;
    deviceFill0(BtrFluxMean.Ptr, (size_t)Mesh->NEdgesAll * sizeof(Real), S);
    // sub-step I reads one half of each double buffer and writes the other; an odd count ends in the second halves
    Real *Eta[2] = {SSH.Ptr, SSHNext.Ptr}, *Vel[2] = {BtrVelocity.Ptr, BtrVelocityNext.Ptr};
@@ -167,6 +210,7 @@ void BarotropicMode::copyToHost() {
    OMEGA::copyToHost(BtrThickEdgeH.data(), BtrThickEdge);
    OMEGA::copyToHost(BtrForcingH.data(), BtrForcing);
    OMEGA::copyToHost(BtrFluxMeanH.data(), BtrFluxMean);
+   OMEGA::copyToHost(BtrTendMeanH.data(), BtrTendMean);
    OMEGA::copyToHost(SSHH.data(), SSH);
    OMEGA::copyToHost(BclVelocityH.data(), BclVelocity);
 }

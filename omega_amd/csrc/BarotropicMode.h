@@ -3,8 +3,8 @@
 // (sea-surface height, barotropic velocity) that carries the external gravity wave.  The reference names the
 // forward-backward scheme for "the barotropic mode of layered models" (components/omega/doc/design/TimeStepping.md)
 // and lists the split baroclinic-barotropic step on its roadmap (doc/design/OmegaV1GoverningEqns.md, section 1); it has
-// no code for either: the contract below is this library's.  A split-explicit TimeStepper that calls this class, and
-// sub-cycling across ranks, are not part of it.
+// no code for either: the contract below is this library's.  SplitExplicitStepper (SplitExplicitStepper.h) is the time
+// stepper built on this class; sub-cycling across ranks is not part of it.
 //
 // Numerical contract (FP64, -ffp-contract=off, IEEE divisions, every chain in the order written; a NumPy restatement in
 // the same order is bit-identical, tests/barotropic_reference.py).  c0, c1 = CellsOnEdge[e]; Lo .. Hi =
@@ -54,6 +54,28 @@
 //    a culled mesh leaves in place) is skipped.  EdgeMask is 0.0 or 1.0.  Every cell of the mesh is treated as wet, with
 //    the water depth SSH + BottomDepth: columns that are dry by their layer range are the caller's to keep out.
 //
+//  The three calls of a split-explicit step (SplitExplicitStepper.h gives the sequence):
+//
+//  computeResidualForcing(h, VelTend): the two sums of computeForcing, G = SumHT/Sum (VelTend[e][Lo] on a range of one
+//    level, 0 on an empty range); BtrTendMean[e] = G; then, with SSH and BtrVelocity as they stand,
+//      Cor = 0;  for j < NEdgesOnEdge[e] in slot order (holes skipped):  Cor = Cor + CorWeight[e][j]*BtrVelocity[EdgesOnEdge[e][j]]
+//      R = EdgeMask[e]*(Cor - Gravity*((SSH[c1] - SSH[c0])*InvDcEdge[e]))
+//      BtrForcing[e] = G - R
+//    An edge with EdgeMask[e] == 0 reads no cell and no neighbour: BtrForcing[e] = G.  R is the bracket a sub-step
+//    evaluates, here at the fields the sub-cycle starts from: the forcing is the mean 3-D tendency with what the
+//    sub-cycle computes itself taken out, whatever pressure force or Coriolis form the 3-D tendency holds, and a state
+//    whose 3-D velocity tendency and flux divergence vanish is held by subcycle bit for bit.  Two launches.
+//
+//  transportVelocity(uOld, uOut):  Q = BtrFluxMean[e]/BtrThickEdge[e] (once per edge);
+//      uOut[e][K] = BclVelocity[e][K] + Q  for K in Lo .. Hi;   uOut[e][K] = uOld[e][K]  for the other K < NVertLayers.
+//    The barotropic part of the transporting velocity is the sub-cycle's time-mean flux over the edge's thickness: the
+//    column sum of hE*uOut is BtrFluxMean up to rounding (tests/test_split_explicit.py has the bound).
+//
+//  advanceVelocity(uOld, VelTend, Dt, uOut):
+//      uOut[e][K] = (BclVelocity[e][K] + Dt*(VelTend[e][K] - BtrTendMean[e])) + BtrVelocity[e]   for K in Lo .. Hi
+//      uOut[e][K] = uOld[e][K] + Dt*VelTend[e][K]    for the other K < NVertLayers (the unsplit update)
+//    uOut may be uOld.  One pass: 24 B per edge-level inside the ranges (uOld is read outside them only).
+//
 // Nothing but the stated entries is written by any call: no other level, no land column, no row >= NCellsAll /
 // NEdgesAll, not the sentinel row, not the pitch padding.  Halo cells and edges are swept like owned ones; the class
 // knows no Halo, so after a sub-step the outermost valid halo layer is no longer valid: subcycle(NSub, .) leaves valid
@@ -90,10 +112,10 @@ class BarotropicMode : public Registry<BarotropicMode> {
    I4 NVertLayers;
    BarotropicConfig Config;
    // zero at construction
-   Array1DReal BtrVelocity, BtrThickEdge, BtrForcing, BtrFluxMean; ///< [NEdgesSize]
+   Array1DReal BtrVelocity, BtrThickEdge, BtrForcing, BtrFluxMean, BtrTendMean; ///< [NEdgesSize]
    Array1DReal SSH;                                                ///< [NCellsSize]
    Array2DReal BclVelocity;                                        ///< [NEdgesSize][levelPitch(K)]
-   HostArrayReal BtrVelocityH, BtrThickEdgeH, BtrForcingH, BtrFluxMeanH, SSHH, BclVelocityH;
+   HostArrayReal BtrVelocityH, BtrThickEdgeH, BtrForcingH, BtrFluxMeanH, BtrTendMeanH, SSHH, BclVelocityH;
    /// [NEdgesSize][MaxEdges2], built in the constructor; the device holds it slot-major for the edge kernel
    HostArrayReal CorWeightH;
 
@@ -104,6 +126,11 @@ class BarotropicMode : public Registry<BarotropicMode> {
    void recombine(const Array2DReal &NormalVelocity, hipStream_t S) const;
    /// Refuses NSub < 1 and a DtBtr that is not finite and positive.  At most two launches per sub-step.
    void subcycle(int NSub, Real DtBtr, hipStream_t S) const;
+   void computeResidualForcing(const Array2DReal &LayerThickness, const Array2DReal &VelocityTend, hipStream_t S) const;
+   void transportVelocity(const Array2DReal &VelocityOld, const Array2DReal &VelocityOut, hipStream_t S) const;
+   /// Refuses a Dt that is not finite and positive.
+   void advanceVelocity(const Array2DReal &VelocityOld, const Array2DReal &VelocityTend, Real Dt,
+                        const Array2DReal &VelocityOut, hipStream_t S) const;
 
    // ---- the reference's style of signature: on this object's `Stream` (default: the null stream)
    hipStream_t Stream = nullptr;
@@ -119,8 +146,18 @@ class BarotropicMode : public Registry<BarotropicMode> {
    }
    void recombine(const Array2DReal &NormalVelocity) const { recombine(NormalVelocity, Stream); }
    void subcycle(int NSub, Real DtBtr) const { subcycle(NSub, DtBtr, Stream); }
+   void computeResidualForcing(const Array2DReal &LayerThickness, const Array2DReal &VelocityTend) const {
+      computeResidualForcing(LayerThickness, VelocityTend, Stream);
+   }
+   void transportVelocity(const Array2DReal &VelocityOld, const Array2DReal &VelocityOut) const {
+      transportVelocity(VelocityOld, VelocityOut, Stream);
+   }
+   void advanceVelocity(const Array2DReal &VelocityOld, const Array2DReal &VelocityTend, Real Dt,
+                        const Array2DReal &VelocityOut) const {
+      advanceVelocity(VelocityOld, VelocityTend, Dt, VelocityOut, Stream);
+   }
 
-   void copyToHost(); ///< the six arrays -> their host mirrors (synchronises the device)
+   void copyToHost(); ///< the seven arrays -> their host mirrors (synchronises the device)
 
    const HorzMesh *Mesh;
    const VertCoord *VCoord;
@@ -128,6 +165,9 @@ class BarotropicMode : public Registry<BarotropicMode> {
 
  private:
    void columnLaunch(const Array2DReal &H, const Array2DReal *Field, int EdgeMode, bool Cells, hipStream_t S) const;
+   void levelLaunch(int Op, const Array2DReal *VelOld, const Array2DReal *VelTend, Real Dt, const Array2DReal &VelOut,
+                    hipStream_t S) const;
+   struct SubTables; ///< what the sub-step kernels read of the mesh (BarotropicMode.cpp)
    // the second halves of the double buffers, and the slot-major tables of the sub-step kernels
    Array1DReal SSHNext, BtrVelocityNext, DvSignSlot, CorSlot;
    Array1DI4 EdgeSlot, NbrSlot, EoESlot;

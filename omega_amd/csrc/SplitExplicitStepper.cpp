@@ -1,0 +1,53 @@
+// SplitExplicitStepper.cpp -- see SplitExplicitStepper.h.
+#include "SplitExplicitStepper.h"
+
+namespace OMEGA {
+
+void SplitExplicitStepper::attachBarotropic(BarotropicMode *B, int N) {
+   OMEGA_REQUIRE(Tend && Mesh && Trc, "SplitExplicitStepper::attachBarotropic: attachData first");
+   OMEGA_REQUIRE(B != nullptr, "SplitExplicitStepper::attachBarotropic: the BarotropicMode is NULL");
+   OMEGA_REQUIRE(B->Mesh == Mesh && B->NVertLayers == Tend->LayerThicknessTend.Ext[1],
+                 "SplitExplicitStepper::attachBarotropic: the BarotropicMode was built for another mesh or layer count");
+   OMEGA_REQUIRE(N >= 1, "SplitExplicitStepper::attachBarotropic: NSub = " + std::to_string(N) +
+                             " is not a number of sub-steps (>= 1)");
+   OMEGA_REQUIRE(!MeshHalo || MeshHalo->NNghbr == 0,
+                 "SplitExplicitStepper::attachBarotropic: this stepper's halo has neighbours: BarotropicMode knows no "
+                 "Halo, and more sub-steps than the halo is wide need an exchange per sub-step, which is not built");
+   Btr  = B;
+   NSub = N;
+}
+
+void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
+   OMEGA_REQUIRE(Btr != nullptr, "Split-Explicit doStep: no BarotropicMode is attached: attachBarotropic first");
+   requireHealthyWire();
+   const int CurLevel = 0, NextLevel = 1;
+   Array3DReal CurTracerArray, NextTracerArray;
+   OMEGA_REQUIRE(Trc->getAll(CurTracerArray, CurLevel) == 0 && Trc->getAll(NextTracerArray, NextLevel) == 0,
+                 "Split-Explicit doStep: error retrieving tracers");
+   Array2DReal HCur, UCur, UNext;
+   OMEGA_REQUIRE(State->getLayerThickness(HCur, CurLevel) == 0 && State->getNormalVelocity(UCur, CurLevel) == 0 &&
+                     State->getNormalVelocity(UNext, NextLevel) == 0,
+                 "Split-Explicit doStep: error retrieving the state");
+   const R8 Dt = coeff(1.0);
+   const R8 T0 = simTime();
+   // R^{n} = RHS(u^{n}, h^{n}, phi^{n}, t^{n}); its velocity part is kept
+   Tend->ModelTime = T0;
+   Tend->computeAllTendencies(State, AuxState, CurTracerArray, CurLevel, CurLevel, S);
+   // the 2-D system over the step, forced by the mean of R_u^{n} less what the sub-steps compute themselves
+   Btr->splitVelocityAndSSH(HCur, UCur, S);
+   Btr->computeResidualForcing(HCur, Tend->NormalVelocityTend, S);
+   Btr->subcycle(NSub, Dt / (R8)NSub, S);
+   // h^{n+1} and phi^{n+1} by the transporting velocity: baroclinic u^{n} + the sub-cycle's mean flux over the thickness
+   Btr->transportVelocity(UCur, UNext, S);
+   Tend->computeThicknessTendencies(State, AuxState, CurLevel, NextLevel, S);
+   updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
+   Tend->computeTracerTendencies(State, AuxState, CurTracerArray, CurLevel, NextLevel, S);
+   updateTracersByTend(NextTracerArray, CurTracerArray, State, NextLevel, State, CurLevel, Dt, S);
+   // u^{n+1} = (baroclinic u^{n} + Dt*(R_u^{n} - its mean)) + the barotropic velocity the sub-cycle ended with
+   Btr->advanceVelocity(UCur, Tend->NormalVelocityTend, Dt, UNext, S);
+   mixNewLevel(State, S);
+   updateTimeLevels(State, S);
+   ++NStepsDone;
+}
+
+} // namespace OMEGA

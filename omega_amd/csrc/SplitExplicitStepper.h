@@ -1,0 +1,57 @@
+// SplitExplicitStepper.h -- the split-explicit time stepper: one evaluation of the 3-D right-hand side per long step, with
+// the fast 2-D system (sea-surface height, barotropic velocity) carried through the step by BarotropicMode::subcycle.
+// The reference names the scheme (components/omega/doc/design/TimeStepping.md, OmegaV1GoverningEqns.md section 1) and
+// has no code for it: the sequence below is this library's, as BarotropicMode's contract is.  DESIGN.md section 4.7.
+//
+// One step (Cur = 0, Next = 1, Dt = coeff(1.0), DtBtr = Dt/NSub), everything on the step's stream:
+//   1. Tend->ModelTime = T0;  Tend->computeAllTendencies(State, AuxState, CurTracers, Cur, Cur)
+//      (the fused path; an attached PressureGrad / VertAdv gets its column pass and its ordering from it).  Only
+//      NormalVelocityTend is kept.
+//   2. Btr->splitVelocityAndSSH(h[Cur], u[Cur])
+//   3. Btr->computeResidualForcing(h[Cur], NormalVelocityTend)
+//   4. Btr->subcycle(NSub, DtBtr)
+//   5. Btr->transportVelocity(u[Cur], u[Next])     (the velocity slot of the new level holds the transporting velocity)
+//   6. Tend->computeThicknessTendencies(State, AuxState, Cur, Next);  updateThicknessByTend(State, Next, State, Cur, Dt)
+//   7. Tend->computeTracerTendencies(State, AuxState, CurTracers, Cur, Next);
+//      updateTracersByTend(NextTracers, CurTracers, State, Next, State, Cur, Dt)
+//      (an attached VertAdv takes its transport from step 6, as Tendencies.h documents for the group methods)
+//   8. Btr->advanceVelocity(u[Cur], NormalVelocityTend, Dt, u[Next])
+//   9. mixNewLevel, updateTimeLevels, ++NStepsDone
+// Steps 6 and 7 leave NormalVelocityTend as step 1 wrote it: the two group methods write LayerThicknessTend, TracerTend
+// and the auxiliary state only (Tendencies.cpp), so step 8 needs no copy of it.  A custom thickness hook that wrote the
+// velocity tendency would break this; the hooks are handed their own array.
+//
+// The result equals these calls made one by one through the public interface, bit for bit.  A step creates no device
+// buffer, stream or event and captures nothing into a graph.  The thickness and tracer halves of step 1 are computed and
+// discarded: a velocity-only fused evaluation is not built (DESIGN.md section 4.7 has the cost).
+//
+// One rank only: BarotropicMode knows no Halo, and more sub-steps than the halo is wide need an exchange per sub-step;
+// attachBarotropic refuses a stepper whose Halo has neighbours.
+#ifndef OMEGA_AMD_SPLITEXPLICITSTEPPER_H
+#define OMEGA_AMD_SPLITEXPLICITSTEPPER_H
+
+#include "BarotropicMode.h"
+#include "TimeStepper.h"
+
+namespace OMEGA {
+
+class SplitExplicitStepper : public TimeStepper {
+ public:
+   SplitExplicitStepper(const std::string &Name, R8 Dt) : TimeStepper(Name, TimeStepperType::SplitExplicit, 2, Dt) {}
+
+   /// Required before the first step (after attachData).  Refuses (OmegaError) a null BarotropicMode, one built for
+   /// another mesh or layer count, NSub < 1, and a stepper whose Halo has neighbours.  The stepper keeps the pointer.
+   void attachBarotropic(BarotropicMode *Btr, int NSub);
+   BarotropicMode *barotropic() const { return Btr; }
+   int subSteps() const { return NSub; }
+
+   void doStep(OceanState *State, hipStream_t S) override;
+   using TimeStepper::doStep;
+
+ protected:
+   BarotropicMode *Btr = nullptr;
+   int NSub            = 0;
+};
+
+} // namespace OMEGA
+#endif

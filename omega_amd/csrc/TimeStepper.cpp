@@ -1,6 +1,7 @@
 // TimeStepper.cpp -- see TimeStepper.h.
 #include "TimeStepper.h"
 #include "Pacer.h"
+#include "SplitExplicitStepper.h"
 #include "VertMixStep.h"
 
 #include <cfloat>
@@ -168,6 +169,8 @@ TimeStepperType TimeStepper::getFromStr(const std::string &In) {
       return TimeStepperType::RungeKutta4;
    if (In == "RungeKutta2")
       return TimeStepperType::RungeKutta2;
+   if (In == "Split-Explicit")
+      return TimeStepperType::SplitExplicit;
    return TimeStepperType::Invalid;
 }
 
@@ -203,6 +206,8 @@ TimeStepper *TimeStepper::make(const std::string &Name, TimeStepperType Type, R8
       return new RungeKutta4Stepper(Name, Dt);
    case TimeStepperType::RungeKutta2:
       return new RungeKutta2Stepper(Name, Dt);
+   case TimeStepperType::SplitExplicit:
+      return new SplitExplicitStepper(Name, Dt);
    default:
       OMEGA_ABORT("TimeStepper::make: unknown time stepper type");
    }

@@ -23,7 +23,8 @@ namespace OMEGA {
 
 class VertMixStep;
 
-enum class TimeStepperType { ForwardBackward, RungeKutta4, RungeKutta2, Invalid };
+/// SplitExplicit is this library's (SplitExplicitStepper.h); the other three are the reference's
+enum class TimeStepperType { ForwardBackward, RungeKutta4, RungeKutta2, SplitExplicit, Invalid };
 
 class TimeStepper {
  public:
@@ -40,7 +41,7 @@ class TimeStepper {
    static TimeStepper *getDefault() { return get("Default"); }
    static void erase(const std::string &Name);
    static void clear();
-   static TimeStepperType getFromStr(const std::string &In); ///< TimeStepper.h:64-75
+   static TimeStepperType getFromStr(const std::string &In); ///< TimeStepper.h:64-75, and "Split-Explicit"
 
    /// attach the objects the scheme works on (TimeStepper::attachData)
    /// (Trc == nullptr: the default store of the static Tracers interface, as in the reference)

@@ -25,6 +25,7 @@
 #include "VertAdv.h"
 #include "VertMixStep.h"
 #include "BarotropicMode.h"
+#include "SplitExplicitStepper.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -1908,11 +1909,45 @@ int omg_btr_subcycle(omg_btr *b, int nsub, double dt_btr, void *stream) {
    b->B->subcycle(nsub, dt_btr, (hipStream_t)stream);
    OMG_CATCH
 }
+int omg_btr_compute_residual_forcing(omg_btr *b, const double *layer_thickness, const double *velocity_tend, void *stream) {
+   OMG_TRY
+   OMG_ARG(b && layer_thickness && velocity_tend);
+   const HorzMesh *M = b->B->Mesh;
+   const int K       = b->B->NVertLayers;
+   b->B->computeResidualForcing(levelView(layer_thickness, M->NCellsSize, K), levelView(velocity_tend, M->NEdgesSize, K),
+                                (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_btr_transport_velocity(omg_btr *b, const double *velocity_old, double *velocity_out, void *stream) {
+   OMG_TRY
+   OMG_ARG(b && velocity_old && velocity_out);
+   const int NE = b->B->Mesh->NEdgesSize, K = b->B->NVertLayers;
+   b->B->transportVelocity(levelView(velocity_old, NE, K), levelView(velocity_out, NE, K), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_btr_advance_velocity(omg_btr *b, const double *velocity_old, const double *velocity_tend, double dt,
+                             double *velocity_out, void *stream) {
+   OMG_TRY
+   OMG_ARG(b && velocity_old && velocity_tend && velocity_out);
+   const int NE = b->B->Mesh->NEdgesSize, K = b->B->NVertLayers;
+   b->B->advanceVelocity(levelView(velocity_old, NE, K), levelView(velocity_tend, NE, K), dt, levelView(velocity_out, NE, K),
+                         (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_stepper_attach_barotropic(omg_stepper *st, omg_btr *b, int nsub) {
+   OMG_TRY
+   OMG_ARG(st);
+   auto *Split = dynamic_cast<SplitExplicitStepper *>(st->St.get());
+   OMEGA_REQUIRE(Split != nullptr, "TimeStepper: attachBarotropic: this stepper is not a Split-Explicit one");
+   Split->attachBarotropic(b ? b->B.get() : nullptr, nsub);
+   OMG_CATCH
+}
 static ArrRef btrLookup(const BarotropicMode &B, const char *Name) {
    return findNamed<ArrRef>({{"BtrVelocity", arrRef(B.BtrVelocity)},
                              {"BtrThickEdge", arrRef(B.BtrThickEdge)},
                              {"BtrForcing", arrRef(B.BtrForcing)},
                              {"BtrFluxMean", arrRef(B.BtrFluxMean)},
+                             {"BtrTendMean", arrRef(B.BtrTendMean)},
                              {"SSH", arrRef(B.SSH)},
                              {"BclVelocity", arrRef(B.BclVelocity)}},
                             Name, "BarotropicMode: no array named ");

@@ -9,7 +9,9 @@
 //          (odd LDS pitch: distinct banks); the baroclinic remainder is written back with the lanes along the flat run
 //          (store2).  Per edge-level: h read twice, the field once, BclVelocity written once.
 //   cells: the thickness tile staged with loadTile, one lane per column sums it.
-// Recombine: the level-row tile over edges, one lane per level pair.
+// Level-row launch (recombine, transportVelocity, advanceVelocity): the level-row tile over edges, one lane per level
+// pair; one kernel body, the operation a template parameter.  Recombine visits the runs that overlap the ranges; the
+// other two visit every run below level K, and read the old velocity only where a run leaves its range.
 //
 // Sub-step launches (2-D): one thread per cell, then one thread per edge.  All per-(element, slot) tables are
 // slot-major, so consecutive lanes read consecutive table entries; what is gathered are the 8-byte field values.  The
@@ -107,26 +109,48 @@ __global__ void __launch_bounds__(ColThreads) btrColumnKernel(BtrColumnArgs A, i
    }
 }
 
-// -------------------------------------------------------------------------------------------------------- recombine
-template <class T> __global__ void __launch_bounds__(RowBlock) btrRecombineKernel(BtrRecombineArgs A, int Pitch) {
-   __shared__ int Lo[RowTile], Hi[RowTile];
-   __shared__ Real Btr[RowTile];
+// ------------------------------------------------------------------------------------------------ level-row launch
+template <class T, int Op> __global__ void __launch_bounds__(RowBlock) btrLevelKernel(BtrLevelArgs A, int Pitch) {
+   __shared__ int Lo[RowTile], Hi[RowTile], VisLo[RowTile], VisHi[RowTile];
+   __shared__ Real Btr[RowTile], Mean[RowTile];
+   constexpr int W = VecW<T>::W;
    const int First = blockIdx.x * RowTile;
    int Cnt         = A.NEdgesAll - First;
    if (Cnt > RowTile)
       Cnt = RowTile;
    stageRanges(A.MinLayerEdgeBot, A.MaxLayerEdgeTop, First, Cnt, A.K, Lo, Hi);
-   if ((int)threadIdx.x < Cnt)
-      Btr[threadIdx.x] = A.BtrVelocity[First + threadIdx.x];
+   if ((int)threadIdx.x < Cnt) {
+      const int Le = threadIdx.x, E = First + Le;
+      // the runs to visit: recombine those of the range, the others every run that holds a level below K
+      VisLo[Le] = Op == BtrLevelRecombine ? Lo[Le] : 0;
+      VisHi[Le] = Op == BtrLevelRecombine ? Hi[Le] : A.K - 1;
+      // (an empty range has BtrThickEdge 0: the quotient is then never used)
+      Btr[Le] = Op == BtrLevelTransport ? A.BtrFluxMean[E] / A.BtrThickEdge[E] : A.BtrVelocity[E];
+      if (Op == BtrLevelAdvance)
+         Mean[Le] = A.BtrTendMean[E];
+   }
    __syncthreads();
-   forLevelRuns<T>(Cnt, Pitch, Lo, Hi, [&](int Le, int K0, int L, int H) {
-      const size_t R = (size_t)(First + Le) * Pitch + K0;
-      const T Bc     = *reinterpret_cast<const T *>(A.BclVelocity + R);
-      T Res;
+   forLevelRuns<T>(Cnt, Pitch, VisLo, VisHi, [&](int Le, int K0, int, int KLast) {
+      const int L = Lo[Le], H = Hi[Le];
+      const size_t R  = (size_t)(First + Le) * Pitch + K0;
+      const bool Some = K0 + W - 1 >= L && K0 <= H, All = K0 >= L && K0 + W - 1 <= H;
+      T Bc = T(), Old = T(), Td = T(), Res;
+      if (Some)
+         Bc = *reinterpret_cast<const T *>(A.BclVelocity + R);
+      if (Op == BtrLevelAdvance)
+         Td = *reinterpret_cast<const T *>(A.VelTend + R);
+      if (Op != BtrLevelRecombine && !All)
+         Old = *reinterpret_cast<const T *>(A.VelOld + R);
 #pragma unroll
-      for (int J = 0; J < VecW<T>::W; ++J)
-         setc(Res, J, getc(Bc, J) + Btr[Le]);
-      storeRanged<T>(A.NormalVelocity + R, Res, K0, L, H);
+      for (int J = 0; J < W; ++J) {
+         const bool In = K0 + J >= L && K0 + J <= H;
+         if (Op == BtrLevelAdvance)
+            setc(Res, J, In ? (getc(Bc, J) + A.Dt * (getc(Td, J) - Mean[Le])) + Btr[Le] : getc(Old, J) + A.Dt * getc(Td, J));
+         else
+            setc(Res, J, In ? getc(Bc, J) + Btr[Le] : getc(Old, J));
+      }
+      // (recombine: KLast = H and the run overlaps [L, H]; the others: every level 0 .. K - 1 of the run)
+      storeRanged<T>(A.VelOut + R, Res, K0, Op == BtrLevelRecombine ? L : 0, KLast);
    });
 }
 
@@ -155,28 +179,50 @@ __global__ void __launch_bounds__(SubThreads) btrCellKernel(BtrSubArgs A) {
    A.SSHNew[C] = Eta - A.Dt * Div;
 }
 
+/// Cor - Gravity*((Eta[c1] - Eta[c0])*InvDcEdge[e]) of edge E with the cells Cc, the Coriolis sum over the slots of E in
+/// slot order from A.Vel (holes skipped): the bracket of a sub-step (Eta = SSHNew) and of the residual forcing (Eta = SSH)
+__device__ inline Real btrBracket(const BtrSubArgs &A, int E, int2 Cc, const Real *Eta) {
+   const size_t NE = (size_t)A.NEdgesAll;
+   const int N     = min(A.NEdgesOnEdge[E], A.MaxEdges2);
+   Real Cor        = 0.0;
+   for (int J = 0; J < N; ++J) {
+      const int Ej = A.EoESlot[J * NE + E];
+      if (Ej >= 0)
+         Cor = Cor + A.CorSlot[J * NE + E] * A.Vel[Ej];
+   }
+   return Cor - A.Gravity * ((Eta[Cc.y] - Eta[Cc.x]) * A.InvDcEdge[E]);
+}
+
+__device__ inline bool btrOpenEdge(const BtrSubArgs &A, Real M, int2 Cc) {
+   return M != 0.0 && Cc.x >= 0 && Cc.x < A.NCellsAll && Cc.y >= 0 && Cc.y < A.NCellsAll;
+}
+
 __global__ void __launch_bounds__(SubThreads) btrEdgeKernel(BtrSubArgs A) {
    const int E = blockIdx.x * SubThreads + threadIdx.x;
    if (E >= A.NEdgesAll)
       return;
-   const size_t NE = (size_t)A.NEdgesAll;
-   const Real U    = A.Vel[E];
-   const Real M    = A.EdgeMask[E];
-   const int2 Cc   = *reinterpret_cast<const int2 *>(A.CellsOnEdge + 2 * (size_t)E);
+   const Real U  = A.Vel[E];
+   const Real M  = A.EdgeMask[E];
+   const int2 Cc = *reinterpret_cast<const int2 *>(A.CellsOnEdge + 2 * (size_t)E);
    Real F = 0.0, Un = U;
-   if (M != 0.0 && Cc.x >= 0 && Cc.x < A.NCellsAll && Cc.y >= 0 && Cc.y < A.NCellsAll) {
-      F = M * ((0.5 * ((A.SSH[Cc.x] + A.BottomDepth[Cc.x]) + (A.SSH[Cc.y] + A.BottomDepth[Cc.y]))) * U);
-      const int N = min(A.NEdgesOnEdge[E], A.MaxEdges2);
-      Real Cor    = 0.0;
-      for (int J = 0; J < N; ++J) {
-         const int Ej = A.EoESlot[J * NE + E];
-         if (Ej >= 0)
-            Cor = Cor + A.CorSlot[J * NE + E] * A.Vel[Ej];
-      }
-      Un = U + A.Dt * (M * ((Cor - A.Gravity * ((A.SSHNew[Cc.y] - A.SSHNew[Cc.x]) * A.InvDcEdge[E])) + A.Forcing[E]));
+   if (btrOpenEdge(A, M, Cc)) {
+      F  = M * ((0.5 * ((A.SSH[Cc.x] + A.BottomDepth[Cc.x]) + (A.SSH[Cc.y] + A.BottomDepth[Cc.y]))) * U);
+      Un = U + A.Dt * (M * (btrBracket(A, E, Cc, A.SSHNew) + A.Forcing[E]));
    }
    A.FluxSum[E] = A.FluxSum[E] + F;
    A.VelNew[E]  = Un;
+}
+
+__global__ void __launch_bounds__(SubThreads) btrResidualKernel(BtrSubArgs A, const Real *TendMean, Real *Forcing) {
+   const int E = blockIdx.x * SubThreads + threadIdx.x;
+   if (E >= A.NEdgesAll)
+      return;
+   const Real M  = A.EdgeMask[E];
+   const int2 Cc = *reinterpret_cast<const int2 *>(A.CellsOnEdge + 2 * (size_t)E);
+   Real G        = TendMean[E];
+   if (btrOpenEdge(A, M, Cc))
+      G = G - M * btrBracket(A, E, Cc, A.SSH);
+   Forcing[E] = G;
 }
 
 __global__ void __launch_bounds__(SubThreads) btrDivideKernel(Real *X, int N, Real Div) {
@@ -203,7 +249,8 @@ int btrColumnTile(int K) {
 void launchBtrColumn(const BtrColumnArgs &A, BtrEdgeMode Edges, bool Cells, hipStream_t S) {
    if (A.K <= 0)
       return;
-   OMEGA_REQUIRE(!(Edges == BtrEdgeForcing && Cells),
+   const bool Forcing = Edges == BtrEdgeForcing || Edges == BtrEdgeTendMean; // one kernel: A.BtrOut tells them apart
+   OMEGA_REQUIRE(!(Forcing && Cells),
                  "BarotropicMode column kernel: the forcing sweep has no cell half (only the split shares its launch)");
    const int Tile = btrColumnTile(A.K);
    OMEGA_REQUIRE(Tile >= 2,
@@ -217,7 +264,7 @@ void launchBtrColumn(const BtrColumnArgs &A, BtrEdgeMode Edges, bool Cells, hipS
       return;
    if (NEdgeTiles == 0)
       columnLaunchAs<BtrEdgeNone, true>(A, P, Tile, 0, NTiles, Bytes, S);
-   else if (Edges == BtrEdgeForcing)
+   else if (Forcing)
       columnLaunchAs<BtrEdgeForcing, false>(A, P, Tile, NEdgeTiles, NEdgeTiles, Bytes, S);
    else if (NCellTiles > 0)
       columnLaunchAs<BtrEdgeSplit, true>(A, P, Tile, NEdgeTiles, NTiles, Bytes, S);
@@ -226,13 +273,19 @@ void launchBtrColumn(const BtrColumnArgs &A, BtrEdgeMode Edges, bool Cells, hipS
    HIP_CHECK(hipGetLastError());
 }
 
-void launchBtrRecombine(const BtrRecombineArgs &A, hipStream_t S) {
+void launchBtrLevels(const BtrLevelArgs &A, BtrLevelOp Op, hipStream_t S) {
    if (A.NEdgesAll <= 0 || A.K <= 0)
       return;
    const int Pitch = levelPitch(A.K);
    const dim3 Grid((A.NEdgesAll + RowTile - 1) / RowTile), Block(RowBlock);
    withLaneType(Pitch, [&](auto Lane) {
-      hipLaunchKernelGGL(btrRecombineKernel<decltype(Lane)>, Grid, Block, 0, S, A, Pitch);
+      using T = decltype(Lane);
+      if (Op == BtrLevelRecombine)
+         hipLaunchKernelGGL((btrLevelKernel<T, BtrLevelRecombine>), Grid, Block, 0, S, A, Pitch);
+      else if (Op == BtrLevelTransport)
+         hipLaunchKernelGGL((btrLevelKernel<T, BtrLevelTransport>), Grid, Block, 0, S, A, Pitch);
+      else
+         hipLaunchKernelGGL((btrLevelKernel<T, BtrLevelAdvance>), Grid, Block, 0, S, A, Pitch);
    });
    HIP_CHECK(hipGetLastError());
 }
@@ -248,6 +301,14 @@ void launchBtrEdges(const BtrSubArgs &A, hipStream_t S) {
    if (A.NEdgesAll <= 0)
       return;
    hipLaunchKernelGGL(btrEdgeKernel, dim3((A.NEdgesAll + SubThreads - 1) / SubThreads), dim3(SubThreads), 0, S, A);
+   HIP_CHECK(hipGetLastError());
+}
+
+void launchBtrResidual(const BtrSubArgs &A, const Real *TendMean, Real *Forcing, hipStream_t S) {
+   if (A.NEdgesAll <= 0)
+      return;
+   hipLaunchKernelGGL(btrResidualKernel, dim3((A.NEdgesAll + SubThreads - 1) / SubThreads), dim3(SubThreads), 0, S, A,
+                      TendMean, Forcing);
    HIP_CHECK(hipGetLastError());
 }
 
