@@ -21,30 +21,24 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    OMEGA_REQUIRE(Btr != nullptr, "Split-Explicit doStep: no BarotropicMode is attached: attachBarotropic first");
    requireHealthyWire();
    const int CurLevel = 0, NextLevel = 1;
-   Array3DReal CurTracerArray, NextTracerArray;
-   OMEGA_REQUIRE(Trc->getAll(CurTracerArray, CurLevel) == 0 && Trc->getAll(NextTracerArray, NextLevel) == 0,
-                 "Split-Explicit doStep: error retrieving tracers");
-   Array2DReal HCur, UCur, UNext;
-   OMEGA_REQUIRE(State->getLayerThickness(HCur, CurLevel) == 0 && State->getNormalVelocity(UCur, CurLevel) == 0 &&
-                     State->getNormalVelocity(UNext, NextLevel) == 0,
-                 "Split-Explicit doStep: error retrieving the state");
+   const StepArrays A = stepArrays("Split-Explicit", State);
    const R8 Dt = coeff(1.0);
    const R8 T0 = simTime();
    // R^{n} = RHS(u^{n}, h^{n}, phi^{n}, t^{n}); its velocity part is kept
    Tend->ModelTime = T0;
-   Tend->computeAllTendencies(State, AuxState, CurTracerArray, CurLevel, CurLevel, S);
+   Tend->computeAllTendencies(State, AuxState, A.CurTr, CurLevel, CurLevel, S);
    // the 2-D system over the step, forced by the mean of R_u^{n} less what the sub-steps compute themselves
-   Btr->splitVelocityAndSSH(HCur, UCur, S);
-   Btr->computeResidualForcing(HCur, Tend->NormalVelocityTend, S);
+   Btr->splitVelocityAndSSH(A.CurH, A.CurU, S);
+   Btr->computeResidualForcing(A.CurH, Tend->NormalVelocityTend, S);
    Btr->subcycle(NSub, Dt / (R8)NSub, S);
    // h^{n+1} and phi^{n+1} by the transporting velocity: baroclinic u^{n} + the sub-cycle's mean flux over the thickness
-   Btr->transportVelocity(UCur, UNext, S);
+   Btr->transportVelocity(A.CurU, A.NextU, S);
    Tend->computeThicknessTendencies(State, AuxState, CurLevel, NextLevel, S);
    updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
-   Tend->computeTracerTendencies(State, AuxState, CurTracerArray, CurLevel, NextLevel, S);
-   updateTracersByTend(NextTracerArray, CurTracerArray, State, NextLevel, State, CurLevel, Dt, S);
+   Tend->computeTracerTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
+   updateTracersByTend(A.NextTr, A.CurTr, State, NextLevel, State, CurLevel, Dt, S);
    // u^{n+1} = (baroclinic u^{n} + Dt*(R_u^{n} - its mean)) + the barotropic velocity the sub-cycle ended with
-   Btr->advanceVelocity(UCur, Tend->NormalVelocityTend, Dt, UNext, S);
+   Btr->advanceVelocity(A.CurU, Tend->NormalVelocityTend, Dt, A.NextU, S);
    mixNewLevel(State, S);
    updateTimeLevels(State, S);
    ++NStepsDone;

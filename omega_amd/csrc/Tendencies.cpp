@@ -196,10 +196,8 @@ bool Tendencies::computeAllTendenciesStage(const OceanState *State, const Auxili
    Pacer::Range Timer("Tend:computeAllTendencies", 1);
    if (!(UseFusedRHS && fusedRHSSupported(Mesh->view(), NVertLayers)))
       return false;
-   if (CustomThicknessTend || CustomVelocityTend)
-      return false; // the custom terms are added to the stored tendencies: needs the plain sequence
-   if (PGrad || VAdv)
-      return false; // so are the attached pressure gradient and vertical advection
+   if (addsTermsAfterFusedRHS())
+      return false; // custom terms, pressure gradient, vertical advection: added to the stored tendencies, needs the plain sequence
    Array2DReal LayerThick, NormVel;
    OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0 && State->getNormalVelocity(NormVel, VelLvl) == 0,
                  "Tendencies: bad time level");
@@ -234,7 +232,7 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
                         EdgeScratch.Ptr, nullptr, Mesh->narrowView());
       };
       // wind forcing reads the stress arrays through a non-tile kernel too, still plain launches: capturable
-      if (graphsOn() && !Ev && !CustomThicknessTend && !CustomVelocityTend && !PGrad && !VAdv) {
+      if (graphsOn() && !Ev && !addsTermsAfterFusedRHS()) { // (!Ev: kernel timing records events between the launches)
          GraphCache::Key Key;
          GraphCache::add(Key, LayerThick.Ptr), GraphCache::add(Key, NormVel.Ptr), GraphCache::add(Key, TracerArray.Ptr);
          GraphCache::add(Key, Aux), GraphCache::add(Key, P), GraphCache::add(Key, S);

@@ -126,6 +126,11 @@ class Tendencies : public Registry<Tendencies> {
    void attachVertAdv(VertAdv *VAdv);
    VertAdv *vertAdv() const { return VAdv; }
 
+   /// Does anything add terms to the stored tendencies after the fused RHS (a custom hook, an attached PressureGrad or
+   /// VertAdv)?  Then the stage-fused form does not apply and neither the RHS nor a step is replayed as a graph.  A new
+   /// attachable term goes here.
+   bool addsTermsAfterFusedRHS() const { return CustomThicknessTend || CustomVelocityTend || PGrad || VAdv; }
+
    void computeThicknessTendenciesOnly(const OceanState *State, const AuxiliaryState *AuxState, int ThickTimeLevel,
                                        int VelTimeLevel, hipStream_t S);
    void computeVelocityTendenciesOnly(const OceanState *State, const AuxiliaryState *AuxState, int ThickTimeLevel,

@@ -9,6 +9,8 @@
 // REFERENCE'S OWN SIGNATURE (TimeInterval coefficient / TimeInstant &SimTime, no stream: the
 // object's `Stream`), so that a reference call site -- ocnRun's `Stepper->doStep(State, SimTime)`,
 // a stepper subclass written like RungeKutta4Stepper.cpp:68-137 -- compiles unchanged.
+// TimeStepper.cpp holds the base class, the registry, the update kernels, Forward-Backward and RungeKutta2;
+// RungeKutta4Stepper.cpp the RungeKutta4 scheme, as the reference lays its steppers out; TimeMgr.cpp the TimeMgr.h arithmetic.
 #ifndef OMEGA_AMD_TIMESTEPPER_H
 #define OMEGA_AMD_TIMESTEPPER_H
 
@@ -142,6 +144,17 @@ class TimeStepper {
    /// first thing in every doStep: a peer-wire wait of an EARLIER step that gave up is reported now (the status word is
    /// host memory: no synchronisation); the halo of that step was left untouched and the state is not to be trusted
    void requireHealthyWire() const;
+   /// what a doStep opens with: the Cur (0) / Next (1) tracer arrays and, given State, its arrays of both levels; aborts
+   /// with "<Scheme> doStep: error retrieving tracers" / "... the state"
+   struct StepArrays {
+      Array3DReal CurTr, NextTr;
+      Array2DReal CurH, CurU, NextH, NextU;
+   };
+   StepArrays stepArrays(const char *Scheme, OceanState *State = nullptr) const;
+   /// h, u of State's time level Level and the tracers Tr in one message per neighbour on stream S, inside the Pacer
+   /// timer TimerName (level 3); aborts with ErrorPrefix + the wire's error
+   void exchangeState(OceanState *State, int Level, const Array3DReal *Tr, hipStream_t S, const char *TimerName,
+                      const char *ErrorPrefix) const;
    Tendencies *Tend         = nullptr;
    AuxiliaryState *AuxState = nullptr;
    const HorzMesh *Mesh     = nullptr;
@@ -199,22 +212,12 @@ class RungeKutta4Stepper : public TimeStepper {
    Array3DReal ProvisTracers2;
    bool doStepFused(OceanState *State, hipStream_t S);
    bool StageFusedKnownGood = false; ///< a direct (un-captured) stage-fused step has succeeded on this configuration
-   // overlapped exchange: communication stream, "band is final" and "halo is in place" events
-   hipStream_t CommStream = nullptr;
-   hipEvent_t EvBand = nullptr, EvDone = nullptr, EvFork = nullptr;
-   void ensureCommStream();
-   bool ExchangePending = false;
-   struct ExchangeJob {
-      RungeKutta4Stepper *Self;
-      hipStream_t S;
-      Array2DReal H, U;
-      Array3DReal *Tr;
-      int NT;
-      bool Provis = false; ///< the mid-step exchange of the provisional state (timer "RK4:haloExchProvis")
-   };
-   static void startExchangeThunk(void *Job);
-   void startExchange(const ExchangeJob &Job);
-   void joinExchange(hipStream_t S);
+   /// the stages of a stage-fused step (RK4StagePlan.h: what each does about the halo); false: the first was refused
+   bool runStages(OceanState *State, const StepArrays &A, hipStream_t S);
+   GraphCache::Key stepGraphKey(OceanState *State, const StepArrays &A, hipStream_t S) const;
+   /// the overlapped exchange's communication stream and events; finalizeInit makes it when the halo has neighbours
+   class HaloOverlap;
+   std::unique_ptr<HaloOverlap> Overlap;
 };
 
 } // namespace OMEGA
