@@ -387,6 +387,14 @@ int omg_tend_compute_velocity(omg_tend *t, const omg_state *s, omg_aux *a, int t
                               void *stream);
 int omg_tend_compute_tracer(omg_tend *t, const omg_state *s, omg_aux *a, const omg_tracers *tr,
                             int tracer_time_level, int thick_time_level, int vel_time_level, void *stream);
+/* Tendencies::computeTransportTendencies (omega_amd/csrc/Tendencies.h): the transport half of the RHS in two launches.
+ * LayerThicknessTend and TracerTend end up, bit for bit on every row < NCellsAll, as omg_tend_compute_thickness followed
+ * by omg_tend_compute_tracer with the same arguments leave them (attached VertAdv terms included); the edge-located
+ * auxiliary arrays FluxLayerThickEdge, MeanLayerThickEdge and HTracersEdge are not written, Del2TracersCell only with
+ * TracerHyperDiffTendencyEnable.  With a custom thickness tendency installed the two group calls run instead.  Fails
+ * for a NULL handle and for a time level out of range. */
+int omg_tend_compute_transport(omg_tend *t, const omg_state *s, omg_aux *a, const omg_tracers *tr,
+                               int tracer_time_level, int thick_time_level, int vel_time_level, void *stream);
 int omg_tend_compute_thickness_only(omg_tend *t, const omg_state *s, omg_aux *a, int thick_time_level,
                                     int vel_time_level, void *stream);
 int omg_tend_compute_velocity_only(omg_tend *t, const omg_state *s, omg_aux *a, int thick_time_level,
@@ -700,6 +708,10 @@ int omg_btr_advance_velocity(omg_btr *b, const double *velocity_old_dev, const d
  * BarotropicMode per step.  Fails for any other stepper type, a null b, one of another mesh or layer count, nsub < 1 and
  * a stepper whose halo has neighbours (the sub-cycle knows no halo exchange).  The stepper keeps a pointer to b. */
 int omg_stepper_attach_barotropic(omg_stepper *st, omg_btr *b, int nsub);
+/* SplitExplicitStepper::UseFusedTransport (default on): the thickness and tracer tendencies of a step through
+ * omg_tend_compute_transport (two launches) instead of the two group calls (five); the step's result is the same bit
+ * for bit either way.  Fails for any other stepper type. */
+int omg_stepper_set_fused_transport(omg_stepper *st, int on);
 /* "BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean", "BtrTendMean" ([NEdgesSize]), "SSH" ([NCellsSize]), "BclVelocity"
  * ([NEdgesSize][NVertLayers]); all zero at creation */
 int omg_btr_device_ptr(const omg_btr *b, const char *name, double **dev, size_t *n);

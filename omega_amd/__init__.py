@@ -1439,6 +1439,12 @@ class Tendencies(_Handle):
     def compute_tracer_tendencies(self, state, aux, tracers, tracer_tl=0, thick_tl=0, vel_tl=0, stream=None):
         _chk(lib().omg_tend_compute_tracer(self.h, state.h, aux.h, tracers.h, tracer_tl, thick_tl, vel_tl, _sh(stream)))
 
+    def compute_transport_tendencies(self, state, aux, tracers, tracer_tl=0, thick_tl=0, vel_tl=0, stream=None):
+        """Tendencies::computeTransportTendencies: LayerThicknessTend and TracerTend as compute_thickness_tendencies
+        followed by compute_tracer_tendencies leave them, bit for bit, in two launches; the edge-located auxiliary
+        arrays are not written."""
+        _chk(lib().omg_tend_compute_transport(self.h, state.h, aux.h, tracers.h, tracer_tl, thick_tl, vel_tl, _sh(stream)))
+
     def compute_thickness_tendencies_only(self, state, aux, thick_tl=0, vel_tl=0, stream=None):
         _chk(lib().omg_tend_compute_thickness_only(self.h, state.h, aux.h, thick_tl, vel_tl, _sh(stream)))
 
@@ -1532,6 +1538,11 @@ class TimeStepper(_Handle):
         raises on any other kind, for another mesh or layer count, nsub < 1 and a halo with neighbours."""
         _chk(lib().omg_stepper_attach_barotropic(self.h, btr.h if btr is not None else None, int(nsub)))
         self._barotropic = btr  # the library keeps a pointer to it
+
+    def set_fused_transport(self, on: bool):
+        """SplitExplicitStepper::UseFusedTransport (default on): the step's thickness and tracer tendencies through
+        Tendencies.compute_transport_tendencies instead of the two group calls; raises on any other kind."""
+        _chk(lib().omg_stepper_set_fused_transport(self.h, int(on)))
 
     def do_step(self, state: OceanState, stream=None):
         _chk(lib().omg_stepper_do_step(self.h, state.h, _sh(stream)))

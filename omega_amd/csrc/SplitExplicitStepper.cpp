@@ -33,9 +33,16 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    Btr->subcycle(NSub, Dt / (R8)NSub, S);
    // h^{n+1} and phi^{n+1} by the transporting velocity: baroclinic u^{n} + the sub-cycle's mean flux over the thickness
    Btr->transportVelocity(A.CurU, A.NextU, S);
-   Tend->computeThicknessTendencies(State, AuxState, CurLevel, NextLevel, S);
-   updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
-   Tend->computeTracerTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
+   if (UseFusedTransport) {
+      // both tendencies first: the tracer tendency reads h^{n} and the transporting velocity, neither of which the
+      // thickness update writes, so the order of the four calls below is free
+      Tend->computeTransportTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
+      updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
+   } else {
+      Tend->computeThicknessTendencies(State, AuxState, CurLevel, NextLevel, S);
+      updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
+      Tend->computeTracerTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
+   }
    updateTracersByTend(A.NextTr, A.CurTr, State, NextLevel, State, CurLevel, Dt, S);
    // u^{n+1} = (baroclinic u^{n} + Dt*(R_u^{n} - its mean)) + the barotropic velocity the sub-cycle ended with
    Btr->advanceVelocity(A.CurU, Tend->NormalVelocityTend, Dt, A.NextU, S);

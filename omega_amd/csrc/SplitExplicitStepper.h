@@ -15,11 +15,17 @@
 //   7. Tend->computeTracerTendencies(State, AuxState, CurTracers, Cur, Next);
 //      updateTracersByTend(NextTracers, CurTracers, State, Next, State, Cur, Dt)
 //      (an attached VertAdv takes its transport from step 6, as Tendencies.h documents for the group methods)
+//      With UseFusedTransport steps 6 and 7 are instead
+//        Tend->computeTransportTendencies(State, AuxState, CurTracers, Cur, Next)    (both tendencies, two launches)
+//        updateThicknessByTend(State, Next, State, Cur, Dt)
+//        updateTracersByTend(NextTracers, CurTracers, State, Next, State, Cur, Dt)
+//      -- the same values bit for bit: computeTransportTendencies equals the two group methods by contract, and the
+//      tracer tendency reads h[Cur] and u[Next], neither of which the thickness update (it writes h[Next]) touches.
 //   8. Btr->advanceVelocity(u[Cur], NormalVelocityTend, Dt, u[Next])
 //   9. mixNewLevel, updateTimeLevels, ++NStepsDone
-// Steps 6 and 7 leave NormalVelocityTend as step 1 wrote it: the two group methods write LayerThicknessTend, TracerTend
-// and the auxiliary state only (Tendencies.cpp), so step 8 needs no copy of it.  A custom thickness hook that wrote the
-// velocity tendency would break this; the hooks are handed their own array.
+// Steps 6 and 7 leave NormalVelocityTend as step 1 wrote it: the group methods and computeTransportTendencies write
+// LayerThicknessTend, TracerTend and the auxiliary state only (Tendencies.cpp), so step 8 needs no copy of it.  A custom
+// thickness hook that wrote the velocity tendency would break this; the hooks are handed their own array.
 //
 // The result equals these calls made one by one through the public interface, bit for bit.  A step creates no device
 // buffer, stream or event and captures nothing into a graph.  The thickness and tracer halves of step 1 are computed and
@@ -44,6 +50,11 @@ class SplitExplicitStepper : public TimeStepper {
    void attachBarotropic(BarotropicMode *Btr, int NSub);
    BarotropicMode *barotropic() const { return Btr; }
    int subSteps() const { return NSub; }
+
+   /// Steps 6-7 through Tendencies::computeTransportTendencies (two launches, no edge-located intermediate in HBM)
+   /// instead of the two group methods (five launches); the step's result is the same bit for bit either way.
+   /// DESIGN.md section 4.8 has the measurement behind the default.
+   bool UseFusedTransport = true;
 
    void doStep(OceanState *State, hipStream_t S) override;
    using TimeStepper::doStep;

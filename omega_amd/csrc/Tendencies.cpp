@@ -189,6 +189,26 @@ void Tendencies::computeTracerTendencies(const OceanState *State, const Auxiliar
    Pacer::stop("Tend:computeTracerAuxCell", 2);
    computeTracerTendenciesOnly(State, Aux, TracerArray, ThickLvl, VelLvl, S);
 }
+// the transport half in two launches (kernels/TransportKernels.hip); no counterpart in the reference
+void Tendencies::computeTransportTendencies(const OceanState *State, const AuxiliaryState *Aux, const Array3DReal &TracerArray,
+                                            int ThickLvl, int VelLvl, hipStream_t S) {
+   Pacer::Range Timer("Tend:computeTransportTendencies", 1);
+   if (CustomThicknessTend) { // the hook may read the auxiliary state: the sequence that materialises it
+      computeThicknessTendencies(State, Aux, ThickLvl, VelLvl, S);
+      computeTracerTendencies(State, Aux, TracerArray, ThickLvl, VelLvl, S);
+      return;
+   }
+   Array2DReal LayerThick, NormVel;
+   OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0 && State->getNormalVelocity(NormVel, VelLvl) == 0,
+                 "Tendencies: bad time level");
+   launchTransportTend(Mesh->view(), NVertLayers, NTracers, paramsFor(Aux), Aux->ptrs(), LayerThicknessTend.Ptr,
+                       TracerTend.Ptr, LayerThick.Ptr, NormVel.Ptr, TracerArray.Ptr, S);
+   if (VAdv) { // the transport of the built-in thickness terms, then the tracer term from it
+      Pacer::Range T2("Tend:vertAdv", 2);
+      VAdv->computeAndAddThickness(LayerThicknessTend, S);
+      VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
+   }
+}
 // Tendencies.cpp:579-600
 bool Tendencies::computeAllTendenciesStage(const OceanState *State, const AuxiliaryState *Aux,
                                            const Array3DReal &TracerArray, int ThickLvl, int VelLvl,

@@ -144,6 +144,28 @@ class Tendencies : public Registry<Tendencies> {
                                   int VelTimeLevel, hipStream_t S);
    void computeTracerTendencies(const OceanState *State, const AuxiliaryState *AuxState,
                                 const Array3DReal &TracerArray, int ThickTimeLevel, int VelTimeLevel, hipStream_t S);
+   /// The transport half of the RHS -- thickness and tracer tendencies, with the velocity taken from a time level of
+   /// the caller's choice (the Split-Explicit step passes the transporting velocity) -- in two launches instead of the
+   /// five of the two group methods (kernels/TransportKernels.hip).  This library's own call:
+   /// the reference has none.
+   ///
+   /// Contract: on every row < NCellsAll (halo included) LayerThicknessTend and TracerTend hold, BIT FOR BIT, what
+   ///    computeThicknessTendencies(State, AuxState, ThickTimeLevel, VelTimeLevel, S);
+   ///    computeTracerTendencies(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, S);
+   /// leave there, attached terms included, in their documented order: the built-in thickness terms, an attached
+   /// VertAdv's computeAndAddThickness, the built-in tracer terms, then VertAdv::addTracerTend with the transport just
+   /// computed.  Nothing else of the tendency arrays is written: not the row padding, not the sentinel row, not
+   /// NormalVelocityTend.  With no tracers the thickness tendency alone is computed.
+   ///
+   /// Deviation from the two group methods: the edge-located auxiliary arrays FluxLayerThickEdge, MeanLayerThickEdge
+   /// and HTracersEdge are NOT materialised (as with the fused RHS: each cell recomputes the values of its own edges in
+   /// registers), and Del2TracersCell is written only when Params.TracerHyperDiffTendencyEnable is set (the group
+   /// method writes it always).
+   ///
+   /// Always valid: with a CustomThicknessTend hook installed -- it is handed the AuxiliaryState and may read those
+   /// arrays -- the call runs the two group methods instead.  A time level out of range is refused with their error.
+   void computeTransportTendencies(const OceanState *State, const AuxiliaryState *AuxState, const Array3DReal &TracerArray,
+                                   int ThickTimeLevel, int VelTimeLevel, hipStream_t S);
    /// computeAllTendencies with a Runge-Kutta stage update folded into the kernels that produce the
    /// tendencies (kernels/Kernels.h: StageUpdate).  Returns false -- nothing launched -- when the
    /// stage-fused kernels do not cover this mesh / option set; the caller then uses the plain sequence.
@@ -173,6 +195,11 @@ class Tendencies : public Registry<Tendencies> {
                              int ThickTimeLevel, int VelTimeLevel, TimeInstant Time) {
       ModelTime = Time.getSeconds();
       computeAllTendencies(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, Stream);
+   }
+   void computeTransportTendencies(const OceanState *State, const AuxiliaryState *AuxState, const Array3DReal &TracerArray,
+                                   int ThickTimeLevel, int VelTimeLevel, TimeInstant Time) {
+      ModelTime = Time.getSeconds();
+      computeTransportTendencies(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, Stream);
    }
    void computeThicknessTendenciesOnly(const OceanState *State, const AuxiliaryState *AuxState, int ThickTimeLevel,
                                        int VelTimeLevel, TimeInstant Time) {

@@ -1176,6 +1176,13 @@ int omg_tend_compute_tracer(omg_tend *t, const omg_state *s, omg_aux *a, const o
    t->T->computeTracerTendencies(s->S.get(), a->A.get(), tracerArray(tr, trtl), ttl, vtl, (hipStream_t)stream);
    OMG_CATCH
 }
+int omg_tend_compute_transport(omg_tend *t, const omg_state *s, omg_aux *a, const omg_tracers *tr, int trtl, int ttl,
+                               int vtl, void *stream) {
+   OMG_TRY
+   OMG_ARG(t && s && a);
+   t->T->computeTransportTendencies(s->S.get(), a->A.get(), tracerArray(tr, trtl), ttl, vtl, (hipStream_t)stream);
+   OMG_CATCH
+}
 int omg_tend_compute_thickness_only(omg_tend *t, const omg_state *s, omg_aux *a, int ttl, int vtl, void *stream) {
    OMG_TRY
    OMG_ARG(t && s && a);
@@ -1940,6 +1947,14 @@ int omg_stepper_attach_barotropic(omg_stepper *st, omg_btr *b, int nsub) {
    auto *Split = dynamic_cast<SplitExplicitStepper *>(st->St.get());
    OMEGA_REQUIRE(Split != nullptr, "TimeStepper: attachBarotropic: this stepper is not a Split-Explicit one");
    Split->attachBarotropic(b ? b->B.get() : nullptr, nsub);
+   OMG_CATCH
+}
+int omg_stepper_set_fused_transport(omg_stepper *st, int on) {
+   OMG_TRY
+   OMG_ARG(st);
+   auto *Split = dynamic_cast<SplitExplicitStepper *>(st->St.get());
+   OMEGA_REQUIRE(Split != nullptr, "TimeStepper: setFusedTransport: this stepper is not a Split-Explicit one");
+   Split->UseFusedTransport = on != 0;
    OMG_CATCH
 }
 static ArrRef btrLookup(const BarotropicMode &B, const char *Name) {

@@ -66,6 +66,14 @@ void launchVelocityTendOnly(const MeshView &M, int K, const TendParams &P, const
 void launchTracerTendOnly(const MeshView &M, int K, int NT, const TendParams &P, const AuxPtrs &A, Real *TrTend,
                           const Real *U, const Real *Tr, hipStream_t S);
 
+// ---- fused transport half (Tendencies::computeTransportTendencies): see TransportKernels.hip ----
+/// HTend and TrTend (through every enabled tracer term) on cells [0, NCellsAll) from H, U, Tr, bit for bit what
+/// launchLayerThickAuxEdge + launchThicknessTendOnly + launchEdgeAuxState4 + launchCellAuxState4 + launchTracerTendOnly
+/// leave there, in one launch, or two with the tracer hyperdiffusion term enabled (A.Del2TracersCell is written then,
+/// and only then); no edge-located array of A is read or written.  NT == 0: the thickness tendency only.
+void launchTransportTend(const MeshView &M, int K, int NT, const TendParams &P, const AuxPtrs &A, Real *HTend, Real *TrTend,
+                         const Real *H, const Real *U, const Real *Tr, hipStream_t S);
+
 // ---- fused RHS (Tendencies::computeAllTendencies): see FusedKernels.hip ----
 /// Kernel order (also the index of the optional timing events, Ev[i] recorded BEFORE kernel i,
 /// Ev[7] after the last): 0 vertex L1, 1 cell L1, 2 cell L2, 3 vertex L2, 4 + 5 edge L3 (cell-centric

@@ -1,0 +1,226 @@
+// TransportKernels.hip -- Tendencies::computeTransportTendencies: the transport half of the RHS (thickness and tracer
+// tendencies at a caller-chosen velocity level) in two launches.  The group calls run five (EdgeAux2Body,
+// ThickTendBody, TracerEdgeBody, TracerCellBody, TracerTendBody) and pass FluxLayerThickEdge, MeanLayerThickEdge,
+// HTracersEdge and Del2TracersCell through HBM; here a cell recomputes the edge values of its own slots in registers
+// from CellsOnEdgeOnCell -- the expressions of those bodies, in their left-to-right order, so every bit of the result
+// is theirs -- and only Del2TracersCell, which the hyperdiffusion term gathers from NEIGHBOURING cells, makes a round
+// trip (and only when that term is enabled).  Compiled with -ffp-contract=off.
+#include "KernelCommon.h"
+#include "Kernels.h"
+
+namespace OMEGA {
+
+// ---------------------------------------------------------------------------------------
+// Launch 1, one thread per (cell, level chunk): LayerThicknessTend (ThickTendBody with the flux of EdgeAux2Body), per
+// tracer Del2TracersCell (TracerCellBody with the mean thickness of EdgeAux2Body) and TracerTend through the advection
+// and del2 terms (TracerTendBody with the edge tracer of TracerEdgeBody).
+//
+// Registers: the edge values of all slots at once (h at both cells and u of 7 slots are 84 VGPRs with dv2) would leave
+// nothing for the tracer loop, so nothing is kept per slot.  The tracers go in blocks of TrBlock: one pass over the
+// slots loads h at the slot's two cells and u at its edge once and serves the block's tracers from them (7 gathers per
+// slot for 2 tracers against 10 one by one); the next block loads them again, from L1/L2 -- the rows were fetched a
+// moment ago by this workgroup.  The thickness tendency rides on the first block's pass.  Block 2 is the measured
+// optimum at QU30 size with 6 tracers (dv2: 118 VGPRs, 4 waves per SIMD): 1 is 8 % slower, 3 (134 VGPRs, 3 waves) 7 %
+// (profiles/EXPERIMENTS.md).
+struct TransportCellBody {
+   static constexpr int TrBlock = 2;
+   MeshView M;
+   int K, NT;
+   TendParams P;
+   const Real *H, *U, *Tr;
+   Real *HTend, *TrTend, *Del2Tr;
+   struct Lds {
+      Real *DvS, *MDvS, *Df2, *D2C, *InvA;
+      int *Edge, *C0, *C1, *N;
+   };
+   size_t ldsBytes(int Tile) const {
+      const int ME = M.MaxEdges;
+      return ldsRound8(sizeof(Real) * Tile * ME) * 4 + ldsRound8(sizeof(Real) * Tile) +
+             ldsRound8(sizeof(int) * Tile * ME) * 3 + ldsRound8(sizeof(int) * Tile);
+   }
+   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
+      const int ME = M.MaxEdges;
+      LdsCarver C{Ptr};
+      Lds L;
+      L.DvS  = C.take<Real>(Tile * ME);
+      L.MDvS = C.take<Real>(Tile * ME);
+      L.Df2  = C.take<Real>(Tile * ME);
+      L.D2C  = C.take<Real>(Tile * ME);
+      L.InvA = C.take<Real>(Tile);
+      L.Edge = C.take<int>(Tile * ME);
+      L.C0   = C.take<int>(Tile * ME);
+      L.C1   = C.take<int>(Tile * ME);
+      L.N    = C.take<int>(Tile);
+      return L;
+   }
+   __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
+      const int ME = M.MaxEdges;
+      for (int I = Tid; I < Cnt * ME; I += NThr) {
+         const size_t G = (size_t)First * ME + I;
+         L.DvS[I]       = M.DvSignOnCell[G];
+         L.MDvS[I]      = M.MaskDvSignOnCell[G];
+         L.Df2[I]       = M.Diff2CoefOnCell[G];
+         L.D2C[I]       = M.Del2TrCoefOnCell[G];
+         L.Edge[I]      = M.EdgesOnCell[G];
+         L.C0[I]        = M.CellsOnEdgeOnCell[2 * G];
+         L.C1[I]        = M.CellsOnEdgeOnCell[2 * G + 1];
+      }
+      for (int I = Tid; I < Cnt; I += NThr) {
+         L.N[I]    = M.NEdgesOnCell[First + I];
+         L.InvA[I] = M.InvAreaCell[First + I];
+      }
+   }
+   /// one pass over the cell's slots for the tracers [Lt0, Lt0 + NB); Thick: the thickness tendency too
+   template <class T, int NB> __device__ __forceinline__ void pass(const Lds &L, int Le, int ICell, int Kv, int Lt0, bool Thick) const {
+      constexpr int NA     = NB > 0 ? NB : 1;
+      const int ME         = M.MaxEdges;
+      const int N          = L.N[Le];
+      const Real InvA      = L.InvA[Le];
+      const size_t CStride = (size_t)M.NCellsSize * K;
+      const bool Adv = P.TracerHorzAdvTendencyEnable, Diff = P.TracerDiffTendencyEnable, Hyp = P.TracerHyperDiffTendencyEnable;
+      const bool DoFlux = Thick && P.ThicknessFluxTendencyEnable;
+      const bool NeedU  = DoFlux || (NB > 0 && Adv);
+      T DivTmp = splat<T>(0.0);
+      T HAdvTmp[NA], DiffTmp[NA], D2Tmp[NA];
+#pragma unroll
+      for (int B = 0; B < NA; ++B)
+         HAdvTmp[B] = DiffTmp[B] = D2Tmp[B] = splat<T>(0.0);
+      for (int J = 0; J < N; ++J) {
+         const int C0 = L.C0[Le * ME + J], C1 = L.C1[Le * ME + J];
+         const T H0 = ldk<T>(H, C0, K, Kv), H1 = ldk<T>(H, C1, K, Kv);
+         const T Mean = 0.5 * (H0 + H1); // MeanLayerThickEdge (EdgeAux2Body)
+         T Ue         = splat<T>(0.0);
+         if (NeedU)
+            Ue = ldk<T>(U, L.Edge[Le * ME + J], K, Kv);
+         if (DoFlux) { // FluxLayerThickEdge (EdgeAux2Body), ThicknessFluxDivOnCell (ThickTendBody)
+            const T Flux = P.FluxThicknessUpwind ? upwind(Ue, H0, H1) : Mean;
+            DivTmp -= L.DvS[Le * ME + J] * Flux * Ue * InvA;
+         }
+#pragma unroll
+         for (int B = 0; B < NB; ++B) {
+            const Real *TrL = Tr + (Lt0 + B) * CStride;
+            const T T0 = ldk<T>(TrL, C0, K, Kv), T1 = ldk<T>(TrL, C1, K, Kv);
+            if (Adv) { // HTracersEdge (TracerEdgeBody), TracerHorzAdvOnCell (TracerTendBody)
+               const T HT0 = H0 * T0;
+               const T HT1 = H1 * T1;
+               T HTr;
+               if (!P.FluxTracerUpwind)
+                  HTr = 0.5 * (HT0 + HT1);
+               else
+                  HTr = upwind(Ue, HT0, HT1);
+               HAdvTmp[B] -= L.MDvS[Le * ME + J] * HTr * Ue * InvA;
+            }
+            const T Grad = T1 - T0;
+            if (Diff) // TracerDiffOnCell (TracerTendBody)
+               DiffTmp[B] -= L.Df2[Le * ME + J] * Mean * Grad;
+            if (Hyp) // Del2TracersCell (TracerCellBody)
+               D2Tmp[B] -= L.D2C[Le * ME + J] * Mean * Grad;
+         }
+      }
+      if (Thick) {
+         T TendV = splat<T>(0.0);
+         if (DoFlux)
+            TendV -= DivTmp;
+         stk<T>(HTend, ICell, K, Kv, TendV);
+      }
+#pragma unroll
+      for (int B = 0; B < NB; ++B) {
+         T TendV = splat<T>(0.0);
+         if (Adv)
+            TendV -= HAdvTmp[B];
+         if (Diff)
+            TendV += P.EddyDiff2 * DiffTmp[B] * InvA;
+         stk<T>(TrTend + (Lt0 + B) * CStride, ICell, K, Kv, TendV);
+         if (Hyp)
+            stk<T>(Del2Tr + (Lt0 + B) * CStride, ICell, K, Kv, D2Tmp[B] * InvA);
+      }
+   }
+   template <class T> __device__ void compute(const Lds &L, int Le, int ICell, int Kv) const {
+      if (NT <= 0) {
+         pass<T, 0>(L, Le, ICell, Kv, 0, true);
+         return;
+      }
+      int Lt = 0;
+      for (; Lt + TrBlock <= NT; Lt += TrBlock)
+         pass<T, TrBlock>(L, Le, ICell, Kv, Lt, Lt == 0);
+      if (Lt < NT) // the odd one
+         pass<T, 1>(L, Le, ICell, Kv, Lt, Lt == 0);
+   }
+};
+
+// ---------------------------------------------------------------------------------------
+// Launch 2 (only with the hyperdiffusion term enabled): TracerHyperDiffOnCell (TracerTendBody).  The tendency launch 1
+// stored is reloaded -- a stored double reloaded is the register value, the accumulation chain goes on exactly -- and
+// the term is subtracted from the Del2TracersCell of the slots' cells.  EddyDiff4 == 0 is evaluated like any other
+// value: a non-finite Del2 propagates as in the group call.
+struct TransportHyperBody {
+   MeshView M;
+   int K, NT;
+   Real EddyDiff4;
+   const Real *Del2Tr;
+   Real *TrTend;
+   struct Lds {
+      Real *Df4, *InvA;
+      int *C0, *C1, *N;
+   };
+   size_t ldsBytes(int Tile) const {
+      const int ME = M.MaxEdges;
+      return ldsRound8(sizeof(Real) * Tile * ME) + ldsRound8(sizeof(Real) * Tile) + ldsRound8(sizeof(int) * Tile * ME) * 2 +
+             ldsRound8(sizeof(int) * Tile);
+   }
+   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
+      const int ME = M.MaxEdges;
+      LdsCarver C{Ptr};
+      Lds L;
+      L.Df4  = C.take<Real>(Tile * ME);
+      L.InvA = C.take<Real>(Tile);
+      L.C0   = C.take<int>(Tile * ME);
+      L.C1   = C.take<int>(Tile * ME);
+      L.N    = C.take<int>(Tile);
+      return L;
+   }
+   __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
+      const int ME = M.MaxEdges;
+      for (int I = Tid; I < Cnt * ME; I += NThr) {
+         const size_t G = (size_t)First * ME + I;
+         L.Df4[I]       = M.Diff4CoefOnCell[G];
+         L.C0[I]        = M.CellsOnEdgeOnCell[2 * G];
+         L.C1[I]        = M.CellsOnEdgeOnCell[2 * G + 1];
+      }
+      for (int I = Tid; I < Cnt; I += NThr) {
+         L.N[I]    = M.NEdgesOnCell[First + I];
+         L.InvA[I] = M.InvAreaCell[First + I];
+      }
+   }
+   template <class T> __device__ void compute(const Lds &L, int Le, int ICell, int Kv) const {
+      const int ME         = M.MaxEdges;
+      const int N          = L.N[Le];
+      const Real InvA      = L.InvA[Le];
+      const size_t CStride = (size_t)M.NCellsSize * K;
+      for (int Lt = 0; Lt < NT; ++Lt) {
+         T TendV         = ldk<T>(TrTend + Lt * CStride, ICell, K, Kv);
+         T HypTmp        = splat<T>(0.0);
+         const Real *D2L = Del2Tr + Lt * CStride;
+         for (int J = 0; J < N; ++J) {
+            const T Grad = ldk<T>(D2L, L.C1[Le * ME + J], K, Kv) - ldk<T>(D2L, L.C0[Le * ME + J], K, Kv);
+            HypTmp -= L.Df4[Le * ME + J] * Grad;
+         }
+         TendV -= EddyDiff4 * HypTmp * InvA;
+         stk<T>(TrTend + Lt * CStride, ICell, K, Kv, TendV);
+      }
+   }
+};
+
+void launchTransportTend(const MeshView &M, int K, int NT, const TendParams &P, const AuxPtrs &A, Real *HTend, Real *TrTend,
+                         const Real *H, const Real *U, const Real *Tr, hipStream_t S) {
+   if (NT < 0)
+      NT = 0;
+   TransportCellBody B{M, K, NT, P, H, U, Tr, HTend, TrTend, A.Del2TracersCell};
+   launchTile(B, M.NCellsAll, K, S);
+   if (NT > 0 && P.TracerHyperDiffTendencyEnable) {
+      TransportHyperBody Hb{M, K, NT, P.EddyDiff4, A.Del2TracersCell, TrTend};
+      launchTile(Hb, M.NCellsAll, K, S);
+   }
+}
+
+} // namespace OMEGA
