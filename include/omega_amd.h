@@ -395,6 +395,24 @@ int omg_tend_compute_tracer(omg_tend *t, const omg_state *s, omg_aux *a, const o
  * for a NULL handle and for a time level out of range. */
 int omg_tend_compute_transport(omg_tend *t, const omg_state *s, omg_aux *a, const omg_tracers *tr,
                                int tracer_time_level, int thick_time_level, int vel_time_level, void *stream);
+/* Tendencies::computeTransportTendenciesAndUpdate: omg_tend_compute_transport with the two updates that follow it in a
+ * step folded into its kernels.  On every row < NCellsAll and level < NVertLayers the thickness of
+ * next_thick_time_level and the tracers of next_tracer_time_level hold, bit for bit, what omg_tend_compute_transport
+ * followed by next_h = h + coeff*LayerThicknessTend (omg_update_by_tend) and
+ * next_tracers = (tracers*h + coeff*TracerTend)/next_h (omg_update_tracers_by_tend) leave there; their level padding is not written.  With
+ * keep_tendencies the two tendency arrays hold what omg_tend_compute_transport leaves, without it their contents on
+ * those rows are unspecified.  With a VertAdv attached, a custom thickness tendency installed, or an output level equal
+ * to its input level the sequence itself runs.  Fails for a NULL handle and for a time level out of range. */
+int omg_tend_compute_transport_update(omg_tend *t, omg_state *s, omg_aux *a, omg_tracers *tr, int tracer_time_level,
+                                      int thick_time_level, int vel_time_level, int next_thick_time_level,
+                                      int next_tracer_time_level, double coeff, int keep_tendencies, void *stream);
+/* Tendencies::computeMomentumTendencies: the fused RHS without its tracer half.  NormalVelocityTend (rows < NEdgesAll)
+ * and LayerThicknessTend (rows < NCellsAll) end up, bit for bit, as omg_tend_compute_all with the same arguments leaves
+ * them, attached PressureGrad / VertAdv terms included; TracerTend and Del2TracersCell are not written.  With a custom
+ * tendency installed, or off the fused RHS, omg_tend_compute_all itself runs (TracerTend is then written too).  Fails
+ * for a NULL handle and for a time level out of range. */
+int omg_tend_compute_momentum(omg_tend *t, const omg_state *s, omg_aux *a, const omg_tracers *tr, int tracer_time_level,
+                              int thick_time_level, int vel_time_level, void *stream);
 int omg_tend_compute_thickness_only(omg_tend *t, const omg_state *s, omg_aux *a, int thick_time_level,
                                     int vel_time_level, void *stream);
 int omg_tend_compute_velocity_only(omg_tend *t, const omg_state *s, omg_aux *a, int thick_time_level,
@@ -458,6 +476,13 @@ int omg_stepper_change_time_step(omg_stepper *st, double time_step_seconds);
  * (out may alias in) */
 int omg_update_by_tend(double *out_dev, const double *in_dev, const double *tend_dev, double coeff, int n_rows,
                        int nvertlayers, void *stream);
+/* the update kernel of TimeStepper::updateTracersByTend (O/src/timeStepping/TimeStepper.cpp:447-469) on raw device
+ * arrays: next[l][r][k] = (cur[l][r][k]*h_cur[r][k] + coeff*tend[l][r][k]) / h_next[r][k] for l < n_tracers, r < n_rows
+ * and every k < row_length, the ROW LENGTH of the arrays (omg_level_pitch(K) for the library's own); the tracer planes
+ * are rows_size rows apart.  omg_update_by_tend's nvertlayers is a row length in the same sense. */
+int omg_update_tracers_by_tend(double *next_dev, const double *cur_dev, const double *h_next_dev, const double *h_cur_dev,
+                               const double *tend_dev, double coeff, int n_tracers, int n_rows, int rows_size,
+                               int row_length, void *stream);
 int omg_stepper_coeff_seconds(double mult, double time_step_seconds, double *out);
 
 /* ---- VertCoord (O/src/ocn/VertCoord.h:28-209, VertCoord.cpp:484-864) and Eos (O/src/ocn/Eos.h:278-328,
@@ -712,6 +737,13 @@ int omg_stepper_attach_barotropic(omg_stepper *st, omg_btr *b, int nsub);
  * omg_tend_compute_transport (two launches) instead of the two group calls (five); the step's result is the same bit
  * for bit either way.  Fails for any other stepper type. */
 int omg_stepper_set_fused_transport(omg_stepper *st, int on);
+/* SplitExplicitStepper::UseMomentumRHS: the first evaluation of a step through omg_tend_compute_momentum instead of
+ * omg_tend_compute_all.  SplitExplicitStepper::FoldUpdates: with the fused transport on, the transport tendencies and
+ * the thickness and tracer updates through omg_tend_compute_transport_update (keep_tendencies = 1) instead of three
+ * calls (with tracers and TracerHyperDiffTendencyEnable off the three calls run: the folded call is no faster there).
+ * The step's result is the same bit for bit under every combination.  Both fail for any other stepper type. */
+int omg_stepper_set_momentum_rhs(omg_stepper *st, int on);
+int omg_stepper_set_folded_updates(omg_stepper *st, int on);
 /* "BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean", "BtrTendMean" ([NEdgesSize]), "SSH" ([NCellsSize]), "BclVelocity"
  * ([NEdgesSize][NVertLayers]); all zero at creation */
 int omg_btr_device_ptr(const omg_btr *b, const char *name, double **dev, size_t *n);

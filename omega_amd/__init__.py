@@ -1445,6 +1445,24 @@ class Tendencies(_Handle):
         arrays are not written."""
         _chk(lib().omg_tend_compute_transport(self.h, state.h, aux.h, tracers.h, tracer_tl, thick_tl, vel_tl, _sh(stream)))
 
+    def compute_transport_tendencies_and_update(self, state, aux, tracers, tracer_tl=0, thick_tl=0, vel_tl=0,
+                                                next_thick_tl=1, next_tracer_tl=1, coeff=0.0, keep_tendencies=True,
+                                                stream=None):
+        """Tendencies::computeTransportTendenciesAndUpdate: compute_transport_tendencies with the thickness and tracer
+        updates folded into its kernels.  The thickness of next_thick_tl and the tracers of next_tracer_tl hold, bit for
+        bit on rows < NCellsAll and levels < K, what the transport call followed by update_by_tend and
+        update_tracers_by_tend leave there; with keep_tendencies the tendency arrays are the transport call's, without
+        it their contents are unspecified."""
+        _chk(lib().omg_tend_compute_transport_update(self.h, state.h, aux.h, tracers.h, tracer_tl, thick_tl, vel_tl,
+                                                     next_thick_tl, next_tracer_tl, C.c_double(coeff),
+                                                     int(bool(keep_tendencies)), _sh(stream)))
+
+    def compute_momentum_tendencies(self, state, aux, tracers, tracer_tl=0, thick_tl=0, vel_tl=0, stream=None):
+        """Tendencies::computeMomentumTendencies: NormalVelocityTend and LayerThicknessTend as compute_all_tendencies
+        leaves them, bit for bit, attached terms included, from the fused RHS without its tracer half; TracerTend and
+        Del2TracersCell are not written (with a custom tendency installed compute_all_tendencies itself runs)."""
+        _chk(lib().omg_tend_compute_momentum(self.h, state.h, aux.h, tracers.h, tracer_tl, thick_tl, vel_tl, _sh(stream)))
+
     def compute_thickness_tendencies_only(self, state, aux, thick_tl=0, vel_tl=0, stream=None):
         _chk(lib().omg_tend_compute_thickness_only(self.h, state.h, aux.h, thick_tl, vel_tl, _sh(stream)))
 
@@ -1544,6 +1562,17 @@ class TimeStepper(_Handle):
         Tendencies.compute_transport_tendencies instead of the two group calls; raises on any other kind."""
         _chk(lib().omg_stepper_set_fused_transport(self.h, int(on)))
 
+    def set_momentum_rhs(self, on: bool):
+        """SplitExplicitStepper::UseMomentumRHS: the step's first evaluation through
+        Tendencies.compute_momentum_tendencies instead of compute_all_tendencies; raises on any other kind."""
+        _chk(lib().omg_stepper_set_momentum_rhs(self.h, int(on)))
+
+    def set_folded_updates(self, on: bool):
+        """SplitExplicitStepper::FoldUpdates: with the fused transport on, the transport tendencies and the thickness
+        and tracer updates through Tendencies.compute_transport_tendencies_and_update (not with tracers and their
+        hyperdiffusion term off: no faster there); raises on any other kind."""
+        _chk(lib().omg_stepper_set_folded_updates(self.h, int(on)))
+
     def do_step(self, state: OceanState, stream=None):
         _chk(lib().omg_stepper_do_step(self.h, state.h, _sh(stream)))
 
@@ -1573,6 +1602,15 @@ def update_by_tend(out_ptr: int, in_ptr: int, tend_ptr: int, coeff: float, n_row
     """out = in + coeff * tend on raw [n_rows][k] device arrays (TimeStepper::update*ByTend's kernel)."""
     _chk(lib().omg_update_by_tend(C.c_void_p(out_ptr), C.c_void_p(in_ptr), C.c_void_p(tend_ptr), C.c_double(coeff),
                                   n_rows, k, C.c_void_p(stream_handle) if stream_handle else None))
+
+
+def update_tracers_by_tend(next_ptr: int, cur_ptr: int, h_next_ptr: int, h_cur_ptr: int, tend_ptr: int, coeff: float,
+                           n_tracers: int, n_rows: int, rows_size: int, k: int, stream_handle=None):
+    """next = (cur*h_cur + coeff*tend)/h_next on raw device arrays of row length k, tracer planes rows_size rows apart
+    (TimeStepper::updateTracersByTend's kernel)."""
+    _chk(lib().omg_update_tracers_by_tend(C.c_void_p(next_ptr), C.c_void_p(cur_ptr), C.c_void_p(h_next_ptr),
+                                          C.c_void_p(h_cur_ptr), C.c_void_p(tend_ptr), C.c_double(coeff), n_tracers,
+                                          n_rows, rows_size, k, C.c_void_p(stream_handle) if stream_handle else None))
 
 
 def coeff_seconds(mult: float, dt: float) -> float:

@@ -26,24 +26,34 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    const R8 T0 = simTime();
    // R^{n} = RHS(u^{n}, h^{n}, phi^{n}, t^{n}); its velocity part is kept
    Tend->ModelTime = T0;
-   Tend->computeAllTendencies(State, AuxState, A.CurTr, CurLevel, CurLevel, S);
+   if (UseMomentumRHS) // (steps 6-7 write the other two tendencies)
+      Tend->computeMomentumTendencies(State, AuxState, A.CurTr, CurLevel, CurLevel, S);
+   else
+      Tend->computeAllTendencies(State, AuxState, A.CurTr, CurLevel, CurLevel, S);
    // the 2-D system over the step, forced by the mean of R_u^{n} less what the sub-steps compute themselves
    Btr->splitVelocityAndSSH(A.CurH, A.CurU, S);
    Btr->computeResidualForcing(A.CurH, Tend->NormalVelocityTend, S);
    Btr->subcycle(NSub, Dt / (R8)NSub, S);
    // h^{n+1} and phi^{n+1} by the transporting velocity: baroclinic u^{n} + the sub-cycle's mean flux over the thickness
    Btr->transportVelocity(A.CurU, A.NextU, S);
-   if (UseFusedTransport) {
+   // (with tracers and their hyperdiffusion term off the tracer update rides in the first transport launch, which loses a
+   // wave to it: measured no faster than the three calls, DESIGN.md section 4.9, so those run)
+   const bool Fold = UseFusedTransport && FoldUpdates && (Tend->NTracers <= 0 || Tend->Params.TracerHyperDiffTendencyEnable);
+   if (Fold) {
+      // both tendencies and both updates in the transport kernels; the tendencies are stored as the calls below do
+      Tend->computeTransportTendenciesAndUpdate(State, AuxState, A.CurTr, CurLevel, NextLevel, A.NextH, A.NextTr, Dt, true, S);
+   } else if (UseFusedTransport) {
       // both tendencies first: the tracer tendency reads h^{n} and the transporting velocity, neither of which the
-      // thickness update writes, so the order of the four calls below is free
+      // thickness update writes, so the order of the three calls below is free
       Tend->computeTransportTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
       updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
+      updateTracersByTend(A.NextTr, A.CurTr, State, NextLevel, State, CurLevel, Dt, S);
    } else {
       Tend->computeThicknessTendencies(State, AuxState, CurLevel, NextLevel, S);
       updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
       Tend->computeTracerTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
+      updateTracersByTend(A.NextTr, A.CurTr, State, NextLevel, State, CurLevel, Dt, S);
    }
-   updateTracersByTend(A.NextTr, A.CurTr, State, NextLevel, State, CurLevel, Dt, S);
    // u^{n+1} = (baroclinic u^{n} + Dt*(R_u^{n} - its mean)) + the barotropic velocity the sub-cycle ended with
    Btr->advanceVelocity(A.CurU, Tend->NormalVelocityTend, Dt, A.NextU, S);
    mixNewLevel(State, S);

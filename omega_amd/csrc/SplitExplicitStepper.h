@@ -4,9 +4,10 @@
 // has no code for it: the sequence below is this library's, as BarotropicMode's contract is.  DESIGN.md section 4.7.
 //
 // One step (Cur = 0, Next = 1, Dt = coeff(1.0), DtBtr = Dt/NSub), everything on the step's stream:
-//   1. Tend->ModelTime = T0;  Tend->computeAllTendencies(State, AuxState, CurTracers, Cur, Cur)
-//      (the fused path; an attached PressureGrad / VertAdv gets its column pass and its ordering from it).  Only
-//      NormalVelocityTend is kept.
+//   1. Tend->ModelTime = T0;  Tend->computeMomentumTendencies(State, AuxState, CurTracers, Cur, Cur)
+//      (the fused RHS without its tracer half; an attached PressureGrad / VertAdv gets its column pass and its ordering
+//      from it).  Only NormalVelocityTend is kept.  With UseMomentumRHS off: Tend->computeAllTendencies(...) with the
+//      same arguments, whose tracer half steps 6-7 overwrite.
 //   2. Btr->splitVelocityAndSSH(h[Cur], u[Cur])
 //   3. Btr->computeResidualForcing(h[Cur], NormalVelocityTend)
 //   4. Btr->subcycle(NSub, DtBtr)
@@ -19,17 +20,22 @@
 //        Tend->computeTransportTendencies(State, AuxState, CurTracers, Cur, Next)    (both tendencies, two launches)
 //        updateThicknessByTend(State, Next, State, Cur, Dt)
 //        updateTracersByTend(NextTracers, CurTracers, State, Next, State, Cur, Dt)
-//      -- the same values bit for bit: computeTransportTendencies equals the two group methods by contract, and the
-//      tracer tendency reads h[Cur] and u[Next], neither of which the thickness update (it writes h[Next]) touches.
+//      and with UseFusedTransport and FoldUpdates (and the tracer hyperdiffusion term enabled, or no tracers) the one call
+//        Tend->computeTransportTendenciesAndUpdate(State, AuxState, CurTracers, Cur, Next, h[Next], NextTracers, Dt,
+//                                                  KeepTendencies = true)            (the same two launches)
+//      -- the same values bit for bit: computeTransportTendencies equals the two group methods by contract, the folded
+//      call equals it and the two updates by contract, and the tracer tendency reads h[Cur] and u[Next], neither of
+//      which the thickness update (it writes h[Next]) touches.  The folded call leaves the level padding of h[Next] and
+//      NextTracers as it was; no kernel reads it.
 //   8. Btr->advanceVelocity(u[Cur], NormalVelocityTend, Dt, u[Next])
 //   9. mixNewLevel, updateTimeLevels, ++NStepsDone
-// Steps 6 and 7 leave NormalVelocityTend as step 1 wrote it: the group methods and computeTransportTendencies write
-// LayerThicknessTend, TracerTend and the auxiliary state only (Tendencies.cpp), so step 8 needs no copy of it.  A custom
-// thickness hook that wrote the velocity tendency would break this; the hooks are handed their own array.
+// Steps 6 and 7 leave NormalVelocityTend as step 1 wrote it: the group methods, computeTransportTendencies and the folded
+// call write LayerThicknessTend, TracerTend and the auxiliary state only (Tendencies.cpp), so step 8 needs no copy of
+// it.  A custom thickness hook that wrote the velocity tendency would break this; the hooks are handed their own array.
 //
-// The result equals these calls made one by one through the public interface, bit for bit.  A step creates no device
-// buffer, stream or event and captures nothing into a graph.  The thickness and tracer halves of step 1 are computed and
-// discarded: a velocity-only fused evaluation is not built (DESIGN.md section 4.7 has the cost).
+// The result equals these calls made one by one through the public interface, bit for bit, under every combination of
+// the three switches.  A step creates no device buffer, stream or event and captures nothing into a graph.  DESIGN.md
+// section 4.9 has the measurements behind the defaults of UseMomentumRHS and FoldUpdates.
 //
 // One rank only: BarotropicMode knows no Halo, and more sub-steps than the halo is wide need an exchange per sub-step;
 // attachBarotropic refuses a stepper whose Halo has neighbours.
@@ -55,6 +61,16 @@ class SplitExplicitStepper : public TimeStepper {
    /// instead of the two group methods (five launches); the step's result is the same bit for bit either way.
    /// DESIGN.md section 4.8 has the measurement behind the default.
    bool UseFusedTransport = true;
+   /// Step 1 through Tendencies::computeMomentumTendencies (the fused RHS without tracers) instead of
+   /// computeAllTendencies, whose tracer half steps 6-7 overwrite.  The same bits either way.
+   bool UseMomentumRHS = true;
+   /// Steps 6-7 through Tendencies::computeTransportTendenciesAndUpdate (KeepTendencies = true, fixed: dropping them is the
+   /// option of a caller of the direct call) instead of computeTransportTendencies and the two update kernels.  Has
+   /// effect only with UseFusedTransport, and only where it was measured to pay: with tracers and
+   /// Params.TracerHyperDiffTendencyEnable off the folded call is no faster than the three calls (the tracer update then
+   /// rides in the first transport launch and costs it a wave), so the step runs those.  The same bits either way.
+   /// DESIGN.md section 4.9.
+   bool FoldUpdates = true;
 
    void doStep(OceanState *State, hipStream_t S) override;
    using TimeStepper::doStep;

@@ -209,6 +209,61 @@ void Tendencies::computeTransportTendencies(const OceanState *State, const Auxil
       VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
    }
 }
+// the transport half with the two updates in its kernels' epilogues; no counterpart in the reference
+void Tendencies::computeTransportTendenciesAndUpdate(const OceanState *State, const AuxiliaryState *Aux,
+                                                     const Array3DReal &TracerArray, int ThickLvl, int VelLvl,
+                                                     const Array2DReal &NextThick, const Array3DReal &NextTracers, R8 Coeff,
+                                                     bool KeepTendencies, hipStream_t S) {
+   Pacer::Range Timer("Tend:computeTransportTendenciesAndUpdate", 1);
+   Array2DReal LayerThick, NormVel;
+   OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0 && State->getNormalVelocity(NormVel, VelLvl) == 0,
+                 "Tendencies: bad time level");
+   OMEGA_REQUIRE(NextThick.Ptr && NextThick.Ext[0] == LayerThick.Ext[0] && NextThick.Ext[1] == LayerThick.Ext[1] &&
+                     NextThick.Pitch == LayerThick.Pitch,
+                 "Tendencies::computeTransportTendenciesAndUpdate: NextThick has not the shape of the layer thickness");
+   OMEGA_REQUIRE(NTracers <= 0 || (NextTracers.Ptr && NextTracers.Ext[0] == TracerArray.Ext[0] &&
+                                   NextTracers.Ext[1] == TracerArray.Ext[1] && NextTracers.Ext[2] == TracerArray.Ext[2] &&
+                                   NextTracers.Pitch == TracerArray.Pitch),
+                 "Tendencies::computeTransportTendenciesAndUpdate: NextTracers has not the shape of the tracer array");
+   // neighbouring cells gather the inputs while a cell stores its new values: an output that is an input needs the
+   // tendencies complete first, and so do the terms a VertAdv or a hook adds after the kernels
+   const bool Aliased = NextThick.Ptr == LayerThick.Ptr || (NTracers > 0 && NextTracers.Ptr == TracerArray.Ptr);
+   if (VAdv || CustomThicknessTend || Aliased) {
+      computeTransportTendencies(State, Aux, TracerArray, ThickLvl, VelLvl, S);
+      launchUpdateByTend(Mesh->NCellsAll, NextThick.Pitch, NextThick.Ptr, LayerThick.Ptr, LayerThicknessTend.Ptr, Coeff, S);
+      launchUpdateTracersByTend(NTracers, Mesh->NCellsAll, Mesh->NCellsSize, NextThick.Pitch, NextTracers.Ptr,
+                                TracerArray.Ptr, NextThick.Ptr, LayerThick.Ptr, TracerTend.Ptr, Coeff, S);
+      return;
+   }
+   launchTransportTendUpdate(Mesh->view(), NVertLayers, NTracers, paramsFor(Aux), Aux->ptrs(), LayerThicknessTend.Ptr,
+                             TracerTend.Ptr, LayerThick.Ptr, NormVel.Ptr, TracerArray.Ptr, NextThick.Ptr, NextTracers.Ptr,
+                             Coeff, KeepTendencies, S);
+}
+// the momentum half: the fused RHS without tracers; no counterpart in the reference
+void Tendencies::computeMomentumTendencies(const OceanState *State, const AuxiliaryState *Aux, const Array3DReal &TracerArray,
+                                           int ThickLvl, int VelLvl, hipStream_t S) {
+   if (CustomThicknessTend || CustomVelocityTend || !(UseFusedRHS && fusedRHSSupported(Mesh->view(), NVertLayers))) {
+      computeAllTendencies(State, Aux, TracerArray, ThickLvl, VelLvl, S); // (the hooks may read the whole auxiliary state)
+      return;
+   }
+   Pacer::Range Timer("Tend:computeMomentumTendencies", 1);
+   Array2DReal LayerThick, NormVel;
+   OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0 && State->getNormalVelocity(NormVel, VelLvl) == 0,
+                 "Tendencies: bad time level");
+   if (PGrad)
+      PGrad->updateColumn(LayerThick, TracerArray, S);
+   // NT = 0: level 1 computes no Del2TracersCell and level 3 is the velocity sweep alone; TracerTend is not touched
+   launchFusedRHS(Mesh->view(), NVertLayers, 0, paramsFor(Aux), Aux->ptrs(), LayerThicknessTend.Ptr, NormalVelocityTend.Ptr,
+                  TracerTend.Ptr, LayerThick.Ptr, NormVel.Ptr, TracerArray.Ptr, S, nullptr, EdgeScratch.Ptr, nullptr,
+                  Mesh->narrowView());
+   if (VAdv) { // the transport of the built-in thickness terms, then the velocity term from it
+      Pacer::Range T2("Tend:vertAdv", 2);
+      VAdv->computeAndAddThickness(LayerThicknessTend, S);
+      VAdv->addVelocityTend(NormalVelocityTend, LayerThick, NormVel, S);
+   }
+   if (PGrad)
+      addPressureGrad(S);
+}
 // Tendencies.cpp:579-600
 bool Tendencies::computeAllTendenciesStage(const OceanState *State, const AuxiliaryState *Aux,
                                            const Array3DReal &TracerArray, int ThickLvl, int VelLvl,

@@ -166,6 +166,49 @@ class Tendencies : public Registry<Tendencies> {
    /// arrays -- the call runs the two group methods instead.  A time level out of range is refused with their error.
    void computeTransportTendencies(const OceanState *State, const AuxiliaryState *AuxState, const Array3DReal &TracerArray,
                                    int ThickTimeLevel, int VelTimeLevel, hipStream_t S);
+   /// computeTransportTendencies with the thickness and tracer updates that follow it in a step folded into the
+   /// epilogues of its two kernels: the tendencies go from the registers into the new values instead of making a round
+   /// trip through HBM for the two streaming update kernels.  This library's own call.
+   ///
+   /// Contract: on every row < NCellsAll (halo included) and every level < NVertLayers, NextThick and NextTracers hold,
+   /// BIT FOR BIT, what this sequence leaves there (Cur = the thickness of ThickTimeLevel and TracerArray):
+   ///    computeTransportTendencies(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, S);
+   ///    NextThick   = CurThick + Coeff*LayerThicknessTend                       (launchUpdateByTend)
+   ///    NextTracers = (CurTracers*CurThick + Coeff*TracerTend)/NextThick        (launchUpdateTracersByTend)
+   /// With KeepTendencies, LayerThicknessTend and TracerTend hold what computeTransportTendencies leaves.  Without it
+   /// their contents on those rows are unspecified (the stores are skipped where no later kernel reads them).  Nothing
+   /// outside those rows is written either way: not the row padding, not the sentinel row, not NormalVelocityTend.
+   ///
+   /// Deviation from the sequence: the LEVEL PADDING of NextThick and NextTracers (levels NVertLayers .. pitch-1) is
+   /// NOT written.  The streaming kernels sweep whole rows and leave Cur's padding plus garbage there; nobody reads it.
+   /// Del2TracersCell is written as by computeTransportTendencies.
+   ///
+   /// Always valid: with a VertAdv attached (it adds its terms to the stored tendencies after the kernels), with a
+   /// CustomThicknessTend hook installed, or when an output aliases an input (NextThick is the thickness of
+   /// ThickTimeLevel, or NextTracers is TracerArray: neighbouring cells still gather the inputs) the call runs the
+   /// sequence above as written, level padding included.  NextThick and NextTracers must have the shape of the
+   /// thickness and of TracerArray.  A time level out of range is refused with computeTransportTendencies' error.
+   void computeTransportTendenciesAndUpdate(const OceanState *State, const AuxiliaryState *AuxState,
+                                            const Array3DReal &TracerArray, int ThickTimeLevel, int VelTimeLevel,
+                                            const Array2DReal &NextThick, const Array3DReal &NextTracers, R8 Coeff,
+                                            bool KeepTendencies, hipStream_t S);
+   /// The momentum half of the RHS: the fused RHS called without tracers, for a caller that computes the transport
+   /// half elsewhere (the Split-Explicit step keeps only NormalVelocityTend of its first evaluation; DESIGN.md section
+   /// 4.9).  This library's own call: the reference has none.
+   ///
+   /// Contract: on every row < NEdgesAll NormalVelocityTend holds, BIT FOR BIT, what
+   ///    computeAllTendencies(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, S);
+   /// leaves there, and so does LayerThicknessTend on every row < NCellsAll, attached terms included: an attached
+   /// PressureGrad gets its column pass on TracerArray (the only use of TracerArray) and its term, an attached VertAdv
+   /// its computeAndAddThickness and addVelocityTend.  LayerThicknessTend is not waste: the VertAdv derives its
+   /// VerticalTransport from it.  TracerTend and Del2TracersCell are NOT written, and nothing else of the tendency
+   /// arrays is: not the row padding, not the sentinel rows.  No graph replay and no kernel-timing events.
+   ///
+   /// Always valid: with a custom hook installed (either one), with UseFusedRHS off or on a mesh outside the fused RHS
+   /// the call runs computeAllTendencies -- TracerTend (and the auxiliary state) is then written too.  A time level out
+   /// of range is refused with computeAllTendencies' error.
+   void computeMomentumTendencies(const OceanState *State, const AuxiliaryState *AuxState, const Array3DReal &TracerArray,
+                                  int ThickTimeLevel, int VelTimeLevel, hipStream_t S);
    /// computeAllTendencies with a Runge-Kutta stage update folded into the kernels that produce the
    /// tendencies (kernels/Kernels.h: StageUpdate).  Returns false -- nothing launched -- when the
    /// stage-fused kernels do not cover this mesh / option set; the caller then uses the plain sequence.
@@ -200,6 +243,19 @@ class Tendencies : public Registry<Tendencies> {
                                    int ThickTimeLevel, int VelTimeLevel, TimeInstant Time) {
       ModelTime = Time.getSeconds();
       computeTransportTendencies(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, Stream);
+   }
+   void computeTransportTendenciesAndUpdate(const OceanState *State, const AuxiliaryState *AuxState,
+                                            const Array3DReal &TracerArray, int ThickTimeLevel, int VelTimeLevel,
+                                            const Array2DReal &NextThick, const Array3DReal &NextTracers, R8 Coeff,
+                                            bool KeepTendencies, TimeInstant Time) {
+      ModelTime = Time.getSeconds();
+      computeTransportTendenciesAndUpdate(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, NextThick, NextTracers,
+                                          Coeff, KeepTendencies, Stream);
+   }
+   void computeMomentumTendencies(const OceanState *State, const AuxiliaryState *AuxState, const Array3DReal &TracerArray,
+                                  int ThickTimeLevel, int VelTimeLevel, TimeInstant Time) {
+      ModelTime = Time.getSeconds();
+      computeMomentumTendencies(State, AuxState, TracerArray, ThickTimeLevel, VelTimeLevel, Stream);
    }
    void computeThicknessTendenciesOnly(const OceanState *State, const AuxiliaryState *AuxState, int ThickTimeLevel,
                                        int VelTimeLevel, TimeInstant Time) {

@@ -1183,6 +1183,23 @@ int omg_tend_compute_transport(omg_tend *t, const omg_state *s, omg_aux *a, cons
    t->T->computeTransportTendencies(s->S.get(), a->A.get(), tracerArray(tr, trtl), ttl, vtl, (hipStream_t)stream);
    OMG_CATCH
 }
+int omg_tend_compute_transport_update(omg_tend *t, omg_state *s, omg_aux *a, omg_tracers *tr, int trtl, int ttl, int vtl,
+                                      int next_ttl, int next_trtl, double coeff, int keep_tendencies, void *stream) {
+   OMG_TRY
+   OMG_ARG(t && s && a);
+   Array2DReal NextThick;
+   OMEGA_REQUIRE(s->S->getLayerThickness(NextThick, next_ttl) == 0, "Tendencies: bad time level");
+   t->T->computeTransportTendenciesAndUpdate(s->S.get(), a->A.get(), tracerArray(tr, trtl), ttl, vtl, NextThick,
+                                             tracerArray(tr, next_trtl), coeff, keep_tendencies != 0, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_tend_compute_momentum(omg_tend *t, const omg_state *s, omg_aux *a, const omg_tracers *tr, int trtl, int ttl,
+                              int vtl, void *stream) {
+   OMG_TRY
+   OMG_ARG(t && s && a);
+   t->T->computeMomentumTendencies(s->S.get(), a->A.get(), tracerArray(tr, trtl), ttl, vtl, (hipStream_t)stream);
+   OMG_CATCH
+}
 int omg_tend_compute_thickness_only(omg_tend *t, const omg_state *s, omg_aux *a, int ttl, int vtl, void *stream) {
    OMG_TRY
    OMG_ARG(t && s && a);
@@ -1325,6 +1342,13 @@ int omg_update_by_tend(double *out, const double *in, const double *tend, double
    OMG_TRY
    OMG_ARG(out && in && tend && n_rows >= 0 && k > 0);
    launchUpdateByTend(n_rows, k, out, in, tend, coeff, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_update_tracers_by_tend(double *next, const double *cur, const double *h_next, const double *h_cur, const double *tend,
+                               double coeff, int n_tracers, int n_rows, int rows_size, int k, void *stream) {
+   OMG_TRY
+   OMG_ARG(next && cur && h_next && h_cur && tend && n_tracers >= 0 && n_rows >= 0 && rows_size >= n_rows && k > 0);
+   launchUpdateTracersByTend(n_tracers, n_rows, rows_size, k, next, cur, h_next, h_cur, tend, coeff, (hipStream_t)stream);
    OMG_CATCH
 }
 int omg_stepper_set_start_time(omg_stepper *st, double seconds) {
@@ -1955,6 +1979,24 @@ int omg_stepper_set_fused_transport(omg_stepper *st, int on) {
    auto *Split = dynamic_cast<SplitExplicitStepper *>(st->St.get());
    OMEGA_REQUIRE(Split != nullptr, "TimeStepper: setFusedTransport: this stepper is not a Split-Explicit one");
    Split->UseFusedTransport = on != 0;
+   OMG_CATCH
+}
+/// the Split-Explicit stepper behind a handle, for the switches only it has
+static SplitExplicitStepper *splitExplicit(omg_stepper *st, const char *What) {
+   auto *Split = dynamic_cast<SplitExplicitStepper *>(st->St.get());
+   OMEGA_REQUIRE(Split != nullptr, std::string("TimeStepper: ") + What + ": this stepper is not a Split-Explicit one");
+   return Split;
+}
+int omg_stepper_set_momentum_rhs(omg_stepper *st, int on) {
+   OMG_TRY
+   OMG_ARG(st);
+   splitExplicit(st, "setMomentumRHS")->UseMomentumRHS = on != 0;
+   OMG_CATCH
+}
+int omg_stepper_set_folded_updates(omg_stepper *st, int on) {
+   OMG_TRY
+   OMG_ARG(st);
+   splitExplicit(st, "setFoldedUpdates")->FoldUpdates = on != 0;
    OMG_CATCH
 }
 static ArrRef btrLookup(const BarotropicMode &B, const char *Name) {

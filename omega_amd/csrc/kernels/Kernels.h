@@ -73,6 +73,18 @@ void launchTracerTendOnly(const MeshView &M, int K, int NT, const TendParams &P,
 /// and only then); no edge-located array of A is read or written.  NT == 0: the thickness tendency only.
 void launchTransportTend(const MeshView &M, int K, int NT, const TendParams &P, const AuxPtrs &A, Real *HTend, Real *TrTend,
                          const Real *H, const Real *U, const Real *Tr, hipStream_t S);
+/// launchTransportTend with the two update kernels folded into its epilogues
+/// (Tendencies::computeTransportTendenciesAndUpdate): on cells [0, NCellsAll) and levels [0, K), bit for bit what
+///    launchTransportTend(...);
+///    launchUpdateByTend(NCellsAll, pitch, NextH, H, HTend, Coeff, S);
+///    launchUpdateTracersByTend(NT, NCellsAll, NCellsSize, pitch, NextTr, Tr, NextH, H, TrTend, Coeff, S);
+/// leave in NextH and NextTr -- the level padding of the two is NOT written (the streaming kernels sweep it).  The same
+/// number of launches as launchTransportTend.  KeepTend: HTend and TrTend hold what launchTransportTend leaves; without
+/// it their contents on those cells are unspecified.  NextH must not be H and NextTr must not be Tr: neighbouring cells
+/// still gather the inputs while a cell stores its new values.
+void launchTransportTendUpdate(const MeshView &M, int K, int NT, const TendParams &P, const AuxPtrs &A, Real *HTend,
+                               Real *TrTend, const Real *H, const Real *U, const Real *Tr, Real *NextH, Real *NextTr,
+                               Real Coeff, bool KeepTend, hipStream_t S);
 
 // ---- fused RHS (Tendencies::computeAllTendencies): see FusedKernels.hip ----
 /// Kernel order (also the index of the optional timing events, Ev[i] recorded BEFORE kernel i,
