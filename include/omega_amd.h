@@ -42,6 +42,7 @@ typedef struct omg_pgrad omg_pgrad;     /* O/doc/design/OmegaV1GoverningEqns.md 
 typedef struct omg_vertmix_step omg_vertmix_step; /* O/doc/design/OmegaV1GoverningEqns.md section 11 (design only) */
 typedef struct omg_vertadv omg_vertadv; /* O/doc/design/OmegaV1GoverningEqns.md (design only) */
 typedef struct omg_btr omg_btr;         /* O/doc/design/TimeStepping.md, OmegaV1GoverningEqns.md section 1 (design only) */
+typedef struct omg_monoadv omg_monoadv; /* O/doc/design/Tracers.md, OmegaV0ShallowWater.md section 3.5.1 (design only) */
 
 enum { OMG_ON_CELL = 0, OMG_ON_EDGE = 1, OMG_ON_VERTEX = 2 }; /* O/src/base/Halo.h:45 MeshElement */
 
@@ -749,6 +750,33 @@ int omg_stepper_set_folded_updates(omg_stepper *st, int on);
 int omg_btr_device_ptr(const omg_btr *b, const char *name, double **dev, size_t *n);
 int omg_btr_copy_to_device(omg_btr *b, const char *name, const double *host, size_t n);
 int omg_btr_copy_to_host(const omg_btr *b, const char *name, double *host, size_t n);
+
+/* ---- MonotoneAdv: flux-corrected (Zalesak) horizontal tracer advection, the centred edge flux limited against the
+ * upwind one so that a forward update over dt creates no new extremum (O/doc/design/Tracers.md asks for a monotone
+ * scheme; the reference has no code for one).  Numerical contract: omega_amd/csrc/MonotoneAdv.h.  Arrays are
+ * level-indexed device arrays as above.  The call is asynchronous on stream and allocates nothing. ---- */
+/* flux_thickness_upwind: the edge thickness of the mass flux, 0 centred, else upwind; it must be the AuxiliaryState's
+ * choice.  Fails for a host-only mesh, nvertlayers < 1 and max_tracers < 1 */
+int omg_monoadv_create(const omg_mesh *m, int nvertlayers, int max_tracers, int flux_thickness_upwind, omg_monoadv **out);
+int omg_monoadv_destroy(omg_monoadv *a);
+/* tracer_tend_dev [ntracers][NCellsSize][pitch] += the limited flux divergence of tracers_dev (same shape) over the step
+ * h_old_dev -> h_new_dev ([NCellsSize][pitch]) of length dt by normal_velocity_dev ([NEdgesSize][pitch]); "ScaleIn" and
+ * "ScaleOut" are overwritten.  Fails for ntracers outside 1 .. max_tracers and a dt that is not finite and positive.
+ * Two launches */
+int omg_monoadv_add_tracers(omg_monoadv *a, double *tracer_tend_dev, const double *h_old_dev, const double *h_new_dev,
+                            const double *normal_velocity_dev, const double *tracers_dev, int ntracers, double dt,
+                            void *stream);
+/* "ScaleIn", "ScaleOut" ([max_tracers][NCellsSize][NVertLayers], zero at creation) */
+int omg_monoadv_device_ptr(const omg_monoadv *a, const char *name, double **dev, size_t *n);
+int omg_monoadv_copy_to_device(omg_monoadv *a, const char *name, const double *host, size_t n);
+int omg_monoadv_copy_to_host(const omg_monoadv *a, const char *name, double *host, size_t n);
+/* SplitExplicitStepper::attachMonotoneAdv (omega_amd/csrc/SplitExplicitStepper.h): the horizontal tracer advection of
+ * every step of a "Split-Explicit" stepper through a (NULL: detach); the step then runs the transport tendencies, the
+ * thickness update, omg_monoadv_add_tracers and the tracer update as four calls.  Fails for any other stepper type, an a
+ * of another mesh or layer count, max_tracers below the stepper's tracer count, a flux_thickness_upwind that differs
+ * from the AuxiliaryState's option, and while TracerHorzAdvTendencyEnable of the Tendencies is on (omg_stepper_do_step
+ * checks the last three again).  The stepper keeps a pointer to a: detach before destroying it. */
+int omg_stepper_attach_monotone_adv(omg_stepper *st, omg_monoadv *a);
 
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at

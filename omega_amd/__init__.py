@@ -1305,6 +1305,36 @@ class VertAdv(_Handle, _NamedArrays):
         return (self.mesh.NCellsSize, self.K)
 
 
+class MonotoneAdv(_Handle, _NamedArrays):
+    """MonotoneAdv (omega_amd/csrc/MonotoneAdv.h): flux-corrected horizontal tracer advection -- the centred edge flux
+    limited against the upwind one, so that a forward update over `dt` creates no new extremum.  Level-indexed inputs
+    are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles; the tendency is accumulated in
+    place: a device address (asynchronous on `stream`) or a numpy array (staged, computed, returned).  The named arrays
+    are "ScaleIn" and "ScaleOut", [max_tracers][NCellsSize][K]."""
+    _destroy, _arrays = "omg_monoadv_destroy", "omg_monoadv"
+
+    def __init__(self, mesh: HorzMesh, nvertlayers: int, max_tracers: int, flux_thickness_upwind: bool = False):
+        self.mesh, self.K, self.max_tracers = mesh, int(nvertlayers), int(max_tracers)
+        self.flux_thickness_upwind = bool(flux_thickness_upwind)
+        self._create("omg_monoadv_create", mesh.h if mesh is not None else None, int(nvertlayers), int(max_tracers),
+                     int(bool(flux_thickness_upwind)))
+
+    def add_tracers(self, tracer_tend, h_old, h_new, normal_velocity, tracers, ntracers: int, dt: float, stream=None):
+        keep, n, nt = [], self.mesh.NCellsSize, max(int(ntracers), 0)
+        ho = _level_dev(h_old, n, self.K, keep)
+        hn = _level_dev(h_new, n, self.K, keep)
+        u = _level_dev(normal_velocity, self.mesh.NEdgesSize, self.K, keep)
+        t = _stage_levels(tracers, (nt, n), self.K, keep)[0]
+        p, buf = _stage_levels(tracer_tend, (nt, n), self.K)
+        _chk(lib().omg_monoadv_add_tracers(self.h, p, ho, hn, u, t, int(ntracers), C.c_double(dt), _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def _shape(self, name):
+        return (self.max_tracers, self.mesh.NCellsSize, self.K)
+
+
 BTR_ARRAYS = {"BtrVelocity": "E", "BtrThickEdge": "E", "BtrForcing": "E", "BtrFluxMean": "E", "BtrTendMean": "E",
               "SSH": "C", "BclVelocity": "EK"}
 
@@ -1556,6 +1586,13 @@ class TimeStepper(_Handle):
         raises on any other kind, for another mesh or layer count, nsub < 1 and a halo with neighbours."""
         _chk(lib().omg_stepper_attach_barotropic(self.h, btr.h if btr is not None else None, int(nsub)))
         self._barotropic = btr  # the library keeps a pointer to it
+
+    def attach_monotone_adv(self, mono: "MonotoneAdv | None"):
+        """SplitExplicitStepper::attachMonotoneAdv: the step's horizontal tracer advection through `mono` (None
+        detaches); raises on any other kind, for another mesh or layer count, too few tracers, a flux-thickness option
+        that differs from the AuxiliaryState's, and while the Tendencies' own TracerHorzAdvTendencyEnable is on."""
+        _chk(lib().omg_stepper_attach_monotone_adv(self.h, mono.h if mono is not None else None))
+        self._monotone_adv = mono  # the library keeps a pointer to it
 
     def set_fused_transport(self, on: bool):
         """SplitExplicitStepper::UseFusedTransport (default on): the step's thickness and tracer tendencies through

@@ -1,0 +1,114 @@
+// MonotoneAdv.h -- flux-corrected horizontal tracer advection: the centred (second-order) tracer flux of every edge,
+// limited against the first-order upwind flux after Zalesak so that a forward-in-time update creates no new extremum.
+// The reference asks for such a scheme in its design documents (components/omega/doc/design/Tracers.md: "many tracers
+// will require monotonic or positive-definite advection schemes to prevent negative concentrations";
+// OmegaV0ShallowWater.md section 3.5.1 names MPAS-Ocean's flux-corrected transport) and has no code for it: its
+// TracerAuxVars offers FluxTracerEdgeOption::Center, which overshoots at every front, and Upwind, which is first order.
+// The contract below is this library's.  A limiter needs a forward update with a known Dt: steps 6-7 of
+// SplitExplicitStepper are one (SplitExplicitStepper::attachMonotoneAdv).
+//
+// Numerical contract (FP64, -ffp-contract=off, IEEE divisions, every chain in the order written; a NumPy restatement in
+// the same order is bit-identical, tests/monotone_adv_reference.py).  max and min are comparisons,
+//      max(a, b) = a < b ? b : a          min(a, b) = b < a ? b : a
+// so they mean the same in C++ and in NumPy for every operand.  All levels K < NVertLayers are swept, as by the
+// horizontal terms of Tendencies.  phi = Tracers[L], per tracer L < NTracers and level.
+//
+//  An edge e < NEdgesAll, c0, c1 = CellsOnEdge[e]:
+//      EdgeMask[e] == 0:  Fm = 0.0 exactly; no cell is read; the edge enters no sum and no max/min
+//      hE    = 0.5*(hOld[c0] + hOld[c1])
+//              (FluxThicknessUpwind: u[e] > 0 ? hOld[c0] : u[e] < 0 ? hOld[c1] : max(hOld[c0], hOld[c1]),
+//               the upwind flux thickness of LayerThicknessAuxVars)
+//      Fm    = DvEdge[e]*(hE*u[e])
+//      FLow  = Fm >= 0.0 ? Fm*phi[c0] : Fm*phi[c1]
+//      FHigh = Fm*(0.5*(phi[c0] + phi[c1]))
+//      A     = FHigh - FLow
+//    A slot of EdgesOnCell that names no local edge (e >= NEdgesAll: the rim of the halo) counts as masked out.  DvEdge
+//    of a local edge is positive.
+//
+//  Pass 1, cells c < NCellsAll, slots j < NEdgesOnCell[c] in slot order, masked-out slots skipped;
+//  s = EdgeSignOnCell[c][j] (-1 where c is c0), n the cell across the edge, InvA = 1/AreaCell[c]; every sum starts at 0.0
+//  and adds its terms one by one:
+//      PMax = PMin = phi[c];  PMax = max(PMax, phi[n]);  PMin = min(PMin, phi[n])
+//      DivLow = sum of s*FLow;            HTd  = hOld[c]*phi[c] + Dt*(DivLow*InvA)
+//      PIn  = Dt*((sum of max(s*A, 0.0))*InvA);       POut = Dt*((sum of max(-(s*A), 0.0))*InvA)
+//      QIn  = max(0.0, PMax*hNew[c] - HTd);           QOut = max(0.0, HTd - PMin*hNew[c])
+//      ScaleIn[L][c]  = PIn  > 0.0 ? min(1.0, QIn/PIn)   : 1.0
+//      ScaleOut[L][c] = POut > 0.0 ? min(1.0, QOut/POut) : 1.0
+//    (s*X is X or -X: exact.)
+//
+//  Pass 2, cells c < NCellsAll, the same slots in the same order; both cells of an edge recompute the edge from the same
+//  operands in the edge's orientation, so they agree on every bit:
+//      Sc = A >= 0.0 ? min(ScaleOut[L][c0], ScaleIn[L][c1]) : min(ScaleIn[L][c0], ScaleOut[L][c1])
+//      F  = FLow + Sc*A
+//      Tend[L][c] = Tend[L][c] + (sum of s*F)*InvA
+//    The tendency is that of h*phi, as everywhere in Tendencies.
+//
+// Only Tend[L < NTracers][c < NCellsAll][K < NVertLayers] and the same entries of ScaleIn / ScaleOut are written: no plane
+// >= NTracers, no row >= NCellsAll, not the sentinel row, not the pitch padding.  The inputs are not written.
+//
+// Halo cells are swept like owned ones.  A cell of the outermost halo layer lacks the edges beyond the rim (they are
+// masked out), so its sums are truncated and its scale factors are not those of the global mesh -- the truncation
+// BarotropicMode.h describes for its rim.  Those scale factors enter the fluxes of the layer inside it, so the result on
+// owned cells is that of the global mesh for a halo of at least 2 cell layers.
+//
+// What the limiter guarantees (Zalesak 1979; the horizontal case).  Given, on every cell-level,
+//      hOld[c] - Dt*InvA*(sum over the edges with outflow of |Fm|) >= 0          (an outflow Courant number <= 1)
+//      hNew[c] = hOld[c] - Dt*div(Fm)        up to rounding                      (the thickness the same fluxes give)
+// the low-order update HTd/hNew is a convex combination of phi[c] and the upwind neighbours, hence inside
+// [PMin, PMax]; ScaleIn caps the anti-diffusive inflow at what lifts the cell to PMax, ScaleOut the outflow at what
+// lowers it to PMin, and an edge takes the smaller of the two factors that concern it, so the updated value
+// (hOld*phi + Dt*Tend)/hNew lies in [PMin, PMax] up to rounding (tests/test_monotone_adv.py derives the margin).  A
+// constant tracer has FHigh == FLow bit for bit on every edge (0.5*(p + p) == p), so A = 0 exactly and the update is
+// the low-order one, which keeps a constant up to the rounding of hNew.  With a VertAdv attached to the Tendencies the
+// vertical term is added unlimited and the guarantee holds for the horizontal part only.
+//
+// Two launches per call, both tile sweeps over the cells (kernels/MonotoneAdvKernels.hip); no atomics and no
+// edge-located array.  Algorithmic traffic per cell-level of a hexagon mesh (3 edge rows per cell), every row counted
+// once per launch: pass 1 reads hOld, hNew and 3 u (40 B) and per tracer reads phi and writes the two scale factors
+// (24 B); pass 2 reads hOld and 3 u (32 B) and per tracer reads phi and the two scale factors and updates Tend in place
+// (40 B): 72 B + 64 B per tracer.  DESIGN.md section 4.10 has the measurement.
+#ifndef OMEGA_AMD_MONOTONEADV_H
+#define OMEGA_AMD_MONOTONEADV_H
+
+#include "Base.h"
+#include "HorzMesh.h"
+
+namespace OMEGA {
+
+struct MonotoneAdvConfig {
+   bool FluxThicknessUpwind = false; ///< must match the AuxiliaryState's FluxThickEdgeChoice (Upwind: true)
+};
+
+class MonotoneAdv : public Registry<MonotoneAdv> {
+ public:
+   /// Refuses (OmegaError) a null or host-only mesh, NVertLayers < 1 and MaxTracers < 1.  Everything is allocated here;
+   /// no call allocates.
+   MonotoneAdv(const std::string &Name, const HorzMesh *Mesh, int NVertLayers, int MaxTracers,
+               const MonotoneAdvConfig &Config);
+
+   I4 NVertLayers, MaxTracers;
+   MonotoneAdvConfig Config;
+   Array3DReal ScaleIn, ScaleOut; ///< [MaxTracers][NCellsSize][levelPitch(K)], zero at construction
+   HostArrayReal ScaleInH, ScaleOutH;
+
+   /// Tend += the limited flux divergence of Tracers[0 .. NTracers) over the step hOld -> hNew of length Dt by the
+   /// velocity u.  Refuses NTracers outside 1 .. MaxTracers, a Dt that is not finite and positive, and arrays of another
+   /// shape.  Two launches.
+   void addTracerTend(const Array3DReal &Tend, const Array2DReal &hOld, const Array2DReal &hNew, const Array2DReal &u,
+                      const Array3DReal &Tracers, int NTracers, Real Dt, hipStream_t S) const;
+
+   // ---- the reference's style of signature: on this object's `Stream` (default: the null stream)
+   hipStream_t Stream = nullptr;
+   void addTracerTend(const Array3DReal &Tend, const Array2DReal &hOld, const Array2DReal &hNew, const Array2DReal &u,
+                      const Array3DReal &Tracers, int NTracers, Real Dt) const {
+      addTracerTend(Tend, hOld, hNew, u, Tracers, NTracers, Dt, Stream);
+   }
+
+   void copyToHost(); ///< ScaleIn, ScaleOut -> their host mirrors (synchronises the device)
+
+   const HorzMesh *Mesh;
+   std::string Name;
+};
+
+} // namespace OMEGA
+#endif

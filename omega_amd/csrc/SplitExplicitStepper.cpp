@@ -17,8 +17,35 @@ void SplitExplicitStepper::attachBarotropic(BarotropicMode *B, int N) {
    NSub = N;
 }
 
+void SplitExplicitStepper::requireMonotoneAdvFits(const MonotoneAdv *M, const char *Where) const {
+   const std::string W = std::string(Where) + ": ";
+   OMEGA_REQUIRE(M->Mesh == Mesh && M->NVertLayers == Tend->LayerThicknessTend.Ext[1],
+                 W + "the MonotoneAdv was built for another mesh or layer count");
+   OMEGA_REQUIRE(M->MaxTracers >= Tend->NTracers, W + "the MonotoneAdv has MaxTracers = " + std::to_string(M->MaxTracers) +
+                                                      ", below the stepper's " + std::to_string(Tend->NTracers) + " tracers");
+   const bool AuxUpwind = AuxState->LayerThicknessAux.FluxThickEdgeChoice == FluxThickEdgeOption::Upwind;
+   OMEGA_REQUIRE(M->Config.FluxThicknessUpwind == AuxUpwind,
+                 W + "the MonotoneAdv's FluxThicknessUpwind differs from the AuxiliaryState's FluxThickEdgeChoice: the "
+                     "limiter must see the mass fluxes the thickness equation uses");
+   OMEGA_REQUIRE(!Tend->Params.TracerHorzAdvTendencyEnable,
+                 W + "TracerHorzAdvTendencyEnable is on: the Tendencies' own horizontal tracer advection and the "
+                     "MonotoneAdv would both be applied; switch the term off");
+}
+
+void SplitExplicitStepper::attachMonotoneAdv(MonotoneAdv *M) {
+   if (M == nullptr) {
+      Mono = nullptr;
+      return;
+   }
+   OMEGA_REQUIRE(Tend && Mesh && Trc && AuxState, "SplitExplicitStepper::attachMonotoneAdv: attachData first");
+   requireMonotoneAdvFits(M, "SplitExplicitStepper::attachMonotoneAdv");
+   Mono = M;
+}
+
 void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    OMEGA_REQUIRE(Btr != nullptr, "Split-Explicit doStep: no BarotropicMode is attached: attachBarotropic first");
+   if (Mono)
+      requireMonotoneAdvFits(Mono, "Split-Explicit doStep");
    requireHealthyWire();
    const int CurLevel = 0, NextLevel = 1;
    const StepArrays A = stepArrays("Split-Explicit", State);
@@ -39,7 +66,20 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    // (with tracers and their hyperdiffusion term off the tracer update rides in the first transport launch, which loses a
    // wave to it: measured no faster than the three calls, DESIGN.md section 4.9, so those run)
    const bool Fold = UseFusedTransport && FoldUpdates && (Tend->NTracers <= 0 || Tend->Params.TracerHyperDiffTendencyEnable);
-   if (Fold) {
+   if (Mono) {
+      // the limiter needs h^{n+1} and the tracer tendency's other terms: both tendencies, the thickness update, the
+      // limited flux divergence onto TracerTend, the tracer update
+      if (UseFusedTransport)
+         Tend->computeTransportTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
+      else {
+         Tend->computeThicknessTendencies(State, AuxState, CurLevel, NextLevel, S);
+         Tend->computeTracerTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
+      }
+      updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
+      if (Tend->NTracers > 0)
+         Mono->addTracerTend(Tend->TracerTend, A.CurH, A.NextH, A.NextU, A.CurTr, Tend->NTracers, Dt, S);
+      updateTracersByTend(A.NextTr, A.CurTr, State, NextLevel, State, CurLevel, Dt, S);
+   } else if (Fold) {
       // both tendencies and both updates in the transport kernels; the tendencies are stored as the calls below do
       Tend->computeTransportTendenciesAndUpdate(State, AuxState, A.CurTr, CurLevel, NextLevel, A.NextH, A.NextTr, Dt, true, S);
    } else if (UseFusedTransport) {

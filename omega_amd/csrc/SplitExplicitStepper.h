@@ -37,12 +37,26 @@
 // the three switches.  A step creates no device buffer, stream or event and captures nothing into a graph.  DESIGN.md
 // section 4.9 has the measurements behind the defaults of UseMomentumRHS and FoldUpdates.
 //
+// With a MonotoneAdv attached (attachMonotoneAdv; MonotoneAdv.h) the horizontal tracer advection of the step is the
+// flux-corrected one, and steps 6-7 are
+//        Tend->computeTransportTendencies(State, AuxState, CurTracers, Cur, Next)
+//            (with UseFusedTransport off: computeThicknessTendencies and computeTracerTendencies with these arguments)
+//        updateThicknessByTend(State, Next, State, Cur, Dt)
+//        M->addTracerTend(TracerTend, h[Cur], h[Next], u[Next], CurTracers, NTracers, Dt)
+//        updateTracersByTend(NextTracers, CurTracers, State, Next, State, Cur, Dt)
+// whatever FoldUpdates says: the limiter needs h[Next] before the tracer tendency is complete.  The Tendencies' own
+// horizontal advection term must be off (two advection terms are refused, at the attachment and again in every step);
+// TracerTend then holds the other enabled terms -- zero if there are none: every path above stores it -- and the limited
+// flux divergence is added to it.  A VertAdv attached to the Tendencies adds its vertical term in its documented place,
+// unlimited: the limiter's guarantee is for the horizontal fluxes.  With nothing attached the step is what it was.
+//
 // One rank only: BarotropicMode knows no Halo, and more sub-steps than the halo is wide need an exchange per sub-step;
 // attachBarotropic refuses a stepper whose Halo has neighbours.
 #ifndef OMEGA_AMD_SPLITEXPLICITSTEPPER_H
 #define OMEGA_AMD_SPLITEXPLICITSTEPPER_H
 
 #include "BarotropicMode.h"
+#include "MonotoneAdv.h"
 #include "TimeStepper.h"
 
 namespace OMEGA {
@@ -72,12 +86,22 @@ class SplitExplicitStepper : public TimeStepper {
    /// DESIGN.md section 4.9.
    bool FoldUpdates = true;
 
+   /// Opt-in (after attachData): the step's horizontal tracer advection through M (see above); nullptr detaches.
+   /// Refuses (OmegaError) a MonotoneAdv of another mesh or layer count, one with MaxTracers below the stepper's tracer
+   /// count, one whose FluxThicknessUpwind differs from the AuxiliaryState's FluxThickEdgeChoice, and a Tendencies whose
+   /// TracerHorzAdvTendencyEnable is on.  The stepper keeps the pointer.
+   void attachMonotoneAdv(MonotoneAdv *M);
+   MonotoneAdv *monotoneAdv() const { return Mono; }
+
    void doStep(OceanState *State, hipStream_t S) override;
    using TimeStepper::doStep;
 
  protected:
    BarotropicMode *Btr = nullptr;
    int NSub            = 0;
+   MonotoneAdv *Mono   = nullptr;
+   /// what attachMonotoneAdv refuses and doStep checks again (the options may have changed since)
+   void requireMonotoneAdvFits(const MonotoneAdv *M, const char *Where) const;
 };
 
 } // namespace OMEGA

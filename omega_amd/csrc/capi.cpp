@@ -22,6 +22,7 @@
 #include "TriDiagSolvers.h"
 #include "VertMix.h"
 #include "PressureGrad.h"
+#include "MonotoneAdv.h"
 #include "VertAdv.h"
 #include "VertMixStep.h"
 #include "BarotropicMode.h"
@@ -88,6 +89,9 @@ struct omg_vertadv {
 };
 struct omg_btr {
    std::unique_ptr<BarotropicMode> B;
+};
+struct omg_monoadv {
+   std::unique_ptr<MonotoneAdv> A;
 };
 
 static thread_local std::string LastError;
@@ -2010,6 +2014,44 @@ static ArrRef btrLookup(const BarotropicMode &B, const char *Name) {
                             Name, "BarotropicMode: no array named ");
 }
 OMG_NAMED_ARRAYS(omg_btr_copy_to_host, omg_btr_copy_to_device, omg_btr_device_ptr, omg_btr, b, btrLookup(*b->B, name))
+
+// ---- MonotoneAdv (MonotoneAdv.h)
+int omg_monoadv_create(const omg_mesh *m, int nvertlayers, int max_tracers, int flux_thickness_upwind, omg_monoadv **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   MonotoneAdvConfig Cfg;
+   Cfg.FluxThicknessUpwind = flux_thickness_upwind != 0;
+   newHandle(out, [&](omg_monoadv &R) { R.A.reset(new MonotoneAdv("Default", m->M.get(), nvertlayers, max_tracers, Cfg)); });
+   OMG_CATCH
+}
+int omg_monoadv_destroy(omg_monoadv *a) {
+   delete a;
+   return 0;
+}
+int omg_monoadv_add_tracers(omg_monoadv *a, double *tracer_tend, const double *h_old, const double *h_new,
+                            const double *normal_velocity, const double *tracers, int ntracers, double dt, void *stream) {
+   OMG_TRY
+   OMG_ARG(a && tracer_tend && h_old && h_new && normal_velocity && tracers);
+   const HorzMesh *M = a->A->Mesh;
+   const int K       = a->A->NVertLayers;
+   const int NT      = ntracers > 0 ? ntracers : 0; // (the class refuses a count outside 1 .. MaxTracers)
+   a->A->addTracerTend(tracerView(tracer_tend, NT, M->NCellsSize, K), levelView(h_old, M->NCellsSize, K),
+                       levelView(h_new, M->NCellsSize, K), levelView(normal_velocity, M->NEdgesSize, K),
+                       tracerView(tracers, NT, M->NCellsSize, K), ntracers, dt, (hipStream_t)stream);
+   OMG_CATCH
+}
+static ArrRef monoAdvLookup(const MonotoneAdv &A, const char *Name) {
+   return findNamed<ArrRef>({{"ScaleIn", arrRef(A.ScaleIn)}, {"ScaleOut", arrRef(A.ScaleOut)}}, Name,
+                            "MonotoneAdv: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_monoadv_copy_to_host, omg_monoadv_copy_to_device, omg_monoadv_device_ptr, omg_monoadv, a,
+                 monoAdvLookup(*a->A, name))
+int omg_stepper_attach_monotone_adv(omg_stepper *st, omg_monoadv *a) {
+   OMG_TRY
+   OMG_ARG(st);
+   splitExplicit(st, "attachMonotoneAdv")->attachMonotoneAdv(a ? a->A.get() : nullptr);
+   OMG_CATCH
+}
 
 // ---- batched tridiagonal solvers (TriDiagSolvers.h)
 /// a caller's [nbatch][nrow] device array of row pitch row_pitch (0: nrow) as the solvers' Array2DReal

@@ -1,0 +1,26 @@
+// MonotoneAdvKernels.h -- host-callable launcher of the kernels behind MonotoneAdv (kernels/MonotoneAdvKernels.hip).
+// Asynchronous on the given stream, raw device pointers, allocates nothing.  Level-indexed arrays are [rows][Pitch] with
+// Pitch = levelPitch(K).  The numerical contract is written down in MonotoneAdv.h.
+#ifndef OMEGA_AMD_MONOTONEADVKERNELS_H
+#define OMEGA_AMD_MONOTONEADVKERNELS_H
+
+#include "../Base.h"
+#include "../HorzMesh.h"
+
+namespace OMEGA {
+
+struct MonotoneAdvArgs {
+   int K = 0, NTracers = 0;
+   int FluxThicknessUpwind = 0;
+   Real Dt                 = 0.0;
+   const Real *HOld = nullptr, *HNew = nullptr;        ///< [NCellsSize][Pitch]
+   const Real *NormalVelocity = nullptr;               ///< [NEdgesSize][Pitch]
+   const Real *Tracers        = nullptr;               ///< [tracer][NCellsSize][Pitch]
+   Real *ScaleIn = nullptr, *ScaleOut = nullptr;       ///< [tracer][NCellsSize][Pitch]: written by launch 1, read by 2
+   Real *Tend = nullptr;                               ///< [tracer][NCellsSize][Pitch], accumulated by launch 2
+};
+/// the two launches of MonotoneAdv::addTracerTend: the scale factors of every cell, then the limited flux divergence
+void launchMonotoneAdv(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S);
+
+} // namespace OMEGA
+#endif
