@@ -22,20 +22,14 @@ struct VortVertexBody {
       Real *KiteC, *VortC, *F;
       int *Cell, *Edge;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int VD = M.VertexDegree;
-      return ldsRound8(sizeof(Real) * Tile * VD) * 2 + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(int) * Tile * VD) * 2;
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int VD = M.VertexDegree;
-      LdsCarver C{P};
       Lds L;
-      L.KiteC = C.take<Real>(Tile * VD);
-      L.VortC = C.take<Real>(Tile * VD);
-      L.F     = C.take<Real>(Tile);
-      L.Cell  = C.take<int>(Tile * VD);
-      L.Edge  = C.take<int>(Tile * VD);
+      L.KiteC = C.template take<Real>(Tile * VD);
+      L.VortC = C.template take<Real>(Tile * VD);
+      L.F     = C.template take<Real>(Tile);
+      L.Cell  = C.template take<int>(Tile * VD);
+      L.Edge  = C.template take<int>(Tile * VD);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -108,19 +102,13 @@ struct KineticCellBody {
       Real *KEC, *DivC;
       int *Edge, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) * 2 + ldsRound8(sizeof(int) * Tile * ME) +
-             ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{P};
       Lds L;
-      L.KEC  = C.take<Real>(Tile * ME);
-      L.DivC = C.take<Real>(Tile * ME);
-      L.Edge = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.KEC  = C.template take<Real>(Tile * ME);
+      L.DivC = C.template take<Real>(Tile * ME);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -206,17 +194,15 @@ template <bool DoVort, bool DoDel2> struct EdgeAux2Body {
       Real *InvDc, *InvDv2, *Mask;
       int *C0, *C1, *V0, *V1;
    };
-   size_t ldsBytes(int Tile) const { return ldsRound8(sizeof(Real) * Tile) * 3 + ldsRound8(sizeof(int) * Tile) * 4; }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      LdsCarver C{P};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.InvDc  = C.take<Real>(Tile);
-      L.InvDv2 = C.take<Real>(Tile);
-      L.Mask   = C.take<Real>(Tile);
-      L.C0     = C.take<int>(Tile);
-      L.C1     = C.take<int>(Tile);
-      L.V0     = C.take<int>(Tile);
-      L.V1     = C.take<int>(Tile);
+      L.InvDc  = C.template take<Real>(Tile);
+      L.InvDv2 = C.template take<Real>(Tile);
+      L.Mask   = C.template take<Real>(Tile);
+      L.C0     = C.template take<int>(Tile);
+      L.C1     = C.template take<int>(Tile);
+      L.V0     = C.template take<int>(Tile);
+      L.V1     = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -282,16 +268,11 @@ struct Del2VertexBody {
       Real *VortC;
       int *Edge;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int VD = M.VertexDegree;
-      return ldsRound8(sizeof(Real) * Tile * VD) + ldsRound8(sizeof(int) * Tile * VD);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int VD = M.VertexDegree;
-      LdsCarver C{P};
       Lds L;
-      L.VortC = C.take<Real>(Tile * VD);
-      L.Edge  = C.take<int>(Tile * VD);
+      L.VortC = C.template take<Real>(Tile * VD);
+      L.Edge  = C.template take<int>(Tile * VD);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -326,17 +307,12 @@ struct Del2CellBody {
       Real *DivC;
       int *Edge, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) + ldsRound8(sizeof(int) * Tile * ME) + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{P};
       Lds L;
-      L.DivC = C.take<Real>(Tile * ME);
-      L.Edge = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.DivC = C.template take<Real>(Tile * ME);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -373,11 +349,9 @@ struct SshCellBody {
    struct Lds {
       Real *BD;
    };
-   size_t ldsBytes(int Tile) const { return ldsRound8(sizeof(Real) * Tile); }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      LdsCarver C{P};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.BD = C.take<Real>(Tile);
+      L.BD = C.template take<Real>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -405,12 +379,10 @@ struct TracerEdgeBody {
    struct Lds {
       int *C0, *C1;
    };
-   size_t ldsBytes(int Tile) const { return ldsRound8(sizeof(int) * Tile) * 2; }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      LdsCarver C{P};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.C0 = C.take<int>(Tile);
-      L.C1 = C.take<int>(Tile);
+      L.C0 = C.template take<int>(Tile);
+      L.C1 = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -457,21 +429,15 @@ struct TracerCellBody {
       Real *Coef, *InvA;
       int *Edge, *C0, *C1, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(int) * Tile * ME) * 3 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{P};
       Lds L;
-      L.Coef = C.take<Real>(Tile * ME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * ME);
-      L.C0   = C.take<int>(Tile * ME);
-      L.C1   = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.Coef = C.template take<Real>(Tile * ME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.C0   = C.template take<int>(Tile * ME);
+      L.C1   = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {

@@ -45,11 +45,9 @@ bool launchFusedRHS(const MeshView &M, int K, int NT, const TendParams &P, const
       else                                                                                                         \
          launchFusedT<MN_, false, MN_, true>(*Narrow, K, NT, P, A, HTend, UTend, TrTend, H, U, Tr, S, Ev, EdgeScratch, nullptr, &M); \
       return true;
-#ifndef OMEGA_ONLY_ME6
          OMEGA_NARROW_CASE(5)
          OMEGA_NARROW_CASE(6)
          OMEGA_NARROW_CASE(7)
-#endif
 #undef OMEGA_NARROW_CASE
       default:
          break;
@@ -75,14 +73,10 @@ bool launchFusedRHS(const MeshView &M, int K, int NT, const TendParams &P, const
          launchFusedT<ME_, false>(M, K, NT, P, A, HTend, UTend, TrTend, H, U, Tr, S, Ev, EdgeScratch, nullptr);    \
       break;
    switch (M.MaxEdges) {
-#ifndef OMEGA_ONLY_ME6 // (measurement builds of a kernel experiment: hexagon meshes only, a quarter of the compile time)
       OMEGA_CASE(5)
-#endif
       OMEGA_CASE(6)
-#ifndef OMEGA_ONLY_ME6
       OMEGA_CASE(7)
       OMEGA_CASE(8)
-#endif
    default:
       return false; // callers check fusedRHSSupported()
    }

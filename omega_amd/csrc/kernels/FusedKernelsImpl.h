@@ -29,28 +29,14 @@
 #include <cstdlib>
 #include <type_traits>
 
-// tuning knobs of the tracer cell kernels (VGPR budget / levels per thread)
-#ifndef OMEGA_CELL_MINW
-#define OMEGA_CELL_MINW 2
-#endif
-#ifndef OMEGA_CELL_MAXW
-#define OMEGA_CELL_MAXW 2
-#endif
-
-#ifndef OMEGA_PVF_MINW
-#define OMEGA_PVF_MINW OMEGA_CELL_MINW
-#endif
-#ifndef OMEGA_C3_MINW
-#define OMEGA_C3_MINW OMEGA_CELL_MINW
-#endif
-#ifndef OMEGA_EDGE_MINW
-#define OMEGA_EDGE_MINW 2
-#endif
-#ifndef OMEGA_EDGE_MAXW
-#define OMEGA_EDGE_MAXW 2
-#endif
-
 namespace OMEGA {
+
+// the VGPR budget (minimum waves per SIMD) and the levels per thread of the cell and edge kernels
+constexpr int CellMinWaves = 2, CellMaxW = 2;
+constexpr int PVFinalMinWaves = CellMinWaves, Cell3MinWaves = CellMinWaves;
+constexpr int EdgeMinWaves = 2, EdgeMaxW = 2;
+// tracers per trip of the level-3 tracer loop at TME <= 6 (CellPVFinalTracerBody::tracerLoopDirect)
+constexpr int L3TracerUnroll = 1;
 
 // ---------------------------------------------------------------------------------------
 // Addressing.  Inside one array plane ([rows][pitch] doubles) an element is addressed by a 32-bit BYTE offset from
@@ -198,8 +184,8 @@ __device__ __forceinline__ dv2 pick(bool C, dv2 A, dv2 B) { return C ? A : B; }
 // ThicknessFluxDivOnCell (TendencyTerms.h:35-58), TracerAuxVars::computeVarsOnCells
 // (TracerAuxVars.h:61-91).
 template <int TME, bool Fast, bool EPI = false> struct FusedCell1Body {
-   static constexpr int MinWaves = OMEGA_CELL_MINW;
-   static constexpr int MaxW     = OMEGA_CELL_MAXW;
+   static constexpr int MinWaves = CellMinWaves;
+   static constexpr int MaxW     = CellMaxW;
    MeshView M;
    int K, NT;
    TendParams P;
@@ -212,21 +198,16 @@ template <int TME, bool Fast, bool EPI = false> struct FusedCell1Body {
       Real *KEC, *DivC, *DvS, *D2T, *InvA;
       int *Edge, *NbrF, *N;
    };
-   size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * TME) * 4 + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(int) * Tile * TME) * 2 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.KEC  = C.take<Real>(Tile * TME);
-      L.DivC = C.take<Real>(Tile * TME);
-      L.DvS  = C.take<Real>(Tile * TME);
-      L.D2T  = C.take<Real>(Tile * TME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * TME);
-      L.NbrF = C.take<int>(Tile * TME);
-      L.N    = C.take<int>(Tile);
+      L.KEC  = C.template take<Real>(Tile * TME);
+      L.DivC = C.template take<Real>(Tile * TME);
+      L.DvS  = C.template take<Real>(Tile * TME);
+      L.D2T  = C.template take<Real>(Tile * TME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * TME);
+      L.NbrF = C.template take<int>(Tile * TME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -338,8 +319,8 @@ template <int TME, bool Fast, bool EPI = false, int NR = TME, bool INLO = false,
       else
          return I;
    }
-   static constexpr int MinWaves = OMEGA_CELL_MINW;
-   static constexpr int MaxW     = OMEGA_CELL_MAXW;
+   static constexpr int MinWaves = CellMinWaves;
+   static constexpr int MaxW     = CellMaxW;
    /// tile-local index opaque per chunk (KernelCommon.h: tileKernel): 240 -> 174 VGPRs at TME = 6, this launch - 2 %.
    /// (Three waves per SIMD are then within reach -- 166 VGPRs with MinWaves = 3 -- and measured slower: + 4 % planar,
    /// + 21 % with the inlined pentagon code spilling; the level-3 bodies lose 4 % with the opaque index.)
@@ -358,30 +339,24 @@ template <int TME, bool Fast, bool EPI = false, int NR = TME, bool INLO = false,
       Real *KEC, *DivC, *DvS, *D2T, *InvA, *Wt, *FV, *KC, *VC;
       int *Edge, *NbrF, *Spoke, *Sel, *Ring, *Role, *N;
    };
-   size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * TME) * 5 + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(Real) * Tile * TME * TM1) + ldsRound8(sizeof(Real) * Tile * TME * 3) * 2 +
-             ldsRound8(sizeof(int) * Tile * TME) * 6 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.KEC   = C.take<Real>(Tile * TME);
-      L.DivC  = C.take<Real>(Tile * TME);
-      L.DvS   = C.take<Real>(Tile * TME);
-      L.D2T   = C.take<Real>(Tile * TME);
-      L.FV    = C.take<Real>(Tile * TME);
-      L.InvA  = C.take<Real>(Tile);
-      L.Wt    = C.take<Real>(Tile * TME * TM1);
-      L.KC    = C.take<Real>(Tile * TME * 3);
-      L.VC    = C.take<Real>(Tile * TME * 3);
-      L.Edge  = C.take<int>(Tile * TME);
-      L.NbrF  = C.take<int>(Tile * TME);
-      L.Spoke = C.take<int>(Tile * TME);
-      L.Sel   = C.take<int>(Tile * TME);
-      L.Ring  = C.take<int>(Tile * TME);
-      L.Role  = C.take<int>(Tile * TME);
-      L.N     = C.take<int>(Tile);
+      L.KEC   = C.template take<Real>(Tile * TME);
+      L.DivC  = C.template take<Real>(Tile * TME);
+      L.DvS   = C.template take<Real>(Tile * TME);
+      L.D2T   = C.template take<Real>(Tile * TME);
+      L.FV    = C.template take<Real>(Tile * TME);
+      L.InvA  = C.template take<Real>(Tile);
+      L.Wt    = C.template take<Real>(Tile * TME * TM1);
+      L.KC    = C.template take<Real>(Tile * TME * 3);
+      L.VC    = C.template take<Real>(Tile * TME * 3);
+      L.Edge  = C.template take<int>(Tile * TME);
+      L.NbrF  = C.template take<int>(Tile * TME);
+      L.Spoke = C.template take<int>(Tile * TME);
+      L.Sel   = C.template take<int>(Tile * TME);
+      L.Ring  = C.template take<int>(Tile * TME);
+      L.Role  = C.template take<int>(Tile * TME);
+      L.N     = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -609,24 +584,18 @@ struct FusedDel2CellBody {
       Real *DivC, *InvDc, *InvDv2, *Mask;
       int *C0, *C1, *V0, *V1, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) * 4 + ldsRound8(sizeof(int) * Tile * ME) * 4 +
-             ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{Ptr};
       Lds L;
-      L.DivC   = C.take<Real>(Tile * ME);
-      L.InvDc  = C.take<Real>(Tile * ME);
-      L.InvDv2 = C.take<Real>(Tile * ME);
-      L.Mask   = C.take<Real>(Tile * ME);
-      L.C0     = C.take<int>(Tile * ME);
-      L.C1     = C.take<int>(Tile * ME);
-      L.V0     = C.take<int>(Tile * ME);
-      L.V1     = C.take<int>(Tile * ME);
-      L.N      = C.take<int>(Tile);
+      L.DivC   = C.template take<Real>(Tile * ME);
+      L.InvDc  = C.template take<Real>(Tile * ME);
+      L.InvDv2 = C.template take<Real>(Tile * ME);
+      L.Mask   = C.template take<Real>(Tile * ME);
+      L.C0     = C.template take<int>(Tile * ME);
+      L.C1     = C.template take<int>(Tile * ME);
+      L.V0     = C.template take<int>(Tile * ME);
+      L.V1     = C.template take<int>(Tile * ME);
+      L.N      = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -676,22 +645,17 @@ struct FusedDel2VertexBody {
       Real *VortC, *InvDc, *InvDv2, *Mask;
       int *C0, *C1, *V0, *V1;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int VD = M.VertexDegree;
-      return ldsRound8(sizeof(Real) * Tile * VD) * 4 + ldsRound8(sizeof(int) * Tile * VD) * 4;
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      const int VD = M.VertexDegree;
-      LdsCarver C{Ptr};
       Lds L;
-      L.VortC  = C.take<Real>(Tile * VD);
-      L.InvDc  = C.take<Real>(Tile * VD);
-      L.InvDv2 = C.take<Real>(Tile * VD);
-      L.Mask   = C.take<Real>(Tile * VD);
-      L.C0     = C.take<int>(Tile * VD);
-      L.C1     = C.take<int>(Tile * VD);
-      L.V0     = C.take<int>(Tile * VD);
-      L.V1     = C.take<int>(Tile * VD);
+      L.VortC  = C.template take<Real>(Tile * VD);
+      L.InvDc  = C.template take<Real>(Tile * VD);
+      L.InvDv2 = C.template take<Real>(Tile * VD);
+      L.Mask   = C.template take<Real>(Tile * VD);
+      L.C0     = C.template take<int>(Tile * VD);
+      L.C1     = C.template take<int>(Tile * VD);
+      L.V0     = C.template take<int>(Tile * VD);
+      L.V1     = C.template take<int>(Tile * VD);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -738,19 +702,15 @@ template <int TME, int FL = 3> struct Del2CellRingBody {
       Real *DivC, *InvDc, *GradS, *CurlC;
       int *Nbr, *Ring, *N;
    };
-   size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * TME) * 4 + ldsRound8(sizeof(int) * Tile * TME) * 2 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.DivC  = C.take<Real>(Tile * TME);
-      L.InvDc = C.take<Real>(Tile * TME);
-      L.GradS = C.take<Real>(Tile * TME);
-      L.CurlC = C.take<Real>(Tile * TME);
-      L.Nbr   = C.take<int>(Tile * TME);
-      L.Ring  = C.take<int>(Tile * TME);
-      L.N     = C.take<int>(Tile);
+      L.DivC  = C.template take<Real>(Tile * TME);
+      L.InvDc = C.template take<Real>(Tile * TME);
+      L.GradS = C.template take<Real>(Tile * TME);
+      L.CurlC = C.template take<Real>(Tile * TME);
+      L.Nbr   = C.template take<int>(Tile * TME);
+      L.Ring  = C.template take<int>(Tile * TME);
+      L.N     = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -807,17 +767,15 @@ struct Del2VertexSelBody {
       Real *VortC, *InvDc, *Mask, *CurlC;
       int *Cell, *NbrV, *Sel;
    };
-   size_t ldsBytes(int Tile) const { return ldsRound8(sizeof(Real) * Tile * 3) * 4 + ldsRound8(sizeof(int) * Tile * 3) * 3; }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.VortC = C.take<Real>(Tile * 3);
-      L.InvDc = C.take<Real>(Tile * 3);
-      L.Mask  = C.take<Real>(Tile * 3);
-      L.CurlC = C.take<Real>(Tile * 3);
-      L.Cell  = C.take<int>(Tile * 3);
-      L.NbrV  = C.take<int>(Tile * 3);
-      L.Sel   = C.take<int>(Tile * 3);
+      L.VortC = C.template take<Real>(Tile * 3);
+      L.InvDc = C.template take<Real>(Tile * 3);
+      L.Mask  = C.template take<Real>(Tile * 3);
+      L.CurlC = C.template take<Real>(Tile * 3);
+      L.Cell  = C.template take<int>(Tile * 3);
+      L.NbrV  = C.template take<int>(Tile * 3);
+      L.Sel   = C.template take<int>(Tile * 3);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -876,32 +834,25 @@ struct FusedEdgeBody {
       Real *W, *InvDc, *InvDv, *Mask, *MaskGrav, *C2, *C4, *BD0, *BD1;
       int *EoE, *PVS, *C0, *C1, *V0, *V1, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME2 = M.MaxEdges2;
-      return ldsRound8(sizeof(Real) * Tile * ME2) + ldsRound8(sizeof(Real) * Tile) * 8 +
-             ldsRound8(sizeof(int) * Tile * ME2) + ldsRound8(sizeof(int) * Tile * ME2 * 4) +
-             ldsRound8(sizeof(int) * Tile) * 5;
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      const int ME2 = M.MaxEdges2;
-      LdsCarver C{Ptr};
       Lds L;
-      L.W        = C.take<Real>(Tile * ME2);
-      L.InvDc    = C.take<Real>(Tile);
-      L.InvDv    = C.take<Real>(Tile);
-      L.Mask     = C.take<Real>(Tile);
-      L.MaskGrav = C.take<Real>(Tile);
-      L.C2       = C.take<Real>(Tile);
-      L.C4       = C.take<Real>(Tile);
-      L.BD0      = C.take<Real>(Tile);
-      L.BD1      = C.take<Real>(Tile);
-      L.EoE      = C.take<int>(Tile * ME2);
-      L.PVS      = C.take<int>(Tile * ME2 * 4);
-      L.C0       = C.take<int>(Tile);
-      L.C1       = C.take<int>(Tile);
-      L.V0       = C.take<int>(Tile);
-      L.V1       = C.take<int>(Tile);
-      L.N        = C.take<int>(Tile);
+      L.W        = C.template take<Real>(Tile * ME2);
+      L.InvDc    = C.template take<Real>(Tile);
+      L.InvDv    = C.template take<Real>(Tile);
+      L.Mask     = C.template take<Real>(Tile);
+      L.MaskGrav = C.template take<Real>(Tile);
+      L.C2       = C.template take<Real>(Tile);
+      L.C4       = C.template take<Real>(Tile);
+      L.BD0      = C.template take<Real>(Tile);
+      L.BD1      = C.template take<Real>(Tile);
+      L.EoE      = C.template take<int>(Tile * ME2);
+      L.PVS      = C.template take<int>(Tile * ME2 * 4);
+      L.C0       = C.template take<int>(Tile);
+      L.C1       = C.template take<int>(Tile);
+      L.V0       = C.template take<int>(Tile);
+      L.V1       = C.template take<int>(Tile);
+      L.N        = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -1007,8 +958,8 @@ struct FusedEdgeBody {
 // are gathered (a+b == b+a exactly, so which end vertex / cell comes first does not matter for
 // the means; the upwind choice keeps its flag).
 template <int TME, bool Fast, bool EPI = false, bool INV = false> struct FusedEdgeChainBody {
-   static constexpr int MinWaves = OMEGA_EDGE_MINW;
-   static constexpr int MaxW     = OMEGA_EDGE_MAXW;
+   static constexpr int MinWaves = EdgeMinWaves;
+   static constexpr int MaxW     = EdgeMaxW;
    static constexpr int TM1      = TME - 1;
    MeshView M;
    int K;
@@ -1037,34 +988,27 @@ template <int TME, bool Fast, bool EPI = false, bool INV = false> struct FusedEd
       Real *W, *InvDc, *InvDv, *Mask, *MaskGrav, *C2, *C4, *BD0, *BD1, *FCh, *F0, *F1; // F*: FVertex of ChV / V0 / V1
       int *ChV, *ChF, *ChE, *C0, *C1, *V0, *V1;
    };
-   size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * 2 * TM1) + ldsRound8(sizeof(Real) * Tile) * 10 +
-             ldsRound8(sizeof(Real) * Tile * 2 * TME) +
-             ldsRound8(sizeof(int) * Tile * 2 * TME) + ldsRound8(sizeof(int) * Tile * 2 * TM1) * 2 +
-             ldsRound8(sizeof(int) * Tile) * 4;
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.W        = C.take<Real>(Tile * 2 * TM1);
-      L.InvDc    = C.take<Real>(Tile);
-      L.InvDv    = C.take<Real>(Tile);
-      L.Mask     = C.take<Real>(Tile);
-      L.MaskGrav = C.take<Real>(Tile);
-      L.C2       = C.take<Real>(Tile);
-      L.C4       = C.take<Real>(Tile);
-      L.BD0      = C.take<Real>(Tile);
-      L.BD1      = C.take<Real>(Tile);
-      L.F0       = C.take<Real>(Tile);
-      L.F1       = C.take<Real>(Tile);
-      L.FCh      = C.take<Real>(Tile * 2 * TME);
-      L.ChV      = C.take<int>(Tile * 2 * TME);
-      L.ChF      = C.take<int>(Tile * 2 * TM1);
-      L.ChE      = C.take<int>(Tile * 2 * TM1);
-      L.C0       = C.take<int>(Tile);
-      L.C1       = C.take<int>(Tile);
-      L.V0       = C.take<int>(Tile);
-      L.V1       = C.take<int>(Tile);
+      L.W        = C.template take<Real>(Tile * 2 * TM1);
+      L.InvDc    = C.template take<Real>(Tile);
+      L.InvDv    = C.template take<Real>(Tile);
+      L.Mask     = C.template take<Real>(Tile);
+      L.MaskGrav = C.template take<Real>(Tile);
+      L.C2       = C.template take<Real>(Tile);
+      L.C4       = C.template take<Real>(Tile);
+      L.BD0      = C.template take<Real>(Tile);
+      L.BD1      = C.template take<Real>(Tile);
+      L.F0       = C.template take<Real>(Tile);
+      L.F1       = C.template take<Real>(Tile);
+      L.FCh      = C.template take<Real>(Tile * 2 * TME);
+      L.ChV      = C.template take<int>(Tile * 2 * TME);
+      L.ChF      = C.template take<int>(Tile * 2 * TM1);
+      L.ChE      = C.template take<int>(Tile * 2 * TM1);
+      L.C0       = C.template take<int>(Tile);
+      L.C1       = C.template take<int>(Tile);
+      L.V0       = C.template take<int>(Tile);
+      L.V1       = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -1202,7 +1146,7 @@ template <int TME, bool Fast, bool EPI = false, bool INV = false> struct FusedEd
 // form.  Side = 0 launches first and stores the running sums; Side = 1 continues each sum from the
 // stored value, so the additions happen in exactly the reference's order.
 template <int TME, bool Fast, int Side, int NR = TME> struct CellPVBody {
-   static constexpr int MinWaves = OMEGA_CELL_MINW;
+   static constexpr int MinWaves = CellMinWaves;
    static constexpr int TM1      = TME - 1;
    MeshView M;
    int K;
@@ -1214,20 +1158,15 @@ template <int TME, bool Fast, int Side, int NR = TME> struct CellPVBody {
       Real *Wt, *FV;
       int *Edge, *NbrF, *Ring, *Role, *N;
    };
-   __host__ __device__ size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * TME * TM1) + ldsRound8(sizeof(Real) * Tile * TME) +
-             ldsRound8(sizeof(int) * Tile * TME) * 4 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.Wt   = C.take<Real>(Tile * TME * TM1);
-      L.FV   = C.take<Real>(Tile * TME);
-      L.Edge = C.take<int>(Tile * TME);
-      L.NbrF = C.take<int>(Tile * TME);
-      L.Ring = C.take<int>(Tile * TME);
-      L.Role = C.take<int>(Tile * TME);
-      L.N    = C.take<int>(Tile);
+      L.Wt   = C.template take<Real>(Tile * TME * TM1);
+      L.FV   = C.template take<Real>(Tile * TME);
+      L.Edge = C.template take<int>(Tile * TME);
+      L.NbrF = C.template take<int>(Tile * TME);
+      L.Ring = C.template take<int>(Tile * TME);
+      L.Role = C.template take<int>(Tile * TME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -1318,7 +1257,7 @@ template <int TME, bool Fast, int Side, int NR = TME> struct CellPVBody {
 // extra terms need sits on the same ring: h / KE / Div / Del2Div at this cell and the cell across,
 // RelVort / Del2RelVort at ring vertices j-1 and j (orientation folded into InvDvS).
 template <int TME, int NR = TME, bool EPI = false> struct CellPVFinalBody {
-   static constexpr int MinWaves = OMEGA_PVF_MINW;
+   static constexpr int MinWaves = PVFinalMinWaves;
    static constexpr int TM1      = TME - 1;
    MeshView M;
    int K;
@@ -1332,26 +1271,21 @@ template <int TME, int NR = TME, bool EPI = false> struct CellPVFinalBody {
       Real *Wt, *InvDc, *InvDvS, *C2, *C4, *BDn, *BDs, *FV;
       int *Edge, *NbrF, *Ring, *Role, *N;
    };
-   size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * TME * TM1) + ldsRound8(sizeof(Real) * Tile * TME) * 6 +
-             ldsRound8(sizeof(Real) * Tile) + ldsRound8(sizeof(int) * Tile * TME) * 4 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.Wt     = C.take<Real>(Tile * TME * TM1);
-      L.InvDc  = C.take<Real>(Tile * TME);
-      L.InvDvS = C.take<Real>(Tile * TME);
-      L.C2     = C.take<Real>(Tile * TME);
-      L.C4     = C.take<Real>(Tile * TME);
-      L.BDn    = C.take<Real>(Tile * TME);
-      L.FV     = C.take<Real>(Tile * TME);
-      L.BDs    = C.take<Real>(Tile);
-      L.Edge   = C.take<int>(Tile * TME);
-      L.NbrF   = C.take<int>(Tile * TME);
-      L.Ring   = C.take<int>(Tile * TME);
-      L.Role   = C.take<int>(Tile * TME);
-      L.N      = C.take<int>(Tile);
+      L.Wt     = C.template take<Real>(Tile * TME * TM1);
+      L.InvDc  = C.template take<Real>(Tile * TME);
+      L.InvDvS = C.template take<Real>(Tile * TME);
+      L.C2     = C.template take<Real>(Tile * TME);
+      L.C4     = C.template take<Real>(Tile * TME);
+      L.BDn    = C.template take<Real>(Tile * TME);
+      L.FV     = C.template take<Real>(Tile * TME);
+      L.BDs    = C.template take<Real>(Tile);
+      L.Edge   = C.template take<int>(Tile * TME);
+      L.NbrF   = C.template take<int>(Tile * TME);
+      L.Ring   = C.template take<int>(Tile * TME);
+      L.Role   = C.template take<int>(Tile * TME);
+      L.N      = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -1487,7 +1421,7 @@ template <int TME, int NR = TME, int FL = 3> struct CellPVFinalTracerBody {
       else
          return I;
    }
-   static constexpr int MinWaves = OMEGA_PVF_MINW;
+   static constexpr int MinWaves = PVFinalMinWaves;
    static constexpr int TM1      = TME - 1;
    MeshView M;
    int K, NT;
@@ -1502,29 +1436,24 @@ template <int TME, int NR = TME, int FL = 3> struct CellPVFinalTracerBody {
       Real *Wt, *InvDc, *InvDvS, *C2, *C4, *BDn, *CellS, *FV, *MDvS, *Df2, *Df4; // CellS[2 Le] = BottomDepth, [2 Le + 1] = 1/Area
       int *Edge, *NbrF, *Ring, *Role, *N;
    };
-   __host__ __device__ size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * TME * TM1) + ldsRound8(sizeof(Real) * Tile * TME) * 9 +
-             ldsRound8(sizeof(Real) * Tile) * 2 + ldsRound8(sizeof(int) * Tile * TME) * 4 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.Wt     = C.take<Real>(Tile * TME * TM1);
-      L.InvDc  = C.take<Real>(Tile * TME);
-      L.InvDvS = C.take<Real>(Tile * TME);
-      L.C2     = C.take<Real>(Tile * TME);
-      L.C4     = C.take<Real>(Tile * TME);
-      L.BDn    = C.take<Real>(Tile * TME);
-      L.FV     = C.take<Real>(Tile * TME);
-      L.MDvS   = C.take<Real>(Tile * TME);
-      L.Df2    = C.take<Real>(Tile * TME);
-      L.Df4    = C.take<Real>(Tile * TME);
-      L.CellS  = C.take<Real>(Tile * 2);
-      L.Edge   = C.take<int>(Tile * TME);
-      L.NbrF   = C.take<int>(Tile * TME);
-      L.Ring   = C.take<int>(Tile * TME);
-      L.Role   = C.take<int>(Tile * TME);
-      L.N      = C.take<int>(Tile);
+      L.Wt     = C.template take<Real>(Tile * TME * TM1);
+      L.InvDc  = C.template take<Real>(Tile * TME);
+      L.InvDvS = C.template take<Real>(Tile * TME);
+      L.C2     = C.template take<Real>(Tile * TME);
+      L.C4     = C.template take<Real>(Tile * TME);
+      L.BDn    = C.template take<Real>(Tile * TME);
+      L.FV     = C.template take<Real>(Tile * TME);
+      L.MDvS   = C.template take<Real>(Tile * TME);
+      L.Df2    = C.template take<Real>(Tile * TME);
+      L.Df4    = C.template take<Real>(Tile * TME);
+      L.CellS  = C.template take<Real>(Tile * 2);
+      L.Edge   = C.template take<int>(Tile * TME);
+      L.NbrF   = C.template take<int>(Tile * TME);
+      L.Ring   = C.template take<int>(Tile * TME);
+      L.Role   = C.template take<int>(Tile * TME);
+      L.N      = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -1678,10 +1607,7 @@ template <int TME, int NR = TME, int FL = 3> struct CellPVFinalTracerBody {
       const T(&Uj)[TME] = R.Uj;
       const Real InvA      = L.CellS[2 * Le + 1];
       const size_t CStride = (size_t)M.NCellsSize * K;
-#ifndef OMEGA_L3_TRUNROLL
-#define OMEGA_L3_TRUNROLL 1
-#endif
-      constexpr int TU = TME <= 6 ? OMEGA_L3_TRUNROLL : 1; // tracers per trip (see FusedCellL1PVBody); registers
+      constexpr int TU = TME <= 6 ? L3TracerUnroll : 1; // tracers per trip (see FusedCellL1PVBody); registers
 #pragma nounroll
       for (int Lt = 0; Lt < NT; Lt += TU) {
          loopFence();
@@ -1747,17 +1673,24 @@ template <int TME, int NR = TME, int FL = 3> struct CellPVFinalTracerPatchBody :
       unsigned char *PIdxB, *Buf; // Buf: [2 buffers][2 arrays][NP rows][128 bytes]
       int *OKp;
    };
-   size_t ldsBytes(int Tile) const {
-      return Base::ldsBytes(Tile) + ldsRound8(sizeof(int) * NP) + ldsRound8((size_t)Tile * 8) + 16 + 8 + (size_t)4 * NP * 128;
+   /// Where the patch tables start: the bytes of the base's tables as a sum of its own.  Going on from the end of the
+   /// base's chain of pointers gives the same address but ties the patch pointers to all of the base's, which costs this
+   /// kernel SGPR spills (and scratch at TME = 7) in every instantiation.  Not a second source of truth: the sizer
+   /// refuses the launch unless this is exactly what Base::layout took (LdsSizer::resumeAt).
+   __host__ __device__ static size_t baseTablesBytes(int Tile) {
+      constexpr int TM1 = TME - 1;
+      return ldsRound8(sizeof(Real) * Tile * TME * TM1) + ldsRound8(sizeof(Real) * Tile * TME) * 9 +
+             ldsRound8(sizeof(Real) * Tile) * 2 + ldsRound8(sizeof(int) * Tile * TME) * 4 + ldsRound8(sizeof(int) * Tile);
    }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      static_cast<typename Base::Lds &>(L) = Base::carve(Ptr, Tile);
-      LdsCarver C{Ptr + Base::ldsBytes(Tile)};
-      L.PRow  = C.take<int>(NP);
-      L.PIdxB = C.take<unsigned char>(Tile * 8);
-      L.OKp   = C.take<int>(2);
-      L.Buf   = C.P + ((16u - ((unsigned)(C.P - Ptr) & 15u)) & 15u); // (pointer arithmetic only: stays an LDS address)
+      static_cast<typename Base::Lds &>(L) = Base::layout(C, Tile);
+      C.resumeAt(baseTablesBytes(Tile));
+      L.PRow  = C.template take<int>(NP);
+      L.PIdxB = C.template take<unsigned char>(Tile * 8);
+      L.OKp   = C.template take<int>(2);
+      C.align16(); // (the transfers land 16 bytes per lane)
+      L.Buf = C.template take<unsigned char>(4 * NP * 128);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -1901,23 +1834,21 @@ template <bool Fast> struct EdgeFinalBody {
       Real *InvDc, *InvDv, *Mask, *MaskGrav, *C2, *C4, *BD0, *BD1;
       int *C0, *C1, *V0, *V1, *Reg;
    };
-   size_t ldsBytes(int Tile) const { return ldsRound8(sizeof(Real) * Tile) * 8 + ldsRound8(sizeof(int) * Tile) * 5; }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.InvDc    = C.take<Real>(Tile);
-      L.InvDv    = C.take<Real>(Tile);
-      L.Mask     = C.take<Real>(Tile);
-      L.MaskGrav = C.take<Real>(Tile);
-      L.C2       = C.take<Real>(Tile);
-      L.C4       = C.take<Real>(Tile);
-      L.BD0      = C.take<Real>(Tile);
-      L.BD1      = C.take<Real>(Tile);
-      L.C0       = C.take<int>(Tile);
-      L.C1       = C.take<int>(Tile);
-      L.V0       = C.take<int>(Tile);
-      L.V1       = C.take<int>(Tile);
-      L.Reg      = C.take<int>(Tile);
+      L.InvDc    = C.template take<Real>(Tile);
+      L.InvDv    = C.template take<Real>(Tile);
+      L.Mask     = C.template take<Real>(Tile);
+      L.MaskGrav = C.template take<Real>(Tile);
+      L.C2       = C.template take<Real>(Tile);
+      L.C4       = C.template take<Real>(Tile);
+      L.BD0      = C.template take<Real>(Tile);
+      L.BD1      = C.template take<Real>(Tile);
+      L.C0       = C.template take<int>(Tile);
+      L.C1       = C.template take<int>(Tile);
+      L.V0       = C.template take<int>(Tile);
+      L.V1       = C.template take<int>(Tile);
+      L.Reg      = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -1996,8 +1927,8 @@ template <bool Fast> struct EdgeFinalBody {
 // L3 cell pass: tracer tendencies (TendencyTerms.h:349-480) with HTracersEdge
 // (TracerAuxVars.h:25-59) and MeanLayerThickEdge rebuilt inline; tracer loop inside.
 template <int TME, bool Fast, bool EPI = false, int FL = 3> struct FusedCell3Body {
-   static constexpr int MinWaves = OMEGA_C3_MINW;
-   static constexpr int MaxW     = OMEGA_CELL_MAXW;
+   static constexpr int MinWaves = Cell3MinWaves;
+   static constexpr int MaxW     = CellMaxW;
    MeshView M;
    int K, NT;
    TendParams P;
@@ -2009,20 +1940,15 @@ template <int TME, bool Fast, bool EPI = false, int FL = 3> struct FusedCell3Bod
       Real *MDvS, *Df2, *Df4, *InvA;
       int *Edge, *NbrF, *N;
    };
-   size_t ldsBytes(int Tile) const {
-      return ldsRound8(sizeof(Real) * Tile * TME) * 3 + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(int) * Tile * TME) * 2 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      LdsCarver C{Ptr};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.MDvS = C.take<Real>(Tile * TME);
-      L.Df2  = C.take<Real>(Tile * TME);
-      L.Df4  = C.take<Real>(Tile * TME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * TME);
-      L.NbrF = C.take<int>(Tile * TME);
-      L.N    = C.take<int>(Tile);
+      L.MDvS = C.template take<Real>(Tile * TME);
+      L.Df2  = C.template take<Real>(Tile * TME);
+      L.Df4  = C.template take<Real>(Tile * TME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * TME);
+      L.NbrF = C.template take<int>(Tile * TME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -2762,21 +2688,12 @@ void launchFusedT(const MeshView &M, int K, int NT, const TendParams &P, const A
    (const MeshView &, int, int, const TendParams &, const AuxPtrs &, Real *, Real *, Real *, const Real *, const Real *,      \
     const Real *, hipStream_t, hipEvent_t *, Real *, const StageUpdate *, const MeshView *)
 /// every instantiation the dispatcher calls, in the groups the translation units compile: X(TME, Fast, ND, HW)
-#ifdef OMEGA_ONLY_ME6 // (measurement builds of a kernel experiment: hexagon meshes only, a quarter of the compile time)
-#define OMEGA_FUSED_INSTANCES_5(X)
-#define OMEGA_FUSED_INSTANCES_5N(X)
-#define OMEGA_FUSED_INSTANCES_6N(X)
-#define OMEGA_FUSED_INSTANCES_7(X)
-#define OMEGA_FUSED_INSTANCES_7N(X)
-#define OMEGA_FUSED_INSTANCES_8(X)
-#else
 #define OMEGA_FUSED_INSTANCES_5(X) X(5, true, 5, false) X(5, false, 5, false)
 #define OMEGA_FUSED_INSTANCES_5N(X) X(5, true, 5, true) X(5, false, 5, true)
 #define OMEGA_FUSED_INSTANCES_6N(X) X(6, true, 6, true) X(6, false, 6, true)
 #define OMEGA_FUSED_INSTANCES_7(X) X(7, true, 6, false) X(7, true, 7, false) X(7, false, 7, false)
 #define OMEGA_FUSED_INSTANCES_7N(X) X(7, true, 7, true) X(7, false, 7, true)
 #define OMEGA_FUSED_INSTANCES_8(X) X(8, true, 7, false) X(8, true, 8, false) X(8, false, 8, false)
-#endif
 #define OMEGA_FUSED_INSTANCES_6A(X) X(6, true, 5, false) X(6, true, 6, false)
 #define OMEGA_FUSED_INSTANCES_6B(X) X(6, false, 6, false)
 #define OMEGA_FUSED_DEFINE(TME_, FAST_, ND_, HW_) template void launchFusedT<TME_, FAST_, ND_, HW_> OMEGA_FUSED_ARGS;

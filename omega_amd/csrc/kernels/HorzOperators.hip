@@ -21,19 +21,13 @@ struct DivergenceOnCellBody {
       Real *DvS, *InvA;
       int *Edge, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) + ldsRound8(sizeof(Real) * Tile) + ldsRound8(sizeof(int) * Tile * ME) +
-             ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{P};
       Lds L;
-      L.DvS  = C.take<Real>(Tile * ME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.DvS  = C.template take<Real>(Tile * ME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -70,13 +64,11 @@ struct GradientOnEdgeBody {
       Real *InvDc;
       int *C0, *C1;
    };
-   size_t ldsBytes(int Tile) const { return ldsRound8(sizeof(Real) * Tile) + ldsRound8(sizeof(int) * Tile) * 2; }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      LdsCarver C{P};
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       Lds L;
-      L.InvDc = C.take<Real>(Tile);
-      L.C0    = C.take<int>(Tile);
-      L.C1    = C.take<int>(Tile);
+      L.InvDc = C.template take<Real>(Tile);
+      L.C0    = C.template take<int>(Tile);
+      L.C1    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -104,17 +96,12 @@ struct CurlOnVertexBody {
       Real *DcS, *InvA;
       int *Edge;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int VD = M.VertexDegree;
-      return ldsRound8(sizeof(Real) * Tile * VD) + ldsRound8(sizeof(Real) * Tile) + ldsRound8(sizeof(int) * Tile * VD);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int VD = M.VertexDegree;
-      LdsCarver C{P};
       Lds L;
-      L.DcS  = C.take<Real>(Tile * VD);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * VD);
+      L.DcS  = C.template take<Real>(Tile * VD);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * VD);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -148,17 +135,12 @@ struct TangentialReconOnEdgeBody {
       Real *W;
       int *EoE, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME2 = M.MaxEdges2;
-      return ldsRound8(sizeof(Real) * Tile * ME2) + ldsRound8(sizeof(int) * Tile * ME2) + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int ME2 = M.MaxEdges2;
-      LdsCarver C{P};
       Lds L;
-      L.W   = C.take<Real>(Tile * ME2);
-      L.EoE = C.take<int>(Tile * ME2);
-      L.N   = C.take<int>(Tile);
+      L.W   = C.template take<Real>(Tile * ME2);
+      L.EoE = C.template take<int>(Tile * ME2);
+      L.N   = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {

@@ -88,16 +88,49 @@ __device__ __forceinline__ int xcdRemap(int B, int N) {
    return (Xcd < R ? Xcd * (Q + 1) : R * (Q + 1) + (Xcd - R) * Q) + Idx;
 }
 
+// The LDS tables of a body.  A body names them once, in `template <class Cv> Lds layout(Cv &C, int Tile) const`: a list
+// of C.take<U>(N) calls (and C.align16(), C.resumeAt()) that reads only the body's integer members, no device pointer.  The kernels
+// run it on an LdsCarver, which hands out the pointers (carve); the launchers run it on an LdsSizer, which counts the
+// bytes (ldsBytes) -- so the size of a launch's dynamic LDS block cannot disagree with what its workgroups carve from it.
+__host__ __device__ inline size_t ldsRound8(size_t B) { return ((B + 7) >> 3) << 3; }
 /// Bump allocator over the dynamic LDS block (8-byte granules).
 struct LdsCarver {
-   unsigned char *P;
-   template <class U> __device__ __forceinline__ U *take(int N) {
+   unsigned char *P, *Base;
+   template <class U> __host__ __device__ __forceinline__ U *take(int N) {
       U *R = reinterpret_cast<U *>(P);
       P += (((size_t)N * sizeof(U) + 7) >> 3) << 3;
       return R;
    }
+   /// the next table starts on a 16-byte boundary of the block (pointer arithmetic only: stays an LDS address)
+   __host__ __device__ __forceinline__ void align16() { P += (16u - ((unsigned)(P - Base) & 15u)) & 15u; }
+   /// go on at byte Off of the block: where the tables taken so far end, handed in as a value of its own (the sizer
+   /// checks that it is)
+   __host__ __device__ __forceinline__ void resumeAt(size_t Off) { P = Base + Off; }
 };
-__host__ __device__ inline size_t ldsRound8(size_t B) { return ((B + 7) >> 3) << 3; }
+/// The same calls on the host, counting (align16: the 16 bytes the padding can take at most).
+struct LdsSizer {
+   size_t Bytes = 0;
+   template <class U> U *take(int N) {
+      Bytes += ldsRound8((size_t)N * sizeof(U));
+      return nullptr;
+   }
+   void align16() { Bytes += 16; }
+   void resumeAt(size_t Off) {
+      OMEGA_REQUIRE(Off == Bytes, "LDS layout: resumeAt(" + std::to_string(Off) + ") after " + std::to_string(Bytes) +
+                                      " bytes of tables");
+   }
+};
+/// dynamic LDS bytes of a workgroup of body B with Tile elements
+template <class B> size_t ldsBytes(const B &Body, int Tile) {
+   LdsSizer C;
+   Body.layout(C, Tile);
+   return C.Bytes;
+}
+/// the pointers to B's tables in the workgroup's LDS block
+template <class B> __device__ __forceinline__ typename B::Lds carve(const B &Body, unsigned char *Ptr, int Tile) {
+   LdsCarver C{Ptr, Ptr};
+   return Body.layout(C, Tile);
+}
 
 /// Launch geometry for an N-element, K-level sweep.
 struct Geom {
@@ -183,10 +216,8 @@ template <class B> struct BodyHoistTables<B, std::enable_if_t<B::HoistTables>> {
    static constexpr bool V = true;
 };
 template <class B> __device__ __forceinline__ void chunkFence() {
-#ifndef OMEGA_NO_CHUNK_FENCE
    if constexpr (!BodyHoistTables<B>::V)
       __asm__ volatile("" ::: "memory");
-#endif
 }
 template <class B, class = void> struct BodyOpaqueLe {
    static constexpr bool V = false;
@@ -213,11 +244,10 @@ template <class B> struct BodyMaxW<B, decltype((void)B::MaxW)> {
    static constexpr int V = B::MaxW;
 };
 
-#ifndef OMEGA_LB
-#define OMEGA_LB 256
-#endif
+/// threads per workgroup the tile kernels are compiled for (makeGeom: TX * TY = 256)
+constexpr int TileLaunchBound = 256;
 template <class Body, class T>
-__global__ void __launch_bounds__(OMEGA_LB, BodyMinWaves<Body>::V)
+__global__ void __launch_bounds__(TileLaunchBound, BodyMinWaves<Body>::V)
     tileKernel(Body B, int N, int KV, int Tile, int NFull, int TailSplit) {
    extern __shared__ __align__(16) unsigned char Lds[];
    // level chunks of this workgroup: C0, C0 + CS, ...  (whole tile: gridDim.y-way split; tail tile: one chunk each)
@@ -234,15 +264,12 @@ __global__ void __launch_bounds__(OMEGA_LB, BodyMinWaves<Body>::V)
    int Cnt          = N - First;
    if (Cnt > Tile)
       Cnt = Tile;
-   typename Body::Lds L = B.carve(Lds, Tile);
+   typename Body::Lds L = carve(B, Lds, Tile);
    const int Tid        = threadIdx.y * blockDim.x + threadIdx.x;
    const int NThr       = blockDim.x * blockDim.y;
    if (Cnt > 0)
       B.stage(L, First, Cnt, Tid, NThr);
    __syncthreads();
-#ifdef OMEGA_STAGE_ONLY // measurement build: what the staging of the tables costs (time, HBM bytes)
-   return;
-#endif
    if constexpr (BodyCooperative<Body>::V) { // bodies with workgroup barriers walk the tile themselves, all threads
       B.template computeTile<T>(L, First, Cnt, C0, CS, KV);
    } else {
@@ -266,7 +293,7 @@ __global__ void __launch_bounds__(OMEGA_LB, BodyMinWaves<Body>::V)
 /// Saves a launch (what small sweeps are made of) and lets the tail of one sweep overlap the ramp of the other.
 /// Each half keeps its own XCD mapping.  Register budget and LDS are the larger of the two bodies'.
 template <class BA, class BB, class T>
-__global__ void __launch_bounds__(OMEGA_LB, (BodyMinWaves<BA>::V < BodyMinWaves<BB>::V ? BodyMinWaves<BA>::V
+__global__ void __launch_bounds__(TileLaunchBound, (BodyMinWaves<BA>::V < BodyMinWaves<BB>::V ? BodyMinWaves<BA>::V
                                                                                        : BodyMinWaves<BB>::V))
     tileKernel2(BA A, BB Bb, int NA, int NB, int KV, int Tile, int NTilesA, int NFullB, int TailSplit) {
    extern __shared__ __align__(16) unsigned char Lds[];
@@ -276,13 +303,10 @@ __global__ void __launch_bounds__(OMEGA_LB, (BodyMinWaves<BA>::V < BodyMinWaves<
       const int Ta    = xcdRemap(blockIdx.x, NTilesA);
       const int First = Ta * Tile;
       const int Cnt   = NA - First < Tile ? NA - First : Tile;
-      typename BA::Lds L = A.carve(Lds, Tile);
+      typename BA::Lds L = carve(A, Lds, Tile);
       if (Cnt > 0)
          A.stage(L, First, Cnt, Tid, NThr);
       __syncthreads();
-#ifdef OMEGA_STAGE_ONLY
-      return;
-#endif
       for (int Le = threadIdx.y; Le < Cnt; Le += blockDim.y)
          for (int Kv = blockIdx.y * blockDim.x + threadIdx.x; Kv < KV; Kv += blockDim.x * gridDim.y)
          {
@@ -302,13 +326,10 @@ __global__ void __launch_bounds__(OMEGA_LB, (BodyMinWaves<BA>::V < BodyMinWaves<
       }
       const int First = TileId * Tile;
       const int Cnt   = NB - First < Tile ? NB - First : Tile;
-      typename BB::Lds L = Bb.carve(Lds, Tile);
+      typename BB::Lds L = carve(Bb, Lds, Tile);
       if (Cnt > 0)
          Bb.stage(L, First, Cnt, Tid, NThr);
       __syncthreads();
-#ifdef OMEGA_STAGE_ONLY
-      return;
-#endif
       for (int Le = threadIdx.y; Le < Cnt; Le += blockDim.y)
          for (int Kv = C0 * blockDim.x + threadIdx.x; Kv < KV; Kv += blockDim.x * CS)
          {
@@ -337,7 +358,7 @@ template <class B> struct BodyHasKLog<B, decltype((void)std::declval<B &>().KLog
    static constexpr bool V = true;
 };
 /// Bodies that keep per-wavefront areas in LDS (the prefetch slots of CellPVFinalTracerBody) declare `int NWv`: the
-/// launchers set it to the wavefronts per workgroup before asking for ldsBytes().
+/// launchers set it to the wavefronts per workgroup before the launch.
 template <class B, class = void> struct BodyHasNWv {
    static constexpr bool V = false;
 };
@@ -361,7 +382,7 @@ template <class Body> void launchTile(const Body &B0, int N, int K, hipStream_t 
       B.KLog = K;
    Geom G           = makeGeom(N, K, BodyMaxW<Body>::V, B.K, bodyMaxTY(B));
    setWaves(B, G);
-   const size_t Lds = B.ldsBytes(G.Tile);
+   const size_t Lds = ldsBytes(B, G.Tile);
    if constexpr (BodyMaxW<Body>::V >= 2) {
       if (G.W == 2) {
          hipLaunchKernelGGL((tileKernel<Body, dv2>), G.Grid, G.Block, Lds, S, B, N, G.KV, G.Tile, G.NFull, G.TailSplit);
@@ -395,7 +416,7 @@ template <class BA, class BB> void launchTile2(const BA &A0, int NA, const BB &B
    Geom G        = makeGeom(NA + NB, K, BodyMaxW<BA>::V, A.K, TyA > TyB ? TyA : TyB);
    const int NTA = (NA + G.Tile - 1) / G.Tile, NTB = (NB + G.Tile - 1) / G.Tile;
    setWaves(A, G), setWaves(Bb, G);
-   const size_t LA = A.ldsBytes(G.Tile), LB = Bb.ldsBytes(G.Tile), Lds = LA > LB ? LA : LB;
+   const size_t LA = ldsBytes(A, G.Tile), LB = ldsBytes(Bb, G.Tile), Lds = LA > LB ? LA : LB;
    // tail split on the second body's last tiles (the combined sweep's last, partial round of workgroups)
    int NFullB = NTB, TailSplit = 1;
    dim3 Grid(NTA + NTB, G.TailSplit > 1 ? 1 : G.Grid.y, 1);
@@ -439,7 +460,7 @@ __device__ __forceinline__ void runSweep(const SweepPlan &Pl, int KV, int Tile, 
       const int Tl     = xcdRemap(blockIdx.x - Pl.TileStart[I], NTiles);
       const int First  = Tl * Tile;
       const int Cnt    = Pl.N[I] - First < Tile ? Pl.N[I] - First : Tile;
-      typename B::Lds L = Body.carve(Lds, Tile);
+      typename B::Lds L = carve(Body, Lds, Tile);
       const int Tid     = threadIdx.y * blockDim.x + threadIdx.x;
       if (Cnt > 0)
          Body.stage(L, First, Cnt, Tid, blockDim.x * blockDim.y);
@@ -466,7 +487,7 @@ template <class B, class... Bs> struct MinWavesOf<B, Bs...> {
    static constexpr int V = BodyMinWaves<B>::V < MinWavesOf<Bs...>::V ? BodyMinWaves<B>::V : MinWavesOf<Bs...>::V;
 };
 template <class T, class... Bs>
-__global__ void __launch_bounds__(OMEGA_LB, MinWavesOf<Bs...>::V) tileKernelV(SweepPlan Pl, int KV, int Tile, Bs... Bodies) {
+__global__ void __launch_bounds__(TileLaunchBound, MinWavesOf<Bs...>::V) tileKernelV(SweepPlan Pl, int KV, int Tile, Bs... Bodies) {
    extern __shared__ __align__(16) unsigned char Lds[];
    runSweep<0, T>(Pl, KV, Tile, Lds, Bodies...);
 }
@@ -500,7 +521,7 @@ void launchSweeps(int K, hipStream_t S, const int (&NIn)[1 + sizeof...(Bs)], B0 
    if (Pl.TileStart[NB] == 0)
       return;
    setWaves(X0, G), (setWaves(Xs, G), ...);
-   const size_t Lds = std::max({(size_t)X0.ldsBytes(G.Tile), (size_t)Xs.ldsBytes(G.Tile)...});
+   const size_t Lds = std::max({ldsBytes(X0, G.Tile), ldsBytes(Xs, G.Tile)...});
    const dim3 Grid(Pl.TileStart[NB], G.TailSplit > 1 ? 1 : G.Grid.y, 1);
    if constexpr (BodyMaxW<B0>::V >= 2) {
       if (G.W == 2) {

@@ -70,20 +70,14 @@ struct MonoLds {
 };
 struct MonoTables {
    MeshView M;
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ MonoLds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) + ldsRound8(sizeof(Real) * Tile) + ldsRound8(sizeof(int) * Tile * ME) * 2 +
-             ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ MonoLds carve(unsigned char *Ptr, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{Ptr};
       MonoLds L;
-      L.MDvS = C.take<Real>(Tile * ME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * ME);
-      L.Nbr  = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.MDvS = C.template take<Real>(Tile * ME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.Nbr  = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const MonoLds &L, int First, int Cnt, int Tid, int NThr) const {

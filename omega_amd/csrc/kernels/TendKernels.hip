@@ -24,19 +24,13 @@ struct ThickTendBody {
       Real *DvS, *InvA;
       int *Edge, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(int) * Tile * ME) + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *P, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{P};
       Lds L;
-      L.DvS  = C.take<Real>(Tile * ME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.DvS  = C.template take<Real>(Tile * ME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -89,28 +83,22 @@ struct VelTendBody {
       Real *W, *InvDc, *InvDv, *Mask, *MaskGrav, *C2, *C4;
       int *EoE, *C0, *C1, *V0, *V1, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME2 = M.MaxEdges2;
-      return ldsRound8(sizeof(Real) * Tile * ME2) + ldsRound8(sizeof(Real) * Tile) * 6 +
-             ldsRound8(sizeof(int) * Tile * ME2) + ldsRound8(sizeof(int) * Tile) * 5;
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      const int ME2 = M.MaxEdges2;
-      LdsCarver C{Ptr};
       Lds L;
-      L.W        = C.take<Real>(Tile * ME2);
-      L.InvDc    = C.take<Real>(Tile);
-      L.InvDv    = C.take<Real>(Tile);
-      L.Mask     = C.take<Real>(Tile);
-      L.MaskGrav = C.take<Real>(Tile);
-      L.C2       = C.take<Real>(Tile);
-      L.C4       = C.take<Real>(Tile);
-      L.EoE      = C.take<int>(Tile * ME2);
-      L.C0       = C.take<int>(Tile);
-      L.C1       = C.take<int>(Tile);
-      L.V0       = C.take<int>(Tile);
-      L.V1       = C.take<int>(Tile);
-      L.N        = C.take<int>(Tile);
+      L.W        = C.template take<Real>(Tile * ME2);
+      L.InvDc    = C.template take<Real>(Tile);
+      L.InvDv    = C.template take<Real>(Tile);
+      L.Mask     = C.template take<Real>(Tile);
+      L.MaskGrav = C.template take<Real>(Tile);
+      L.C2       = C.template take<Real>(Tile);
+      L.C4       = C.template take<Real>(Tile);
+      L.EoE      = C.template take<int>(Tile * ME2);
+      L.C0       = C.template take<int>(Tile);
+      L.C1       = C.template take<int>(Tile);
+      L.V0       = C.template take<int>(Tile);
+      L.V1       = C.template take<int>(Tile);
+      L.N        = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -208,23 +196,17 @@ struct TracerTendBody {
       Real *MDvS, *Df2, *Df4, *InvA;
       int *Edge, *C0, *C1, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) * 3 + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(int) * Tile * ME) * 3 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{Ptr};
       Lds L;
-      L.MDvS = C.take<Real>(Tile * ME);
-      L.Df2  = C.take<Real>(Tile * ME);
-      L.Df4  = C.take<Real>(Tile * ME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * ME);
-      L.C0   = C.take<int>(Tile * ME);
-      L.C1   = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.MDvS = C.template take<Real>(Tile * ME);
+      L.Df2  = C.template take<Real>(Tile * ME);
+      L.Df4  = C.template take<Real>(Tile * ME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.C0   = C.template take<int>(Tile * ME);
+      L.C1   = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {

@@ -64,24 +64,18 @@ template <int Upd> struct TransportCellBodyT : std::conditional_t<(Upd > 0), Cel
       Real *DvS, *MDvS, *Df2, *D2C, *InvA;
       int *Edge, *C0, *C1, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) * 4 + ldsRound8(sizeof(Real) * Tile) +
-             ldsRound8(sizeof(int) * Tile * ME) * 3 + ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{Ptr};
       Lds L;
-      L.DvS  = C.take<Real>(Tile * ME);
-      L.MDvS = C.take<Real>(Tile * ME);
-      L.Df2  = C.take<Real>(Tile * ME);
-      L.D2C  = C.take<Real>(Tile * ME);
-      L.InvA = C.take<Real>(Tile);
-      L.Edge = C.take<int>(Tile * ME);
-      L.C0   = C.take<int>(Tile * ME);
-      L.C1   = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.DvS  = C.template take<Real>(Tile * ME);
+      L.MDvS = C.template take<Real>(Tile * ME);
+      L.Df2  = C.template take<Real>(Tile * ME);
+      L.D2C  = C.template take<Real>(Tile * ME);
+      L.InvA = C.template take<Real>(Tile);
+      L.Edge = C.template take<int>(Tile * ME);
+      L.C0   = C.template take<int>(Tile * ME);
+      L.C1   = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
@@ -218,20 +212,14 @@ template <bool Upd> struct TransportHyperBodyT : std::conditional_t<Upd, HyperUp
       Real *Df4, *InvA;
       int *C0, *C1, *N;
    };
-   size_t ldsBytes(int Tile) const {
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
-      return ldsRound8(sizeof(Real) * Tile * ME) + ldsRound8(sizeof(Real) * Tile) + ldsRound8(sizeof(int) * Tile * ME) * 2 +
-             ldsRound8(sizeof(int) * Tile);
-   }
-   __device__ Lds carve(unsigned char *Ptr, int Tile) const {
-      const int ME = M.MaxEdges;
-      LdsCarver C{Ptr};
       Lds L;
-      L.Df4  = C.take<Real>(Tile * ME);
-      L.InvA = C.take<Real>(Tile);
-      L.C0   = C.take<int>(Tile * ME);
-      L.C1   = C.take<int>(Tile * ME);
-      L.N    = C.take<int>(Tile);
+      L.Df4  = C.template take<Real>(Tile * ME);
+      L.InvA = C.template take<Real>(Tile);
+      L.C0   = C.template take<int>(Tile * ME);
+      L.C1   = C.template take<int>(Tile * ME);
+      L.N    = C.template take<int>(Tile);
       return L;
    }
    __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {

@@ -55,8 +55,8 @@ def test_tangential_recon_known_answer(P):
 def test_interp_cell_to_edge_known_answer(P):
     M, ops = P.omesh, oa.HorzOperators(P.mesh)
     sc, exact = set_scalar_1d(M, scalar, "Cell"), set_scalar_1d(M, scalar, "Edge")
-    # (values of the oracle pin tests/test_oracle_known_answers.py::test_ho_interp; the reference's
-    # HorzOperatorsTest has no interpolation entry, AuxiliaryVarsTest covers it through the wind stress)
+    # (the planar expected errors of the reference's HorzOperatorsTest, testInterpCellToEdge: anisotropic, then
+    # isotropic; tests/test_oracle_known_answers.py::test_ho_interp pins the oracle to the same values)
     for iso, exp in ((0, (0.0026762081503380526, 0.003058198461518835)),
                      (1, (0.004279097382993937, 0.004200067675522098))):
         num = ops.interp_cell_to_edge(sc, bool(iso), M.NEdgesOwned)
