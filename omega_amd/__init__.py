@@ -1291,6 +1291,12 @@ class VertAdv(_Handle, _NamedArrays):
             device_synchronize()
         return _read_back(buf, self.K, stream)
 
+    def set_tracer_term(self, on: bool):
+        """VertAdv::TracerTermEnable (default on): off, a Tendencies this object is attached to leaves its tracer term
+        out -- for a MonotoneAdv that limits the vertical flux itself (MonotoneAdv.attach_vert_adv).  add_tracers
+        called directly does not look at it."""
+        _chk(lib().omg_vertadv_set_tracer_term(self.h, int(bool(on))))
+
     def add_velocity(self, velocity_tend, layer_thickness, normal_velocity, stream=None):
         keep = []
         h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
@@ -1318,6 +1324,12 @@ class MonotoneAdv(_Handle, _NamedArrays):
         self.flux_thickness_upwind = bool(flux_thickness_upwind)
         self._create("omg_monoadv_create", mesh.h if mesh is not None else None, int(nvertlayers), int(max_tracers),
                      int(bool(flux_thickness_upwind)))
+
+    def attach_vert_adv(self, vert_adv: "VertAdv | None"):
+        """MonotoneAdv::attachVertAdv: while attached add_tracers limits the vertical flux of `vert_adv`'s
+        VerticalTransport (as it stands) together with the horizontal ones; None detaches."""
+        _chk(lib().omg_monoadv_attach_vert_adv(self.h, vert_adv.h if vert_adv is not None else None))
+        self.vert_adv = vert_adv  # (the C++ object keeps the pointer)
 
     def add_tracers(self, tracer_tend, h_old, h_new, normal_velocity, tracers, ntracers: int, dt: float, stream=None):
         keep, n, nt = [], self.mesh.NCellsSize, max(int(ntracers), 0)

@@ -19,6 +19,12 @@ MonotoneAdv::MonotoneAdv(const std::string &Name_, const HorzMesh *Mesh_, int K,
    ScaleOutH = HostArrayReal(MaxTracers, Mesh->NCellsSize, NVertLayers);
 }
 
+void MonotoneAdv::attachVertAdv(const VertAdv *V) {
+   OMEGA_REQUIRE(V == nullptr || (V->Mesh == Mesh && V->NVertLayers == NVertLayers),
+                 "MonotoneAdv::attachVertAdv: the VertAdv was built for another mesh or layer count");
+   VAdv = V;
+}
+
 /// a tracer array of the kernel's plane stride: exactly NCellsSize rows per tracer
 static void requirePlanes(const Array3DReal &A, int NT, int Rows, int K, const char *What) {
    requireLevelArray("MonotoneAdv", A, NT, Rows, K, What);
@@ -41,6 +47,10 @@ void MonotoneAdv::addTracerTend(const Array3DReal &Tend, const Array2DReal &HOld
    A.K = NVertLayers, A.NTracers = NTracers, A.FluxThicknessUpwind = Config.FluxThicknessUpwind ? 1 : 0, A.Dt = Dt;
    A.HOld = HOld.Ptr, A.HNew = HNew.Ptr, A.NormalVelocity = U.Ptr, A.Tracers = Tracers.Ptr;
    A.ScaleIn = ScaleIn.Ptr, A.ScaleOut = ScaleOut.Ptr, A.Tend = Tend.Ptr;
+   if (VAdv) { // the 3-D form
+      A.VerticalTransport = VAdv->VerticalTransport.Ptr;
+      A.MinLayerCell = VAdv->VCoord->MinLayerCell.Ptr, A.MaxLayerCell = VAdv->VCoord->MaxLayerCell.Ptr;
+   }
    launchMonotoneAdv(Mesh->view(), A, S);
 }
 

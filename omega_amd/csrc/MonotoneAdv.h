@@ -59,8 +59,53 @@
 // lowers it to PMin, and an edge takes the smaller of the two factors that concern it, so the updated value
 // (hOld*phi + Dt*Tend)/hNew lies in [PMin, PMax] up to rounding (tests/test_monotone_adv.py derives the margin).  A
 // constant tracer has FHigh == FLow bit for bit on every edge (0.5*(p + p) == p), so A = 0 exactly and the update is
-// the low-order one, which keeps a constant up to the rounding of hNew.  With a VertAdv attached to the Tendencies the
-// vertical term is added unlimited and the guarantee holds for the horizontal part only.
+// the low-order one, which keeps a constant up to the rounding of hNew.  With a VertAdv attached to the Tendencies and
+// none attached here the vertical term is added unlimited and the guarantee holds for the horizontal part only; the
+// 3-D form below limits both.
+//
+// The 3-D form (attachVertAdv(V); same rules: FP64, -ffp-contract=off, every chain in the order written, the same max
+// and min; a NumPy restatement in the same order is bit-identical, tests/monotone_adv3d_reference.py).  Everything
+// about the horizontal edges stays as written above: Fm, FLow, FHigh, A, the slot order, the masking.
+//
+//  Interfaces of a cell c < NCellsAll with KMin .. KMax = MinLayerCell[c] .. MaxLayerCell[c] of V->VCoord,
+//  Wt = V->VerticalTransport[c] as it stands, h = hOld[c].  Interface K is the top of layer K, Wt positive upward: a
+//  positive flux leaves layer K and enters layer K-1.
+//      Wv[K]    = (KMin < K && K <= KMax) ? Wt[K] : 0.0           (a select: Wt outside the range is never used)
+//      VLow[K]  = Wv[K] > 0.0 ? Wv[K]*phi[K] : Wv[K]*phi[K-1]     (VertAdv's order-1 flux)
+//      PhiT[K]  = phi[K-1] + (h[K-1]/(h[K-1] + h[K]))*(phi[K] - phi[K-1])
+//      VHigh[K] = Wv[K]*PhiT[K]
+//      AV[K]    = VHigh[K] - VLow[K]
+//    PhiT is VertAdv's order-2 interface value, rearranged so that a constant tracer has AV == 0 bit for bit, the
+//    property A has.  At an interface outside KMin < K <= KMax -- the bottom of KMax and everything at K >= NVertLayers
+//    included -- VLow = AV = 0.0 exactly and no phi, h, ScaleIn or ScaleOut value from across it enters any arithmetic.
+//    Levels outside KMin .. KMax and land columns (MaxLayerCell < MinLayerCell) so get the horizontal form only; they
+//    are swept as above.
+//
+//  Pass 1, level K of cell c, after the horizontal slots:
+//      PMax = max(PMax, phi[K-1]), PMin = min(PMin, phi[K-1])   if KMin < K <= KMax
+//      PMax = max(PMax, phi[K+1]), PMin = min(PMin, phi[K+1])   if KMin <= K < KMax       (in this order)
+//      HTd  = hOld*phi + Dt*(((DivLow*InvA) - VLow[K]) + VLow[K+1])
+//      PIn  = Dt*((((sum of max(s*A, 0.0))*InvA)    + max(-AV[K], 0.0)) + max(AV[K+1], 0.0))
+//      POut = Dt*((((sum of max(-(s*A), 0.0))*InvA) + max(AV[K], 0.0))  + max(-AV[K+1], 0.0))
+//      QIn, QOut, ScaleIn, ScaleOut as above
+//
+//  Pass 2, the scale factors of the cell's own rows:
+//      ScV[K] = AV[K] >= 0.0 ? min(ScaleOut[K], ScaleIn[K-1]) : min(ScaleIn[K], ScaleOut[K-1])
+//      FV[K]  = VLow[K] + ScV[K]*AV[K]          (0.0 outside KMin < K <= KMax; no scale factor is read there)
+//      Tend[L][c][K] = Tend[L][c][K] + ((((sum of s*F)*InvA) - FV[K]) + FV[K+1])
+//    Layers K and K-1 evaluate interface K from the same operands, so the column telescopes exactly as the edges do.
+//
+//  The guarantee in 3-D.  Given, on every cell-level,
+//      hOld - Dt*(InvA*(sum over the edges with outflow of |Fm|) + max(Wv[K], 0) + max(-Wv[K+1], 0)) >= 0
+//      hNew = hOld + Dt*(-div(Fm) - Wv[K] + Wv[K+1])        up to rounding
+//  the update (hOld*phi + Dt*Tend)/hNew lies between the smallest and the largest phi of the cell, its edge neighbours
+//  and the levels above and below it inside the range, up to rounding (tests/test_monotone_adv_3d.py derives the margin).
+//  The vertical part needs no other cell, so the halo rule stays at 2 cell layers.  The Tendencies must not add the
+//  vertical tracer term as well: VertAdv::TracerTermEnable = false (SplitExplicitStepper::attachMonotoneAdv checks it).
+//
+//  Traffic of the 3-D form per cell-level of a hexagon mesh (the rows of the cell's own column count once per launch):
+//  pass 1 adds VerticalTransport, 48 B + 24 B per tracer; pass 2 likewise, 40 B + 40 B per tracer; and 8 B per cell and
+//  launch for the range.  DESIGN.md section 4.11.
 //
 // Two launches per call, both tile sweeps over the cells (kernels/MonotoneAdvKernels.hip); no atomics and no
 // edge-located array.  Algorithmic traffic per cell-level of a hexagon mesh (3 edge rows per cell), every row counted
@@ -72,6 +117,7 @@
 
 #include "Base.h"
 #include "HorzMesh.h"
+#include "VertAdv.h"
 
 namespace OMEGA {
 
@@ -104,10 +150,19 @@ class MonotoneAdv : public Registry<MonotoneAdv> {
       addTracerTend(Tend, hOld, hNew, u, Tracers, NTracers, Dt, Stream);
    }
 
+   /// While a VertAdv is attached addTracerTend runs the 3-D form: the same arguments, two launches, no allocation; it
+   /// reads V->VerticalTransport as it stands and the layer ranges of V->VCoord.  nullptr detaches.  Refuses (OmegaError)
+   /// a VertAdv of another mesh or layer count.
+   void attachVertAdv(const VertAdv *V);
+   const VertAdv *vertAdv() const { return VAdv; }
+
    void copyToHost(); ///< ScaleIn, ScaleOut -> their host mirrors (synchronises the device)
 
    const HorzMesh *Mesh;
    std::string Name;
+
+ private:
+   const VertAdv *VAdv = nullptr;
 };
 
 } // namespace OMEGA

@@ -30,6 +30,13 @@ void SplitExplicitStepper::requireMonotoneAdvFits(const MonotoneAdv *M, const ch
    OMEGA_REQUIRE(!Tend->Params.TracerHorzAdvTendencyEnable,
                  W + "TracerHorzAdvTendencyEnable is on: the Tendencies' own horizontal tracer advection and the "
                      "MonotoneAdv would both be applied; switch the term off");
+   if (const VertAdv *V = M->vertAdv()) { // the 3-D form: VerticalTransport must be the step's, and limited only once
+      OMEGA_REQUIRE(V == Tend->vertAdv(), W + "the MonotoneAdv's VertAdv is not the one attached to the Tendencies: its "
+                                              "VerticalTransport would not be that of the step");
+      OMEGA_REQUIRE(!V->TracerTermEnable,
+                    W + "the VertAdv's TracerTermEnable is on: the Tendencies' vertical tracer term and the MonotoneAdv's "
+                        "limited one would both be applied; switch the term off");
+   }
 }
 
 void SplitExplicitStepper::attachMonotoneAdv(MonotoneAdv *M) {

@@ -48,7 +48,10 @@
 // horizontal advection term must be off (two advection terms are refused, at the attachment and again in every step);
 // TracerTend then holds the other enabled terms -- zero if there are none: every path above stores it -- and the limited
 // flux divergence is added to it.  A VertAdv attached to the Tendencies adds its vertical term in its documented place,
-// unlimited: the limiter's guarantee is for the horizontal fluxes.  With nothing attached the step is what it was.
+// unlimited: the limiter's guarantee is then for the horizontal fluxes.  A MonotoneAdv that has that VertAdv attached
+// itself (MonotoneAdv::attachVertAdv) limits the vertical flux too; the sequence is the same -- VerticalTransport is
+// current after the transport call, h[Next] after the thickness update -- and the VertAdv's TracerTermEnable must be
+// off (two vertical terms are refused like two horizontal ones).  With nothing attached the step is what it was.
 //
 // One rank only: BarotropicMode knows no Halo, and more sub-steps than the halo is wide need an exchange per sub-step;
 // attachBarotropic refuses a stepper whose Halo has neighbours.
@@ -89,7 +92,8 @@ class SplitExplicitStepper : public TimeStepper {
    /// Opt-in (after attachData): the step's horizontal tracer advection through M (see above); nullptr detaches.
    /// Refuses (OmegaError) a MonotoneAdv of another mesh or layer count, one with MaxTracers below the stepper's tracer
    /// count, one whose FluxThicknessUpwind differs from the AuxiliaryState's FluxThickEdgeChoice, and a Tendencies whose
-   /// TracerHorzAdvTendencyEnable is on.  The stepper keeps the pointer.
+   /// TracerHorzAdvTendencyEnable is on; of a MonotoneAdv with a VertAdv attached also one whose VertAdv is not
+   /// Tend->vertAdv() or still has TracerTermEnable on.  The stepper keeps the pointer.
    void attachMonotoneAdv(MonotoneAdv *M);
    MonotoneAdv *monotoneAdv() const { return Mono; }
 

@@ -145,7 +145,7 @@ void Tendencies::computeTracerTendenciesOnly(const OceanState *State, const Auxi
    OMEGA_REQUIRE(State->getNormalVelocity(NormalVelEdge, VelLvl) == 0, "Tendencies: bad velocity time level");
    launchTracerTendOnly(Mesh->view(), NVertLayers, NTracers, paramsFor(Aux), Aux->ptrs(), TracerTend.Ptr,
                         NormalVelEdge.Ptr, TracerArray.Ptr, S);
-   if (VAdv) { // from VerticalTransport as it stands
+   if (VAdv && VAdv->TracerTermEnable) { // from VerticalTransport as it stands
       Pacer::Range T2("Tend:vertAdvTracer", 2);
       Array2DReal LayerThick;
       OMEGA_REQUIRE(State->getLayerThickness(LayerThick, ThickLvl) == 0, "Tendencies: bad thickness time level");
@@ -206,7 +206,8 @@ void Tendencies::computeTransportTendencies(const OceanState *State, const Auxil
    if (VAdv) { // the transport of the built-in thickness terms, then the tracer term from it
       Pacer::Range T2("Tend:vertAdv", 2);
       VAdv->computeAndAddThickness(LayerThicknessTend, S);
-      VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
+      if (VAdv->TracerTermEnable)
+         VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
    }
 }
 // the transport half with the two updates in its kernels' epilogues; no counterpart in the reference
@@ -319,7 +320,8 @@ void Tendencies::computeAllTendencies(const OceanState *State, const AuxiliarySt
       if (VAdv) { // the transport of the built-in thickness terms, then the three vertical-advection terms
          Pacer::Range T2("Tend:vertAdv", 2);
          VAdv->computeAndAddThickness(LayerThicknessTend, S);
-         VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
+         if (VAdv->TracerTermEnable)
+            VAdv->addTracerTend(TracerTend, LayerThick, TracerArray, NTracers, S);
          VAdv->addVelocityTend(NormalVelocityTend, LayerThick, NormVel, S);
       }
       if (PGrad)

@@ -79,6 +79,10 @@ class VertAdv : public Registry<VertAdv> {
    I4 NVertLayers;
    VertAdvConfig Config;
    Array2DReal VerticalTransport; ///< [NCellsSize][levelPitch(K)], zero at construction
+   /// false: the Tendencies leave this object's tracer term out (the tracer group, computeTransportTendencies,
+   /// computeAllTendencies), for a MonotoneAdv that limits the vertical flux itself (MonotoneAdv::attachVertAdv).
+   /// addTracerTend called directly does not look at it; the thickness and velocity terms are not concerned.
+   bool TracerTermEnable = true;
    HostArrayReal VerticalTransportH;
 
    void computeVerticalTransport(const Array2DReal &ThickTend, hipStream_t S) const;

@@ -1867,6 +1867,12 @@ int omg_vertadv_add_velocity(omg_vertadv *a, double *velocity_tend, const double
                          levelView(normal_velocity, M->NEdgesSize, K), (hipStream_t)stream);
    OMG_CATCH
 }
+int omg_vertadv_set_tracer_term(omg_vertadv *a, int on) {
+   OMG_TRY
+   OMG_ARG(a);
+   a->A->TracerTermEnable = on != 0;
+   OMG_CATCH
+}
 int omg_vertadv_max_layers(int *n) {
    OMG_TRY
    OMG_ARG(n);
@@ -2038,6 +2044,12 @@ int omg_monoadv_add_tracers(omg_monoadv *a, double *tracer_tend, const double *h
    a->A->addTracerTend(tracerView(tracer_tend, NT, M->NCellsSize, K), levelView(h_old, M->NCellsSize, K),
                        levelView(h_new, M->NCellsSize, K), levelView(normal_velocity, M->NEdgesSize, K),
                        tracerView(tracers, NT, M->NCellsSize, K), ntracers, dt, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_monoadv_attach_vert_adv(omg_monoadv *a, omg_vertadv *v) {
+   OMG_TRY
+   OMG_ARG(a);
+   a->A->attachVertAdv(v ? v->A.get() : nullptr);
    OMG_CATCH
 }
 static ArrRef monoAdvLookup(const MonotoneAdv &A, const char *Name) {

@@ -18,8 +18,12 @@ struct MonotoneAdvArgs {
    const Real *Tracers        = nullptr;               ///< [tracer][NCellsSize][Pitch]
    Real *ScaleIn = nullptr, *ScaleOut = nullptr;       ///< [tracer][NCellsSize][Pitch]: written by launch 1, read by 2
    Real *Tend = nullptr;                               ///< [tracer][NCellsSize][Pitch], accumulated by launch 2
+   /// the 3-D form (MonotoneAdv::attachVertAdv): all three set, or all three null for the horizontal form
+   const Real *VerticalTransport = nullptr;                   ///< [NCellsSize][Pitch]
+   const I4 *MinLayerCell = nullptr, *MaxLayerCell = nullptr; ///< [cell]
 };
 /// the two launches of MonotoneAdv::addTracerTend: the scale factors of every cell, then the limited flux divergence
+/// (with VerticalTransport set, of the horizontal and the vertical fluxes)
 void launchMonotoneAdv(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S);
 
 } // namespace OMEGA

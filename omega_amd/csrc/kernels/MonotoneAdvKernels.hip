@@ -23,6 +23,25 @@
 // gathers of three tracers in flight per slot are worth more than the fourth wave that blocks of 2 keep (the transport
 // body, with fewer gathers per tracer, settled on 2).  6 tracers are two blocks of 3; 4 + 2 is no better than 2 + 2 + 2.
 // A remainder of 2 or 1 tracers takes a pass of that size.
+//
+// The 3-D form (Vert = true: MonotoneAdv::attachVertAdv) is a compile-time variant of the two bodies; the Vert = false
+// instantiations are the ones above, register for register.  After the slots of a block each tracer adds the two
+// interfaces of the thread's levels: the level above the first and below the last own level come as single values from
+// the cell's own rows (lines the wavefront holds in L1: no new gather, no lane exchange, so nothing changes where an
+// interface crosses a lane pair, a line or a level chunk of gridDim.y), and in the two-level lane type the interface
+// between the two own levels is evaluated once, from registers alone (it is the top interface of the second level and
+// the bottom interface of the first).  Both layers of an interface evaluate it from the same operands, so they agree on
+// every bit.  The tracers of a block go one after the other behind a scheduling barrier: interleaved, the twelve
+// divisions of a block's scale factors take the dv2 form of launch 1 to 198 VGPRs (2 waves); with the barrier and a
+// 3-wave budget it needs 166 and no scratch, and the one-level form of launch 2 keeps its fourth wave (154 -> 118).
+// Blocks stay at 3 (VGPRs / waves per SIMD of the dv2 and the one-level instantiation, scratch 0 in each):
+//                    block 3, Vert = true
+//   MonoScaleBody   166 / 3, 118 / 4
+//   MonoFluxBody    160 / 3, 118 / 4
+// At QU30 size with 6 tracers the 3-D call takes 8.67 ms where the 2-D one takes 6.27 (launch 1 +0.6 ms, launch 2
+// +1.7 ms; profiles/r20_monotone_adv3d_diag_qu30.json).  Tried and not kept, DESIGN.md section 4.11: the neighbouring
+// levels from the neighbouring lanes instead of loads (no gain: the loads are not what costs), VerticalTransport asked
+// for above the slot loop (slower), launch 2 without the barrier in the dv2 form (slower).
 #include "KernelCommon.h"
 #include "MonotoneAdvKernels.h"
 
@@ -69,6 +88,7 @@ struct MonoLds {
    int *Edge, *Nbr, *N;
 };
 struct MonoTables {
+   using Lds = MonoLds;
    MeshView M;
    template <class Cv> __host__ __device__ MonoLds layout(Cv &C, int Tile) const {
       const int ME = M.MaxEdges;
@@ -96,6 +116,98 @@ struct MonoTables {
    }
 };
 
+/// The 3-D form (MonotoneAdv::attachVertAdv) adds the cell's layer range to the tables and VerticalTransport to the rows.
+struct MonoLdsV : MonoLds {
+   int *KMin, *KMax;
+};
+struct MonoTablesV : MonoTables {
+   using Lds = MonoLdsV;
+   int KLog; ///< NVertLayers (launchTile sets it): no interface at or below it carries flux
+   const Real *Wt;
+   const I4 *KMinCell, *KMaxCell;
+   template <class Cv> __host__ __device__ MonoLdsV layout(Cv &C, int Tile) const {
+      MonoLdsV L;
+      static_cast<MonoLds &>(L) = MonoTables::layout(C, Tile);
+      L.KMin                    = C.template take<int>(Tile);
+      L.KMax                    = C.template take<int>(Tile);
+      return L;
+   }
+   __device__ void stage(const MonoLdsV &L, int First, int Cnt, int Tid, int NThr) const {
+      MonoTables::stage(L, First, Cnt, Tid, NThr);
+      for (int I = Tid; I < Cnt; I += NThr) {
+         L.KMin[I] = KMinCell[First + I];
+         L.KMax[I] = KMaxCell[First + I];
+      }
+   }
+};
+template <bool Vert> using MonoTablesOf = std::conditional_t<Vert, MonoTablesV, MonoTables>;
+
+// The vertical part of a thread: its own levels are in registers; of the level above its first and the one below its
+// last it loads single values from the cell's own rows (lines this wavefront has just fetched).  Interface K is the top
+// of layer K and carries flux for KMin < K <= KMax; where it does not, the level across it is not read (the index is
+// clamped to the thread's own level) and every value of the interface is selected to 0.0.
+template <class T> struct VertSpan {
+   static constexpr int W = VecW<T>::W;
+   bool Top[W], Bot[W]; ///< the top / bottom interface of each own level carries flux
+   int KUp, KDn;        ///< the level above the first own level, below the last; the own level where there is none
+   __device__ __forceinline__ VertSpan(int Kv, int KMin, int KMax, int KLog) {
+#pragma unroll
+      for (int I = 0; I < W; ++I) {
+         const int Lev = Kv * W + I;
+         Top[I]        = KMin < Lev && Lev <= KMax && Lev > 0 && Lev < KLog; // (the last two: whatever the range says)
+         Bot[I]        = KMin <= Lev && Lev < KMax && Lev + 1 < KLog;
+      }
+      KUp = Top[0] ? Kv * W - 1 : Kv * W;
+      KDn = Bot[W - 1] ? Kv * W + W : Kv * W + W - 1;
+   }
+};
+__device__ __forceinline__ double ld1(const double *P, int Row, int K, int Lev) { return P[(size_t)Row * K + Lev]; }
+/// the values one level above / below each own level
+__device__ __forceinline__ double above(double, double Up) { return Up; }
+__device__ __forceinline__ dv2 above(dv2 Own, double Up) {
+   dv2 R;
+   R.x = Up;
+   R.y = Own.x;
+   return R;
+}
+__device__ __forceinline__ double below(double, double Dn) { return Dn; }
+__device__ __forceinline__ dv2 below(dv2 Own, double Dn) {
+   dv2 R;
+   R.x = Own.y;
+   R.y = Dn;
+   return R;
+}
+/// the last own level
+__device__ __forceinline__ double last(double Own) { return Own; }
+__device__ __forceinline__ double last(dv2 Own) { return Own.y; }
+/// M ? X : Y per level
+__device__ __forceinline__ double selIn(const bool (&M)[1], double X, double Y) { return M[0] ? X : Y; }
+__device__ __forceinline__ dv2 selIn(const bool (&M)[2], dv2 X, dv2 Y) {
+   dv2 R;
+   R.x = M[0] ? X.x : Y.x;
+   R.y = M[1] ? X.y : Y.y;
+   return R;
+}
+/// VLow = Wv > 0.0 ? Wv*PD : Wv*PU
+__device__ __forceinline__ double lowFluxV(double Wv, double PU, double PD) { return Wv > 0.0 ? Wv * PD : Wv * PU; }
+__device__ __forceinline__ dv2 lowFluxV(dv2 Wv, dv2 PU, dv2 PD) {
+   dv2 R;
+   R.x = lowFluxV(Wv.x, PU.x, PD.x);
+   R.y = lowFluxV(Wv.y, PU.y, PD.y);
+   return R;
+}
+/// VLow and AV of the interface between the layers U (above) and D (below), RU = hU/(hU + hD); 0.0 where In is false
+template <class T, int W>
+__device__ __forceinline__ void vertIface(const bool (&In)[W], const T &Wv, const T &PU, const T &PD, const T &RU, T &VLow,
+                                          T &AV) {
+   const T Z     = splat<T>(0.0);
+   const T VL    = lowFluxV(Wv, PU, PD);
+   const T PhiT  = PU + RU * (PD - PU);
+   const T VHigh = Wv * PhiT;
+   VLow          = selIn(In, VL, Z);
+   AV            = selIn(In, T(VHigh - VL), Z);
+}
+
 /// the mass flux of a slot's edge in edge orientation: Fm = DvEdge*(hE*u)
 template <class T>
 __device__ __forceinline__ T massFlux(Real Dv, bool IsC0, bool Upwind, const T &Hc, const T &Hn, const T &Ue) {
@@ -106,14 +218,17 @@ __device__ __forceinline__ T massFlux(Real Dv, bool IsC0, bool Upwind, const T &
 
 // ---------------------------------------------------------------------------------------
 // Launch 1, one thread per (cell, level chunk): ScaleIn, ScaleOut of the cell for every tracer.
-struct MonoScaleBody : MonoTables {
-   static constexpr int TrBlock = 3;
-   using Lds                    = MonoLds;
+// Vert: the 3-D form, which adds the two interfaces of every level to the sums after the slots.
+template <bool Vert> struct MonoScaleBodyT : MonoTablesOf<Vert> {
+   static constexpr int TrBlock  = 3;
+   static constexpr int MinWaves = Vert ? 3 : 1; // (1 is what a body without the member gets)
+   using Lds                    = typename MonoTablesOf<Vert>::Lds;
    int K, NT, Upwind;
    Real Dt;
    const Real *HOld, *HNew, *U, *Tr;
    Real *SIn, *SOut;
    template <class T, int NB> __device__ __forceinline__ void pass(const Lds &L, int Le, int ICell, int Kv, int Lt0) const {
+      const MeshView &M    = this->M;
       const int ME         = M.MaxEdges;
       const int N          = L.N[Le];
       const Real InvA      = L.InvA[Le];
@@ -150,6 +265,42 @@ struct MonoScaleBody : MonoTables {
          }
       }
       const T Hw = ldk<T>(HNew, ICell, K, Kv);
+      if constexpr (Vert) {
+         const T Z = splat<T>(0.0);
+         const VertSpan<T> Sp(Kv, L.KMin[Le], L.KMax[Le], this->KLog);
+         // the top interfaces of the own levels as T, the bottom interface of the last own level as one value (D); the
+         // bottom interface of the first of two levels is the top interface of the second
+         const bool BotD[1] = {Sp.Bot[VecW<T>::W - 1]};
+         const T WvT     = selIn(Sp.Top, ldk<T>(this->Wt, ICell, K, Kv), Z);
+         const double WvD = selIn(BotD, ld1(this->Wt, ICell, K, Sp.KDn), 0.0);
+         const T HA      = above(Hc, ld1(HOld, ICell, K, Sp.KUp));
+         const T RT      = HA / (HA + Hc); // h[K-1]/(h[K-1] + h[K])
+         const double RD = last(Hc) / (last(Hc) + ld1(HOld, ICell, K, Sp.KDn));
+#pragma unroll
+         for (int B = 0; B < NB; ++B) {
+            const Real *TrL  = Tr + (Lt0 + B) * CStride;
+            const double PDn = ld1(TrL, ICell, K, Sp.KDn);
+            const T PA = above(Pc[B], ld1(TrL, ICell, K, Sp.KUp)), PB = below(Pc[B], PDn);
+            PMax[B] = selIn(Sp.Top, kmax(PMax[B], PA), PMax[B]);
+            PMin[B] = selIn(Sp.Top, kmin(PMin[B], PA), PMin[B]);
+            PMax[B] = selIn(Sp.Bot, kmax(PMax[B], PB), PMax[B]);
+            PMin[B] = selIn(Sp.Bot, kmin(PMin[B], PB), PMin[B]);
+            T VLt, AVt;
+            double VLd, AVd;
+            vertIface(Sp.Top, WvT, PA, Pc[B], RT, VLt, AVt);
+            vertIface(BotD, WvD, last(Pc[B]), PDn, RD, VLd, AVd);
+            const T VLb = below(VLt, VLd), AVb = below(AVt, AVd);
+            const T HTd  = Hc * Pc[B] + Dt * (((DivLow[B] * InvA) - VLt) + VLb);
+            const T PIn  = Dt * (((In[B] * InvA) + kmax(T(-AVt), Z)) + kmax(AVb, Z));
+            const T POut = Dt * (((Out[B] * InvA) + kmax(AVt, Z)) + kmax(T(-AVb), Z));
+            const T QIn  = kmax(Z, T(PMax[B] * Hw - HTd));
+            const T QOut = kmax(Z, T(HTd - PMin[B] * Hw));
+            stk<T>(SIn + (Lt0 + B) * CStride, ICell, K, Kv, scaleOf(PIn, QIn));
+            stk<T>(SOut + (Lt0 + B) * CStride, ICell, K, Kv, scaleOf(POut, QOut));
+            __builtin_amdgcn_sched_barrier(0);
+         }
+         return;
+      }
 #pragma unroll
       for (int B = 0; B < NB; ++B) {
          const T HTd  = Hc * Pc[B] + Dt * (DivLow[B] * InvA);
@@ -179,13 +330,16 @@ struct MonoScaleBody : MonoTables {
 // ---------------------------------------------------------------------------------------
 // Launch 2, one thread per (cell, level chunk): Tend += (sum over the slots of s*(FLow + Sc*A))/AreaCell, with the scale
 // factors launch 1 stored at the cell and at the cells across.
-struct MonoFluxBody : MonoTables {
+// Vert: the 3-D form, which adds the limited fluxes of the two interfaces of every level after the slots; an interface's
+// scale factors are the cell's own, launch 1's of the levels on its two sides.
+template <bool Vert> struct MonoFluxBodyT : MonoTablesOf<Vert> {
    static constexpr int TrBlock = 3;
-   using Lds                    = MonoLds;
+   using Lds                    = typename MonoTablesOf<Vert>::Lds;
    int K, NT, Upwind;
    const Real *HOld, *U, *Tr, *SIn, *SOut;
    Real *Tend;
    template <class T, int NB> __device__ __forceinline__ void pass(const Lds &L, int Le, int ICell, int Kv, int Lt0) const {
+      const MeshView &M    = this->M;
       const int ME         = M.MaxEdges;
       const int N          = L.N[Le];
       const Real InvA      = L.InvA[Le];
@@ -224,6 +378,36 @@ struct MonoFluxBody : MonoTables {
             Sum[B]        = Sum[B] + (IsC0 ? T(-F) : F); // s*F
          }
       }
+      if constexpr (Vert) {
+         const T Z = splat<T>(0.0);
+         const VertSpan<T> Sp(Kv, L.KMin[Le], L.KMax[Le], this->KLog);
+         const bool BotD[1] = {Sp.Bot[VecW<T>::W - 1]}; // (as in launch 1)
+         const T WvT     = selIn(Sp.Top, ldk<T>(this->Wt, ICell, K, Kv), Z);
+         const double WvD = selIn(BotD, ld1(this->Wt, ICell, K, Sp.KDn), 0.0);
+         const T HA      = above(Hc, ld1(HOld, ICell, K, Sp.KUp));
+         const T RT      = HA / (HA + Hc);
+         const double RD = last(Hc) / (last(Hc) + ld1(HOld, ICell, K, Sp.KDn));
+#pragma unroll
+         for (int B = 0; B < NB; ++B) {
+            const size_t Off = (Lt0 + B) * CStride;
+            const T PA  = above(Pc[B], ld1(Tr + Off, ICell, K, Sp.KUp));
+            const T SIA = above(SIc[B], ld1(SIn + Off, ICell, K, Sp.KUp)), SOA = above(SOc[B], ld1(SOut + Off, ICell, K, Sp.KUp));
+            const double PDn = ld1(Tr + Off, ICell, K, Sp.KDn);
+            const double SIDn = ld1(SIn + Off, ICell, K, Sp.KDn), SODn = ld1(SOut + Off, ICell, K, Sp.KDn);
+            T VLt, AVt;
+            double VLd, AVd;
+            vertIface(Sp.Top, WvT, PA, Pc[B], RT, VLt, AVt);
+            vertIface(BotD, WvD, last(Pc[B]), PDn, RD, VLd, AVd);
+            // interface K: out of layer K into K-1 where AV >= 0
+            const T ScT      = selGe0(AVt, kmin(SOc[B], SIA), kmin(SIc[B], SOA));
+            const double ScD = selGe0(AVd, kmin(SODn, last(SIc[B])), kmin(SIDn, last(SOc[B])));
+            const T FVt      = selIn(Sp.Top, T(VLt + ScT * AVt), Z);
+            const T FVb      = below(FVt, selIn(BotD, VLd + ScD * AVd, 0.0));
+            stk<T>(Tend + Off, ICell, K, Kv, ldk<T>(Tend + Off, ICell, K, Kv) + (((Sum[B] * InvA) - FVt) + FVb));
+            __builtin_amdgcn_sched_barrier(0);
+         }
+         return;
+      }
 #pragma unroll
       for (int B = 0; B < NB; ++B) {
          Real *TendL = Tend + (Lt0 + B) * CStride;
@@ -245,15 +429,29 @@ struct MonoFluxBody : MonoTables {
    }
 };
 
+template <bool Vert> static void launchMonotoneAdvT(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S) {
+   MonoScaleBodyT<Vert> B1{};
+   MonoFluxBodyT<Vert> B2{};
+   B1.M = B2.M = M;
+   B1.K = B2.K = A.K, B1.NT = B2.NT = A.NTracers, B1.Upwind = B2.Upwind = A.FluxThicknessUpwind;
+   B1.HOld = B2.HOld = A.HOld, B1.U = B2.U = A.NormalVelocity, B1.Tr = B2.Tr = A.Tracers;
+   B1.SIn = A.ScaleIn, B1.SOut = A.ScaleOut, B2.SIn = A.ScaleIn, B2.SOut = A.ScaleOut;
+   B1.Dt = A.Dt, B1.HNew = A.HNew, B2.Tend = A.Tend;
+   if constexpr (Vert) {
+      B1.Wt = B2.Wt = A.VerticalTransport;
+      B1.KMinCell = B2.KMinCell = A.MinLayerCell, B1.KMaxCell = B2.KMaxCell = A.MaxLayerCell;
+   }
+   launchTile(B1, M.NCellsAll, A.K, S);
+   launchTile(B2, M.NCellsAll, A.K, S);
+}
+
 void launchMonotoneAdv(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S) {
    if (A.NTracers <= 0)
       return;
-   MonoScaleBody B1{{M}, A.K, A.NTracers, A.FluxThicknessUpwind, A.Dt, A.HOld, A.HNew, A.NormalVelocity, A.Tracers,
-                    A.ScaleIn, A.ScaleOut};
-   launchTile(B1, M.NCellsAll, A.K, S);
-   MonoFluxBody B2{{M}, A.K, A.NTracers, A.FluxThicknessUpwind, A.HOld, A.NormalVelocity, A.Tracers, A.ScaleIn, A.ScaleOut,
-                   A.Tend};
-   launchTile(B2, M.NCellsAll, A.K, S);
+   if (A.VerticalTransport != nullptr)
+      launchMonotoneAdvT<true>(M, A, S);
+   else
+      launchMonotoneAdvT<false>(M, A, S);
 }
 
 } // namespace OMEGA
