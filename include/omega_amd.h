@@ -766,7 +766,7 @@ int omg_monoadv_destroy(omg_monoadv *a);
 /* tracer_tend_dev [ntracers][NCellsSize][pitch] += the limited flux divergence of tracers_dev (same shape) over the step
  * h_old_dev -> h_new_dev ([NCellsSize][pitch]) of length dt by normal_velocity_dev ([NEdgesSize][pitch]); "ScaleIn" and
  * "ScaleOut" are overwritten.  Fails for ntracers outside 1 .. max_tracers and a dt that is not finite and positive.
- * Two launches */
+ * Two launches; three after omg_monoadv_set_horz_order(a, 3 or 4, ...), which also overwrites "Hess" */
 int omg_monoadv_add_tracers(omg_monoadv *a, double *tracer_tend_dev, const double *h_old_dev, const double *h_new_dev,
                             const double *normal_velocity_dev, const double *tracers_dev, int ntracers, double dt,
                             void *stream);
@@ -775,7 +775,29 @@ int omg_monoadv_add_tracers(omg_monoadv *a, double *tracer_tend_dev, const doubl
  * of v's VertCoord: the same arguments, two launches.  Fails for a v of another mesh or layer count.  a keeps a pointer
  * to v: detach before destroying it. */
 int omg_monoadv_attach_vert_adv(omg_monoadv *a, omg_vertadv *v);
-/* "ScaleIn", "ScaleOut" ([max_tracers][NCellsSize][NVertLayers], zero at creation) */
+/* MonotoneAdv::setHorzOrder: the order of the horizontal flux under the limiter.  2 (the state at creation): the centred
+ * flux, two launches.  4 and 3: the centred edge value corrected by the second derivative of the tracer along the line
+ * between the two cells, from a least-squares quadratic at each cell (Skamarock and Gassmann 2011); order 3 adds the
+ * upwind-biased term times coef3rd (in (0, 1]; MPAS's default 0.25; unused at the other orders).  The first such call
+ * allocates "Hess" and the tables; it builds the tables on the host from the mesh's cell positions with sphere_radius
+ * (0: a planar mesh) and the periods of a planar mesh (0: not periodic) and uploads them.  omg_monoadv_add_tracers then
+ * makes three launches and still allocates nothing; order 2 frees nothing and gives the bits of an object never
+ * configured.  Fails for an order outside {2, 3, 4}, coef3rd outside (0, 1] at order 3 and a negative or non-finite
+ * radius or period.  A halo of at least 3 cell layers gives the global mesh's result on owned cells */
+int omg_monoadv_set_horz_order(omg_monoadv *a, int order, double coef3rd, double sphere_radius, double x_period,
+                               double y_period);
+/* The tables omg_monoadv_set_horz_order(a, 3 or 4, ...) builds for an object on m, on the host alone (m may be
+ * host-only): fit_cell [NCellsSize], the other three [NCellsSize][MaxEdges][3].  Order 2 writes nothing.  Fails as
+ * omg_monoadv_set_horz_order does */
+int omg_monoadv_high_order_tables(const omg_mesh *m, int order, double coef3rd, double sphere_radius, double x_period,
+                                  double y_period, double *fit_cell, double *hess_weight, double *edge_dir_own,
+                                  double *edge_dir_across);
+/* kernel launches omg_monoadv_add_tracers has issued on a so far (two per call, three at order 3 or 4) */
+int omg_monoadv_launch_count(const omg_monoadv *a, int64_t *n);
+/* "ScaleIn", "ScaleOut" ([max_tracers][NCellsSize][NVertLayers], zero at creation); after
+ * omg_monoadv_set_horz_order(3 or 4) also "Hess" ([max_tracers][3: xx, xy, yy][NCellsSize][NVertLayers]), "HessWeight",
+ * "EdgeDirOwn", "EdgeDirAcross" ([NCellsSize][MaxEdges][3]) and "FitCell" ([NCellsSize], 1.0 or 0.0); before it these
+ * five names fail */
 int omg_monoadv_device_ptr(const omg_monoadv *a, const char *name, double **dev, size_t *n);
 int omg_monoadv_copy_to_device(omg_monoadv *a, const char *name, const double *host, size_t n);
 int omg_monoadv_copy_to_host(const omg_monoadv *a, const char *name, double *host, size_t n);

@@ -1311,12 +1311,24 @@ class VertAdv(_Handle, _NamedArrays):
         return (self.mesh.NCellsSize, self.K)
 
 
+def monotone_adv_high_order_tables(mesh: "HorzMesh", order: int, coef_3rd_order: float = 0.25, sphere_radius: float = 0.0,
+                                   x_period: float = 0.0, y_period: float = 0.0) -> dict:
+    """omg_monoadv_high_order_tables: the tables MonotoneAdv.set_horz_order builds on `mesh` (host-only will do), as
+    {"FitCell" [NCellsSize], "HessWeight", "EdgeDirOwn", "EdgeDirAcross" [NCellsSize][MaxEdges][3]}"""
+    n, me = mesh.NCellsSize, mesh.MaxEdges
+    out = {"FitCell": np.zeros(n), "HessWeight": np.zeros((n, me, 3)), "EdgeDirOwn": np.zeros((n, me, 3)),
+           "EdgeDirAcross": np.zeros((n, me, 3))}
+    _chk(lib().omg_monoadv_high_order_tables(mesh.h, int(order), C.c_double(coef_3rd_order), C.c_double(sphere_radius),
+                                             C.c_double(x_period), C.c_double(y_period), *(_pd(a) for a in out.values())))
+    return out
+
+
 class MonotoneAdv(_Handle, _NamedArrays):
     """MonotoneAdv (omega_amd/csrc/MonotoneAdv.h): flux-corrected horizontal tracer advection -- the centred edge flux
     limited against the upwind one, so that a forward update over `dt` creates no new extremum.  Level-indexed inputs
     are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles; the tendency is accumulated in
     place: a device address (asynchronous on `stream`) or a numpy array (staged, computed, returned).  The named arrays
-    are "ScaleIn" and "ScaleOut", [max_tracers][NCellsSize][K]."""
+    are "ScaleIn" and "ScaleOut", [max_tracers][NCellsSize][K], and after set_horz_order(3 or 4) those it names."""
     _destroy, _arrays = "omg_monoadv_destroy", "omg_monoadv"
 
     def __init__(self, mesh: HorzMesh, nvertlayers: int, max_tracers: int, flux_thickness_upwind: bool = False):
@@ -1343,7 +1355,30 @@ class MonotoneAdv(_Handle, _NamedArrays):
             device_synchronize()
         return _read_back(buf, self.K, stream)
 
+    def set_horz_order(self, order: int, coef_3rd_order: float = 0.25, sphere_radius: float = 0.0,
+                       x_period: float = 0.0, y_period: float = 0.0):
+        """MonotoneAdv::setHorzOrder: 2 the centred flux (the state at creation), 4 the fourth-order flux, 3 the
+        third-order one with the upwind-biased term times `coef_3rd_order` (in (0, 1]).  Orders 3 and 4 build the
+        tables from the mesh's cell positions -- on a sphere of `sphere_radius` (0: planar, with the periods of a
+        periodic mesh) -- and add the named arrays "Hess" [max_tracers][3][NCellsSize][K], "HessWeight", "EdgeDirOwn",
+        "EdgeDirAcross" [NCellsSize][MaxEdges][3] and "FitCell" [NCellsSize]; add_tracers then makes three launches."""
+        _chk(lib().omg_monoadv_set_horz_order(self.h, int(order), C.c_double(coef_3rd_order), C.c_double(sphere_radius),
+                                              C.c_double(x_period), C.c_double(y_period)))
+        self.horz_order = int(order)
+
+    def launch_count(self) -> int:
+        """kernel launches add_tracers has issued on this object so far"""
+        n = C.c_int64(0)
+        _chk(lib().omg_monoadv_launch_count(self.h, C.byref(n)))
+        return n.value
+
     def _shape(self, name):
+        if name == "Hess":
+            return (self.max_tracers, 3, self.mesh.NCellsSize, self.K)
+        if name in ("HessWeight", "EdgeDirOwn", "EdgeDirAcross"):
+            return (self.mesh.NCellsSize, self.mesh.MaxEdges, 3)
+        if name == "FitCell":
+            return (self.mesh.NCellsSize,)
         return (self.max_tracers, self.mesh.NCellsSize, self.K)
 
 

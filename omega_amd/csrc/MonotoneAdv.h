@@ -107,6 +107,58 @@
 //  pass 1 adds VerticalTransport, 48 B + 24 B per tracer; pass 2 likewise, 40 B + 40 B per tracer; and 8 B per cell and
 //  launch for the range.  DESIGN.md section 4.11.
 //
+// The high-order horizontal flux (setHorzOrder(3 or 4); same rules: FP64, -ffp-contract=off, every chain in the order
+// written, the same max and min; a NumPy restatement in the same order that reads the tables from the object is
+// bit-identical, tests/monotone_adv_ho_reference.py).  OmegaV0ShallowWater.md section 3.5.1 describes MPAS-Ocean's
+// transport as "fourth order under normal conditions, and reduces to third order to preserve monotonicity"
+// (Skamarock and Gassmann 2011): the centred edge value is corrected by the second derivative of phi along the line
+// between the two cells, taken from a least-squares quadratic at each of them.  Zalesak's argument holds for any FHigh,
+// so Fm, FLow, A = FHigh - FLow, both passes, the vertical form and the masking are exactly as written above.
+//
+//  Tables, built once on the host by setHorzOrder (checked to a tolerance: a least-squares solve is not restated bit
+//  for bit):
+//    A cell c < NCellsAll is a fit cell (FitCell[c] = 1.0, else 0.0) when NEdgesOnCell[c] >= 5, every slot
+//    j < NEdgesOnCell[c] names a local edge (e < NEdgesAll) with EdgeMask != 0 and a local cell across it
+//    (n < NCellsAll), and the fit matrix below has full column rank (Householder QR: the smallest |R(k,k)| is above
+//    1e-8 times the largest).  A coast cell and a cell of the outermost halo layer are never fit cells.
+//    d_j: the offset from c to the cell across slot j.  Planar: X_n - X_c, the minimum image over a non-zero period.
+//    Sphere: azimuthal equidistant -- the direction of the tangential part of X_n - X_c at c, the length
+//    R*acos(r_c.r_n), evaluated as R*atan2(|r_c x r_n|, r_c.r_n): acos loses half the digits at these angles.
+//    (e1, e2): an orthonormal frame of the tangent plane at c; the results do not depend on it beyond rounding, and the
+//    library takes x, y on a plane and e1 = a x r_c/|a x r_c|, e2 = r_c x e1 on a sphere, a the z axis, or the x axis
+//    where |r_c.z| >= 0.9.  (x_j, y_j): the components of d_j/L, L the mean |d_j|.  With P+ the pseudo-inverse of the
+//    n x 5 matrix of rows (x, y, x^2, x*y, y^2) -- the least-squares quadratic through the centre value --
+//      HessWeight[c][j] = (2*P+[2][j], P+[3][j], 2*P+[4][j])/L^2     (phi_xx, phi_xy, phi_yy per unit phi[n_j] - phi[c])
+//    and zeros for a cell that is not a fit cell.  An edge is high when it is masked in and both its cells are fit
+//    cells.  For slot j of c with edge e, (cs, sn) the unit direction of d_j in c's frame:
+//      EdgeDirOwn[c][j]    = (DcEdge[e]^2/12)*(cs^2, 2*cs*sn, sn^2)
+//      EdgeDirAcross[c][j] = a copy of EdgeDirOwn[n][j'], j' the slot of e in n (the same bits)
+//    both 0.0 on a slot whose edge is not high.  EdgeDirOwn[c][j][0] and [2] are not both zero on a high edge, which is
+//    how the kernels tell one.
+//
+//  Pass 0, cells c < NCellsAll, all levels, per tracer L and t in {xx, xy, yy}:
+//      Hess[L][t][c] = the sum, started at 0.0, of HessWeight[c][j][t]*(phi[n_j] - phi[c]) over the slots in slot order
+//    a cell that is not a fit cell stores 0.0 and reads no neighbour.
+//
+//  The edge, as evaluated by both its cells in passes 1 and 2, in the edge's orientation (Q0: the direction
+//  coefficients on c0's side -- EdgeDirOwn of c0's slot, which is EdgeDirAcross of c1's):
+//      D0    = (Q0[0]*Hxx[c0] + Q0[1]*Hxy[c0]) + Q0[2]*Hyy[c0]
+//      D1    = (Q1[0]*Hxx[c1] + Q1[1]*Hxy[c1]) + Q1[2]*Hyy[c1]
+//      S = D0 + D1;   T = D0 - D1;   B = Beta*T
+//      Corr  = high edge ? S + (Fm >= 0.0 ? B : -B) : 0.0        (a select: nothing of Hess enters on another edge)
+//      FHigh = Fm*(0.5*(phi[c0] + phi[c1]) - Corr)
+//    Beta = 0.0 at order 4 and Coef3rdOrder at order 3 (MPAS's default 0.25; 1: the upwind-biased third order).  A
+//    constant tracer has Hess == 0.0 exactly, so Corr = 0.0 and A = 0.0 bit for bit as before.
+//
+//  Only Hess[L < NTracers][t][c < NCellsAll][K < NVertLayers] is written besides the entries named above.  Hess of a
+//  cell needs its neighbours, the scale factors need Hess of the cell and of the cells across, and the fluxes need the
+//  scale factors of the cells across: the result on owned cells is that of the global mesh for a halo of at least 3
+//  cell layers, the reference's default (Decomp.md gives higher-order tracer advection as one reason for it).
+//
+//  Three launches; traffic per cell-level of a hexagon mesh: pass 0 reads phi and writes three rows per tracer (32 B);
+//  pass 1 adds the three Hess rows (40 B + 48 B per tracer), pass 2 likewise (32 B + 64 B per tracer): 72 B + 144 B per
+//  tracer.  DESIGN.md section 4.12.
+//
 // Two launches per call, both tile sweeps over the cells (kernels/MonotoneAdvKernels.hip); no atomics and no
 // edge-located array.  Algorithmic traffic per cell-level of a hexagon mesh (3 edge rows per cell), every row counted
 // once per launch: pass 1 reads hOld, hNew and 3 u (40 B) and per tracer reads phi and writes the two scale factors
@@ -125,6 +177,22 @@ struct MonotoneAdvConfig {
    bool FluxThicknessUpwind = false; ///< must match the AuxiliaryState's FluxThickEdgeChoice (Upwind: true)
 };
 
+/// The high-order horizontal flux of MonotoneAdv::setHorzOrder
+struct MonoHighOrderConfig {
+   int HorzOrder     = 2;    ///< 2: the centred flux; 4: Beta = 0.0; 3: Beta = Coef3rdOrder
+   Real Coef3rdOrder = 0.25; ///< in (0, 1]; MPAS's default
+   Real SphereRadius = 0.0;  ///< 0: planar
+   Real XPeriod = 0.0, YPeriod = 0.0; ///< 0: not periodic
+};
+
+/// The tables of the high-order flux as setHorzOrder builds them, on the host alone (a host-only mesh will do): FitCell
+/// [NCellsSize], HessWeight, EdgeDirOwn, EdgeDirAcross [NCellsSize][MaxEdges][3].  build refuses what setHorzOrder
+/// refuses; at order 2 it builds nothing.
+struct MonoHighOrderTables {
+   HostArrayReal Fit, Weight, Own, Acr;
+   void build(const HorzMesh &M, const MonoHighOrderConfig &C);
+};
+
 class MonotoneAdv : public Registry<MonotoneAdv> {
  public:
    /// Refuses (OmegaError) a null or host-only mesh, NVertLayers < 1 and MaxTracers < 1.  Everything is allocated here;
@@ -139,7 +207,7 @@ class MonotoneAdv : public Registry<MonotoneAdv> {
 
    /// Tend += the limited flux divergence of Tracers[0 .. NTracers) over the step hOld -> hNew of length Dt by the
    /// velocity u.  Refuses NTracers outside 1 .. MaxTracers, a Dt that is not finite and positive, and arrays of another
-   /// shape.  Two launches.
+   /// shape.  Two launches; three at order 3 or 4 (setHorzOrder).
    void addTracerTend(const Array3DReal &Tend, const Array2DReal &hOld, const Array2DReal &hNew, const Array2DReal &u,
                       const Array3DReal &Tracers, int NTracers, Real Dt, hipStream_t S) const;
 
@@ -155,6 +223,18 @@ class MonotoneAdv : public Registry<MonotoneAdv> {
    /// a VertAdv of another mesh or layer count.
    void attachVertAdv(const VertAdv *V);
    const VertAdv *vertAdv() const { return VAdv; }
+
+   /// Orders 3 and 4: builds the tables of the high-order flux on the host from the mesh's host arrays, uploads them and
+   /// allocates Hess (the only allocation; addTracerTend still allocates nothing), and addTracerTend runs three launches.
+   /// Order 2 frees nothing and switches the form off: two launches and the bits of an object never configured.
+   /// Refuses (OmegaError) an order outside {2, 3, 4}, Coef3rdOrder outside (0, 1] at order 3 and a negative or
+   /// non-finite radius or period.
+   void setHorzOrder(const MonoHighOrderConfig &C);
+   MonoHighOrderConfig HighOrder; ///< as last set
+   Array3DReal Hess;              ///< [MaxTracers*3][NCellsSize][levelPitch(K)]: plane 3*L + t, t = xx, xy, yy
+   Array3DReal HessWeight, EdgeDirOwn, EdgeDirAcross; ///< [NCellsSize][MaxEdges][3]
+   Array1DReal FitCell;                               ///< [NCellsSize] 1.0 / 0.0
+   mutable I8 LaunchCount = 0; ///< kernel launches issued by addTracerTend so far
 
    void copyToHost(); ///< ScaleIn, ScaleOut -> their host mirrors (synchronises the device)
 

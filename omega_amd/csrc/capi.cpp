@@ -28,6 +28,7 @@
 #include "BarotropicMode.h"
 #include "SplitExplicitStepper.h"
 
+#include <algorithm>
 #include <cstring>
 #include <initializer_list>
 #include <map>
@@ -2052,9 +2053,49 @@ int omg_monoadv_attach_vert_adv(omg_monoadv *a, omg_vertadv *v) {
    a->A->attachVertAdv(v ? v->A.get() : nullptr);
    OMG_CATCH
 }
+static MonoHighOrderConfig monoHighCfg(int Order, double Coef3rd, double Radius, double XPeriod, double YPeriod) {
+   MonoHighOrderConfig Cfg;
+   Cfg.HorzOrder = Order, Cfg.Coef3rdOrder = Coef3rd, Cfg.SphereRadius = Radius;
+   Cfg.XPeriod = XPeriod, Cfg.YPeriod = YPeriod;
+   return Cfg;
+}
+int omg_monoadv_set_horz_order(omg_monoadv *a, int order, double coef3rd, double sphere_radius, double x_period,
+                               double y_period) {
+   OMG_TRY
+   OMG_ARG(a);
+   a->A->setHorzOrder(monoHighCfg(order, coef3rd, sphere_radius, x_period, y_period));
+   OMG_CATCH
+}
+int omg_monoadv_high_order_tables(const omg_mesh *m, int order, double coef3rd, double sphere_radius, double x_period,
+                                  double y_period, double *fit_cell, double *hess_weight, double *edge_dir_own,
+                                  double *edge_dir_across) {
+   OMG_TRY
+   OMG_ARG(m && fit_cell && hess_weight && edge_dir_own && edge_dir_across);
+   MonoHighOrderTables T;
+   T.build(*m->M, monoHighCfg(order, coef3rd, sphere_radius, x_period, y_period));
+   std::copy(T.Fit.V.begin(), T.Fit.V.end(), fit_cell);
+   std::copy(T.Weight.V.begin(), T.Weight.V.end(), hess_weight);
+   std::copy(T.Own.V.begin(), T.Own.V.end(), edge_dir_own);
+   std::copy(T.Acr.V.begin(), T.Acr.V.end(), edge_dir_across);
+   OMG_CATCH
+}
+int omg_monoadv_launch_count(const omg_monoadv *a, int64_t *n) {
+   OMG_TRY
+   OMG_ARG(a && n);
+   *n = a->A->LaunchCount;
+   OMG_CATCH
+}
 static ArrRef monoAdvLookup(const MonotoneAdv &A, const char *Name) {
-   return findNamed<ArrRef>({{"ScaleIn", arrRef(A.ScaleIn)}, {"ScaleOut", arrRef(A.ScaleOut)}}, Name,
-                            "MonotoneAdv: no array named ");
+   const ArrRef R = findNamed<ArrRef>({{"ScaleIn", arrRef(A.ScaleIn)},
+                                       {"ScaleOut", arrRef(A.ScaleOut)},
+                                       {"Hess", arrRef(A.Hess)},
+                                       {"HessWeight", arrRef(A.HessWeight)},
+                                       {"EdgeDirOwn", arrRef(A.EdgeDirOwn)},
+                                       {"EdgeDirAcross", arrRef(A.EdgeDirAcross)},
+                                       {"FitCell", arrRef(A.FitCell)}},
+                                      Name, "MonotoneAdv: no array named ");
+   OMEGA_REQUIRE(R.Ptr != nullptr, std::string("MonotoneAdv: ") + Name + " exists after setHorzOrder(3 or 4) only");
+   return R;
 }
 OMG_NAMED_ARRAYS(omg_monoadv_copy_to_host, omg_monoadv_copy_to_device, omg_monoadv_device_ptr, omg_monoadv, a,
                  monoAdvLookup(*a->A, name))

@@ -21,10 +21,17 @@ struct MonotoneAdvArgs {
    /// the 3-D form (MonotoneAdv::attachVertAdv): all three set, or all three null for the horizontal form
    const Real *VerticalTransport = nullptr;                   ///< [NCellsSize][Pitch]
    const I4 *MinLayerCell = nullptr, *MaxLayerCell = nullptr; ///< [cell]
+   /// the high-order horizontal flux (MonotoneAdv::setHorzOrder(3 or 4)): all five set, or all five null
+   Real *Hess = nullptr;                                      ///< [tracer*3 + t][NCellsSize][Pitch], written by pass 0
+   const Real *HessWeight = nullptr;                          ///< [cell][MaxEdges][3]
+   const Real *EdgeDirOwn = nullptr, *EdgeDirAcross = nullptr; ///< [cell][MaxEdges][3]
+   const Real *FitCell = nullptr;                             ///< [cell] 1.0 / 0.0
+   Real Beta           = 0.0;
 };
-/// the two launches of MonotoneAdv::addTracerTend: the scale factors of every cell, then the limited flux divergence
-/// (with VerticalTransport set, of the horizontal and the vertical fluxes)
-void launchMonotoneAdv(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S);
+/// the launches of MonotoneAdv::addTracerTend: with Hess set the Hessians of every cell first; the scale factors of every
+/// cell, then the limited flux divergence (with VerticalTransport set, of the horizontal and the vertical fluxes).
+/// Returns the number of launches issued.
+int launchMonotoneAdv(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S);
 
 } // namespace OMEGA
 #endif

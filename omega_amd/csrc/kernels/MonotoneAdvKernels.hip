@@ -42,6 +42,22 @@
 // +1.7 ms; profiles/r20_monotone_adv3d_diag_qu30.json).  Tried and not kept, DESIGN.md section 4.11: the neighbouring
 // levels from the neighbouring lanes instead of loads (no gain: the loads are not what costs), VerticalTransport asked
 // for above the slot loop (slower), launch 2 without the barrier in the dv2 form (slower).
+//
+// The high-order horizontal flux (High = true: MonotoneAdv::setHorzOrder(3 or 4)) is a second compile-time variant of the
+// two bodies behind a launch of its own, MonoHessBody, which stores the three Hess rows of every cell and tracer; the
+// High = false instantiations are the ones above, register for register.  The direction coefficients of a slot, on the
+// cell's side and on the side of the cell across, are staged in the LDS tile (48 B per slot); the cell's own Hess rows
+// are loaded once per tracer, those of the cell across per slot and tracer, under a branch on the slot's high flag, so
+// that nothing of Hess enters on an edge that is not high.  Both cells of an edge put D of the two sides into the edge's
+// order by selects, as they do with phi.  Blocks of 2 tracers (VGPRs / waves per SIMD of the dv2 and the one-level
+// instantiation, scratch 0 in each; the 3-D scale body takes a 2-wave budget here: at 3 waves it spills 48 B):
+//                    Vert = false         Vert = true          with blocks of 3
+//   MonoScaleBody   182 / 2, 126 / 4     188 / 2, 136 / 3     224 / 2, 146 / 3;  168 / 3 + 236 B scratch, 158 / 3
+//   MonoFluxBody    182 / 2, 122 / 4     188 / 2, 148 / 3     226 / 2, 148 / 3;  232 / 2, 174 / 2
+//   MonoHessBody    110 / 4,  68 / 7     (blocks of 3)
+// At QU30 size with 6 tracers the order-4 call takes 16.36 ms where the centred one takes 6.13 (pass 0 2.06 ms, pass 1
+// 6.37 against 2.59, pass 2 7.99 against 3.56; profiles/r21_monotone_adv_ho_diag_qu30.json); blocks of 3 give 16.02 ms
+// and cost the one-level forms a wave and the 3-D forms their registers.  DESIGN.md section 4.12.
 #include "KernelCommon.h"
 #include "MonotoneAdvKernels.h"
 
@@ -140,7 +156,51 @@ struct MonoTablesV : MonoTables {
       }
    }
 };
-template <bool Vert> using MonoTablesOf = std::conditional_t<Vert, MonoTablesV, MonoTables>;
+/// The high-order horizontal flux (MonotoneAdv::setHorzOrder(3 or 4)) adds the direction coefficients of every slot, on
+/// the cell's side and on the side of the cell across, to the tables (48 B per slot) and Hess to the rows.
+template <class Base> struct MonoLdsH : Base::Lds {
+   Real *QOwn, *QAcr;
+};
+template <class Base> struct MonoTablesH : Base {
+   using Lds = MonoLdsH<Base>;
+   const Real *DirOwn, *DirAcr, *Hess;
+   Real Beta;
+   template <class Cv> __host__ __device__ Lds layout(Cv &C, int Tile) const {
+      Lds L;
+      static_cast<typename Base::Lds &>(L) = Base::layout(C, Tile);
+      L.QOwn                               = C.template take<Real>(Tile * this->M.MaxEdges * 3);
+      L.QAcr                               = C.template take<Real>(Tile * this->M.MaxEdges * 3);
+      return L;
+   }
+   __device__ void stage(const Lds &L, int First, int Cnt, int Tid, int NThr) const {
+      Base::stage(L, First, Cnt, Tid, NThr);
+      const int ME3 = this->M.MaxEdges * 3;
+      for (int I = Tid; I < Cnt * ME3; I += NThr) {
+         L.QOwn[I] = DirOwn[(size_t)First * ME3 + I];
+         L.QAcr[I] = DirAcr[(size_t)First * ME3 + I];
+      }
+   }
+};
+template <bool Vert, bool High>
+using MonoTablesOf = std::conditional_t<High, MonoTablesH<std::conditional_t<Vert, MonoTablesV, MonoTables>>,
+                                        std::conditional_t<Vert, MonoTablesV, MonoTables>>;
+
+/// tracers per pass over the slots of the two bodies with the high-order flux
+constexpr int HighTrBlock = 2;
+/// a slot's edge is high: its direction coefficients are set (cs^2 and sn^2 are not both zero)
+__device__ __forceinline__ bool highSlot(const Real *Qo) { return Qo[0] != 0.0 || Qo[2] != 0.0; }
+/// Corr of a high edge in edge orientation: D of this cell (its Hess Hc, its side's coefficients Qo) and of the cell
+/// across (Hn, Qa) put into the order c0, c1; S + (Fm >= 0.0 ? B : -B)
+template <class T>
+__device__ __forceinline__ T highCorr(const Real *Qo, const Real *Qa, bool IsC0, Real Beta, const T &Fm, const T (&Hc)[3],
+                                      const T (&Hn)[3]) {
+   const T Dc = (Qo[0] * Hc[0] + Qo[1] * Hc[1]) + Qo[2] * Hc[2];
+   const T Dn = (Qa[0] * Hn[0] + Qa[1] * Hn[1]) + Qa[2] * Hn[2];
+   const T D0 = IsC0 ? Dc : Dn, D1 = IsC0 ? Dn : Dc;
+   const T S = D0 + D1, Td = D0 - D1;
+   const T B = Beta * Td;
+   return S + selGe0(Fm, B, T(-B));
+}
 
 // The vertical part of a thread: its own levels are in registers; of the level above its first and the one below its
 // last it loads single values from the cell's own rows (lines this wavefront has just fetched).  Interface K is the top
@@ -219,10 +279,12 @@ __device__ __forceinline__ T massFlux(Real Dv, bool IsC0, bool Upwind, const T &
 // ---------------------------------------------------------------------------------------
 // Launch 1, one thread per (cell, level chunk): ScaleIn, ScaleOut of the cell for every tracer.
 // Vert: the 3-D form, which adds the two interfaces of every level to the sums after the slots.
-template <bool Vert> struct MonoScaleBodyT : MonoTablesOf<Vert> {
-   static constexpr int TrBlock  = 3;
-   static constexpr int MinWaves = Vert ? 3 : 1; // (1 is what a body without the member gets)
-   using Lds                    = typename MonoTablesOf<Vert>::Lds;
+// High: the high-order horizontal flux, which takes the cell's own three Hess rows once and gathers those of the cell
+// across per slot and tracer.
+template <bool Vert, bool High> struct MonoScaleBodyT : MonoTablesOf<Vert, High> {
+   static constexpr int TrBlock  = High ? HighTrBlock : 3;
+   static constexpr int MinWaves = Vert ? (High ? 2 : 3) : 1; // (1 is what a body without the member gets)
+   using Lds                    = typename MonoTablesOf<Vert, High>::Lds;
    int K, NT, Upwind;
    Real Dt;
    const Real *HOld, *HNew, *U, *Tr;
@@ -240,6 +302,14 @@ template <bool Vert> struct MonoScaleBodyT : MonoTablesOf<Vert> {
          Pc[B] = PMax[B] = PMin[B] = ldk<T>(Tr + (Lt0 + B) * CStride, ICell, K, Kv);
          DivLow[B] = In[B] = Out[B] = splat<T>(0.0);
       }
+      T Hs[High ? NB : 1][3];
+      if constexpr (High) {
+#pragma unroll
+         for (int B = 0; B < NB; ++B)
+#pragma unroll
+            for (int X = 0; X < 3; ++X)
+               Hs[B][X] = ldk<T>(this->Hess + ((Lt0 + B) * 3 + X) * CStride, ICell, K, Kv);
+      }
       for (int J = 0; J < N; ++J) {
          const Real Md = L.MDvS[Le * ME + J];
          if (Md == 0.0) // EdgeMask 0, or no local edge: Fm = 0.0 exactly, no cell is read
@@ -249,12 +319,30 @@ template <bool Vert> struct MonoScaleBodyT : MonoTablesOf<Vert> {
          const T Hn      = ldk<T>(HOld, Nb, K, Kv);
          const T Ue      = ldk<T>(U, L.Edge[Le * ME + J], K, Kv);
          const T Fm      = massFlux<T>(IsC0 ? -Md : Md, IsC0, Upwind != 0, Hc, Hn, Ue);
+         [[maybe_unused]] const Real *Qo = nullptr;
+         [[maybe_unused]] bool Hi        = false;
+         if constexpr (High) {
+            Qo = L.QOwn + (Le * ME + J) * 3;
+            Hi = highSlot(Qo);
+         }
 #pragma unroll
          for (int B = 0; B < NB; ++B) {
             const T Pn = ldk<T>(Tr + (Lt0 + B) * CStride, Nb, K, Kv);
             const T P0 = IsC0 ? Pc[B] : Pn, P1 = IsC0 ? Pn : Pc[B];
             const T FLow  = lowFlux(Fm, P0, P1);
-            const T FHigh = Fm * (0.5 * (P0 + P1));
+            T FHigh;
+            if constexpr (High) {
+               T Corr = splat<T>(0.0);
+               if (Hi) {
+                  T HnX[3];
+#pragma unroll
+                  for (int X = 0; X < 3; ++X)
+                     HnX[X] = ldk<T>(this->Hess + ((Lt0 + B) * 3 + X) * CStride, Nb, K, Kv);
+                  Corr = highCorr<T>(Qo, L.QAcr + (Le * ME + J) * 3, IsC0, this->Beta, Fm, Hs[B], HnX);
+               }
+               FHigh = Fm * (0.5 * (P0 + P1) - Corr);
+            } else
+               FHigh = Fm * (0.5 * (P0 + P1));
             const T A     = FHigh - FLow;
             PMax[B]       = kmax(PMax[B], Pn);
             PMin[B]       = kmin(PMin[B], Pn);
@@ -332,9 +420,9 @@ template <bool Vert> struct MonoScaleBodyT : MonoTablesOf<Vert> {
 // factors launch 1 stored at the cell and at the cells across.
 // Vert: the 3-D form, which adds the limited fluxes of the two interfaces of every level after the slots; an interface's
 // scale factors are the cell's own, launch 1's of the levels on its two sides.
-template <bool Vert> struct MonoFluxBodyT : MonoTablesOf<Vert> {
-   static constexpr int TrBlock = 3;
-   using Lds                    = typename MonoTablesOf<Vert>::Lds;
+template <bool Vert, bool High> struct MonoFluxBodyT : MonoTablesOf<Vert, High> {
+   static constexpr int TrBlock = High ? HighTrBlock : 3;
+   using Lds                    = typename MonoTablesOf<Vert, High>::Lds;
    int K, NT, Upwind;
    const Real *HOld, *U, *Tr, *SIn, *SOut;
    Real *Tend;
@@ -353,6 +441,14 @@ template <bool Vert> struct MonoFluxBodyT : MonoTablesOf<Vert> {
          SOc[B] = ldk<T>(SOut + (Lt0 + B) * CStride, ICell, K, Kv);
          Sum[B] = splat<T>(0.0);
       }
+      T Hs[High ? NB : 1][3];
+      if constexpr (High) {
+#pragma unroll
+         for (int B = 0; B < NB; ++B)
+#pragma unroll
+            for (int X = 0; X < 3; ++X)
+               Hs[B][X] = ldk<T>(this->Hess + ((Lt0 + B) * 3 + X) * CStride, ICell, K, Kv);
+      }
       for (int J = 0; J < N; ++J) {
          const Real Md = L.MDvS[Le * ME + J];
          if (Md == 0.0)
@@ -362,6 +458,12 @@ template <bool Vert> struct MonoFluxBodyT : MonoTablesOf<Vert> {
          const T Hn      = ldk<T>(HOld, Nb, K, Kv);
          const T Ue      = ldk<T>(U, L.Edge[Le * ME + J], K, Kv);
          const T Fm      = massFlux<T>(IsC0 ? -Md : Md, IsC0, Upwind != 0, Hc, Hn, Ue);
+         [[maybe_unused]] const Real *Qo = nullptr;
+         [[maybe_unused]] bool Hi        = false;
+         if constexpr (High) {
+            Qo = L.QOwn + (Le * ME + J) * 3;
+            Hi = highSlot(Qo);
+         }
 #pragma unroll
          for (int B = 0; B < NB; ++B) {
             const T Pn  = ldk<T>(Tr + (Lt0 + B) * CStride, Nb, K, Kv);
@@ -371,7 +473,19 @@ template <bool Vert> struct MonoFluxBodyT : MonoTablesOf<Vert> {
             const T SI0 = IsC0 ? SIc[B] : SIn_, SI1 = IsC0 ? SIn_ : SIc[B];
             const T SO0 = IsC0 ? SOc[B] : SOn, SO1 = IsC0 ? SOn : SOc[B];
             const T FLow  = lowFlux(Fm, P0, P1);
-            const T FHigh = Fm * (0.5 * (P0 + P1));
+            T FHigh;
+            if constexpr (High) {
+               T Corr = splat<T>(0.0);
+               if (Hi) {
+                  T HnX[3];
+#pragma unroll
+                  for (int X = 0; X < 3; ++X)
+                     HnX[X] = ldk<T>(this->Hess + ((Lt0 + B) * 3 + X) * CStride, Nb, K, Kv);
+                  Corr = highCorr<T>(Qo, L.QAcr + (Le * ME + J) * 3, IsC0, this->Beta, Fm, Hs[B], HnX);
+               }
+               FHigh = Fm * (0.5 * (P0 + P1) - Corr);
+            } else
+               FHigh = Fm * (0.5 * (P0 + P1));
             const T A     = FHigh - FLow;
             const T Sc    = selGe0(A, kmin(SO0, SI1), kmin(SI0, SO1));
             const T F     = FLow + Sc * A;
@@ -429,9 +543,88 @@ template <bool Vert> struct MonoFluxBodyT : MonoTablesOf<Vert> {
    }
 };
 
-template <bool Vert> static void launchMonotoneAdvT(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S) {
-   MonoScaleBodyT<Vert> B1{};
-   MonoFluxBodyT<Vert> B2{};
+// ---------------------------------------------------------------------------------------
+// Pass 0 of the high-order flux, one thread per (cell, level chunk): Hess[L][xx, xy, yy] of the cell for every tracer, the
+// sum over the slots of HessWeight*(phi[n] - phi[c]).  A cell that is not a fit cell stores 0.0 and reads no neighbour.
+struct MonoHessLds {
+   Real *W;
+   int *Nbr, *N, *Fit;
+};
+struct MonoHessBody {
+   static constexpr int TrBlock = 3;
+   using Lds                    = MonoHessLds;
+   MeshView M;
+   int K, NT;
+   const Real *HessWeight, *FitCell, *Tr;
+   Real *Hess;
+   template <class Cv> __host__ __device__ MonoHessLds layout(Cv &C, int Tile) const {
+      MonoHessLds L;
+      L.W   = C.template take<Real>(Tile * M.MaxEdges * 3);
+      L.Nbr = C.template take<int>(Tile * M.MaxEdges);
+      L.N   = C.template take<int>(Tile);
+      L.Fit = C.template take<int>(Tile);
+      return L;
+   }
+   __device__ void stage(const MonoHessLds &L, int First, int Cnt, int Tid, int NThr) const {
+      const int ME = M.MaxEdges;
+      for (int I = Tid; I < Cnt * ME * 3; I += NThr)
+         L.W[I] = HessWeight[(size_t)First * ME * 3 + I];
+      for (int I = Tid; I < Cnt * ME; I += NThr) {
+         const size_t G = (size_t)First * ME + I;
+         L.Nbr[I]       = M.CellsOnEdgeOnCell[2 * G + (M.MaskDvSignOnCell[G] < 0.0 ? 1 : 0)]; // (as MonoTables::stage)
+      }
+      for (int I = Tid; I < Cnt; I += NThr) {
+         L.N[I]   = M.NEdgesOnCell[First + I];
+         L.Fit[I] = FitCell[First + I] != 0.0 ? 1 : 0;
+      }
+   }
+   template <class T, int NB> __device__ __forceinline__ void pass(const Lds &L, int Le, int ICell, int Kv, int Lt0) const {
+      const int ME         = M.MaxEdges;
+      const size_t CStride = (size_t)M.NCellsSize * K;
+      T H[NB][3];
+#pragma unroll
+      for (int B = 0; B < NB; ++B)
+         H[B][0] = H[B][1] = H[B][2] = splat<T>(0.0);
+      if (L.Fit[Le]) { // every slot of a fit cell has a local cell across a masked-in edge
+         const int N = L.N[Le];
+         T Pc[NB];
+#pragma unroll
+         for (int B = 0; B < NB; ++B)
+            Pc[B] = ldk<T>(Tr + (Lt0 + B) * CStride, ICell, K, Kv);
+         for (int J = 0; J < N; ++J) {
+            const int Nb  = L.Nbr[Le * ME + J];
+            const Real *W = L.W + (Le * ME + J) * 3;
+#pragma unroll
+            for (int B = 0; B < NB; ++B) {
+               const T D = ldk<T>(Tr + (Lt0 + B) * CStride, Nb, K, Kv) - Pc[B];
+#pragma unroll
+               for (int X = 0; X < 3; ++X)
+                  H[B][X] = H[B][X] + W[X] * D;
+            }
+         }
+      }
+#pragma unroll
+      for (int B = 0; B < NB; ++B)
+#pragma unroll
+         for (int X = 0; X < 3; ++X)
+            stk<T>(Hess + ((Lt0 + B) * 3 + X) * CStride, ICell, K, Kv, H[B][X]);
+   }
+   template <class T> __device__ void compute(const Lds &L, int Le, int ICell, int Kv) const {
+      int Lt = 0;
+      for (; Lt + TrBlock <= NT; Lt += TrBlock)
+         pass<T, TrBlock>(L, Le, ICell, Kv, Lt);
+      if (NT - Lt >= 2) {
+         pass<T, 2>(L, Le, ICell, Kv, Lt);
+         Lt += 2;
+      }
+      if (Lt < NT) // the odd one
+         pass<T, 1>(L, Le, ICell, Kv, Lt);
+   }
+};
+
+template <bool Vert, bool High> static int launchMonotoneAdvT(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S) {
+   MonoScaleBodyT<Vert, High> B1{};
+   MonoFluxBodyT<Vert, High> B2{};
    B1.M = B2.M = M;
    B1.K = B2.K = A.K, B1.NT = B2.NT = A.NTracers, B1.Upwind = B2.Upwind = A.FluxThicknessUpwind;
    B1.HOld = B2.HOld = A.HOld, B1.U = B2.U = A.NormalVelocity, B1.Tr = B2.Tr = A.Tracers;
@@ -441,17 +634,26 @@ template <bool Vert> static void launchMonotoneAdvT(const MeshView &M, const Mon
       B1.Wt = B2.Wt = A.VerticalTransport;
       B1.KMinCell = B2.KMinCell = A.MinLayerCell, B1.KMaxCell = B2.KMaxCell = A.MaxLayerCell;
    }
+   if constexpr (High) {
+      MonoHessBody B0{};
+      B0.M = M, B0.K = A.K, B0.NT = A.NTracers;
+      B0.HessWeight = A.HessWeight, B0.FitCell = A.FitCell, B0.Tr = A.Tracers, B0.Hess = A.Hess;
+      B1.DirOwn = B2.DirOwn = A.EdgeDirOwn, B1.DirAcr = B2.DirAcr = A.EdgeDirAcross;
+      B1.Hess = B2.Hess = A.Hess, B1.Beta = B2.Beta = A.Beta;
+      launchTile(B0, M.NCellsAll, A.K, S);
+   }
    launchTile(B1, M.NCellsAll, A.K, S);
    launchTile(B2, M.NCellsAll, A.K, S);
+   return High ? 3 : 2;
 }
 
-void launchMonotoneAdv(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S) {
+int launchMonotoneAdv(const MeshView &M, const MonotoneAdvArgs &A, hipStream_t S) {
    if (A.NTracers <= 0)
-      return;
-   if (A.VerticalTransport != nullptr)
-      launchMonotoneAdvT<true>(M, A, S);
-   else
-      launchMonotoneAdvT<false>(M, A, S);
+      return 0;
+   const bool Vert = A.VerticalTransport != nullptr;
+   if (A.Hess != nullptr)
+      return Vert ? launchMonotoneAdvT<true, true>(M, A, S) : launchMonotoneAdvT<false, true>(M, A, S);
+   return Vert ? launchMonotoneAdvT<true, false>(M, A, S) : launchMonotoneAdvT<false, false>(M, A, S);
 }
 
 } // namespace OMEGA
