@@ -812,6 +812,45 @@ int omg_monoadv_copy_to_host(const omg_monoadv *a, const char *name, double *hos
  * twice.  The stepper keeps a pointer to a: detach before destroying it. */
 int omg_stepper_attach_monotone_adv(omg_stepper *st, omg_monoadv *a);
 
+/* ---- GentMcWilliams: the eddy-induced (bolus) velocity of the Gent-McWilliams closure on the edges, in the
+ * boundary-value form of Ferrari et al. (2010) -- one symmetric tridiagonal system per edge column (the reference has no
+ * code for it).  Numerical contract: omega_amd/csrc/GentMcWilliams.h.  Arrays are level-indexed device arrays as above.
+ * Every call is asynchronous on stream and allocates nothing.  The object keeps pointers to v and e: destroy it before
+ * them. ---- */
+typedef struct omg_gm omg_gm;
+/* kappa: the diffusivity every entry of "Kappa" starts with (m^2 s^-1, the class's default is 600); grav_wave_speed: c
+ * of the boundary-value problem (m s^-1, default 0.3).  Fails for a host-only mesh, a VertCoord or Eos of another mesh
+ * or layer count, more than 1024 layers, a kappa that is negative or not finite and a grav_wave_speed that is not
+ * finite or <= 0 */
+int omg_gm_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, double kappa, double grav_wave_speed, omg_gm **out);
+int omg_gm_destroy(omg_gm *g);
+/* the fused column pass (omg_vcoord_compute_column) from raw arrays: layer_thickness_dev [NCellsSize][pitch],
+ * tracers_dev [ntracers >= 2][NCellsSize][pitch] with temperature at index 0 and salinity at 1, the displaced volume at
+ * kdisp = 1, and the object's SurfacePressure / TidalPotential / SelfAttractionLoading */
+int omg_gm_update_column(omg_gm *g, const double *layer_thickness_dev, const double *tracers_dev, int ntracers,
+                         void *stream);
+/* "BolusVelocity" and "StreamFunction" on every edge's level range, from the Eos's SpecVol / SpecVolDisplaced and the
+ * VertCoord's ZMid as they stand; transport_dev [NEdgesSize][pitch] += BolusVelocity there (NULL: no term).  One launch */
+int omg_gm_compute(omg_gm *g, const double *layer_thickness_dev, double *transport_dev, void *stream);
+/* the same from the caller's [NCellsSize][pitch] arrays */
+int omg_gm_compute_arrays(omg_gm *g, const double *layer_thickness_dev, const double *spec_vol_dev,
+                          const double *spec_vol_displaced_dev, const double *z_mid_dev, double *transport_dev,
+                          void *stream);
+/* "Kappa" ([NEdgesSize], kappa at creation), "BolusVelocity", "StreamFunction" ([NEdgesSize][K], zero at creation; row K
+ * of StreamFunction is the interface at the top of layer K), "SurfacePressure", "TidalPotential",
+ * "SelfAttractionLoading" ([NCellsSize], zero at creation) */
+int omg_gm_device_ptr(const omg_gm *g, const char *name, double **dev, size_t *n);
+int omg_gm_copy_to_device(omg_gm *g, const char *name, const double *host, size_t n);
+int omg_gm_copy_to_host(const omg_gm *g, const char *name, double *host, size_t n);
+/* SplitExplicitStepper::attachGentMcWilliams (omega_amd/csrc/SplitExplicitStepper.h): every step of a "Split-Explicit"
+ * stepper adds the bolus velocity of the current level's stratification to its transporting velocity (g NULL: detach):
+ * omg_gm_update_column and omg_gm_compute on the current thickness and tracers between the transport velocity and the
+ * transport tendencies.  The prognostic velocity never sees it.  Fails for any other stepper type, a g of another mesh
+ * or layer count, a stepper with fewer than 2 tracers, and, while a PressureGrad is attached to the Tendencies, a g on
+ * another VertCoord or Eos than that PressureGrad's (omg_stepper_do_step checks again); the caller keeps the forcing
+ * arrays of the two objects equal.  The stepper keeps a pointer to g: detach before destroying it. */
+int omg_stepper_attach_gm(omg_stepper *st, omg_gm *g);
+
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at
  * dev + i * row_pitch (row_pitch 0: nrow).  x holds the right-hand side on entry and the solution on return; only

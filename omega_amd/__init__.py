@@ -2,7 +2,7 @@
 
 Thin ctypes plumbing used by tests/, bench.py and __graft_entry__.py: the product is the
 C++/HIP library under omega_amd/csrc (classes named after Omega's own: Decomp, Halo,
-HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, VertMix, VertMixStep, PressureGrad, VertAdv, Tendencies,
+HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, VertMix, VertMixStep, PressureGrad, VertAdv, GentMcWilliams, Tendencies,
 TimeStepper).  There is no
 Python or CPU implementation of the hot path here: if the shared library is missing,
 importing the binding raises, and without a HIP device every device call fails.
@@ -1460,6 +1460,61 @@ class BarotropicMode(_Handle, _NamedArrays):
         return (self.mesh.NEdgesSize, self.K) if s == "EK" else (self.mesh.NEdgesSize,)
 
 
+GM_ARRAYS = {"Kappa": "E", "BolusVelocity": "EK", "StreamFunction": "EK", "SurfacePressure": "C",
+             "TidalPotential": "C", "SelfAttractionLoading": "C"}
+
+
+class GentMcWilliams(_Handle, _NamedArrays):
+    """GentMcWilliams (omega_amd/csrc/GentMcWilliams.h): the eddy-induced (bolus) velocity of the Gent-McWilliams closure
+    on the edges from the stratification of `vcoord` / `eos`, one tridiagonal solve per edge column.  Level-indexed
+    inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles; the results are the
+    object's BolusVelocity and StreamFunction (`get`); `transport` is accumulated in place: a device address
+    (asynchronous on `stream`) or a numpy array (staged, computed, returned)."""
+    _destroy, _arrays = "omg_gm_destroy", "omg_gm"
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", kappa: float = 600.0,
+                 grav_wave_speed: float = 0.3):
+        self.mesh, self.vcoord, self.eos = mesh, vcoord, eos
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self._create("omg_gm_create", mesh.h, vcoord.h if vcoord is not None else None,
+                     eos.h if eos is not None else None, C.c_double(kappa), C.c_double(grav_wave_speed))
+
+    def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
+        """The fused column pass with the displaced volume (kdisp = 1) from raw arrays: thickness [NCellsSize][K],
+        tracers [ntracers][NCellsSize][K] (temperature 0, salinity 1), with this object's SurfacePressure /
+        TidalPotential / SelfAttractionLoading."""
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
+        _chk(lib().omg_gm_update_column(self.h, h, t, int(ntracers), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def compute(self, layer_thickness, transport=None, spec_vol=None, spec_vol_displaced=None, z_mid=None, stream=None):
+        """BolusVelocity and StreamFunction from the three given cell arrays (the array form; all three or none), or from
+        the Eos's and the VertCoord's arrays as they stand; transport += BolusVelocity if it is given."""
+        given = [x is not None for x in (spec_vol, spec_vol_displaced, z_mid)]
+        assert all(given) or not any(given), "give SpecVol, SpecVolDisplaced and ZMid, or none of them"
+        keep, n = [], self.mesh.NCellsSize
+        p, buf = (None, None) if transport is None else _stage_levels(transport, (self.mesh.NEdgesSize,), self.K)
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        if all(given):
+            _chk(lib().omg_gm_compute_arrays(self.h, h, _level_dev(spec_vol, n, self.K, keep),
+                                             _level_dev(spec_vol_displaced, n, self.K, keep),
+                                             _level_dev(z_mid, n, self.K, keep), p, _sh(stream)))
+        else:
+            _chk(lib().omg_gm_compute(self.h, h, p, _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def _shape(self, name):
+        s = GM_ARRAYS.get(name, "C")  # (an unknown name: the library says so)
+        if s == "C":
+            return (self.mesh.NCellsSize,)
+        return (self.mesh.NEdgesSize, self.K) if s == "EK" else (self.mesh.NEdgesSize,)
+
+
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""
@@ -1640,6 +1695,14 @@ class TimeStepper(_Handle):
         that differs from the AuxiliaryState's, and while the Tendencies' own TracerHorzAdvTendencyEnable is on."""
         _chk(lib().omg_stepper_attach_monotone_adv(self.h, mono.h if mono is not None else None))
         self._monotone_adv = mono  # the library keeps a pointer to it
+
+    def attach_gent_mcwilliams(self, gm: "GentMcWilliams | None"):
+        """SplitExplicitStepper::attachGentMcWilliams: every step adds the bolus velocity of the current level's
+        stratification to its transporting velocity (None detaches); raises on any other kind, for another mesh or layer
+        count, fewer than 2 tracers, and, with a PressureGrad attached to the Tendencies, for a `gm` on another VertCoord
+        or Eos than its (the caller keeps the forcing arrays of the two equal)."""
+        _chk(lib().omg_stepper_attach_gm(self.h, gm.h if gm is not None else None))
+        self._gent_mcwilliams = gm  # the library keeps a pointer to it
 
     def set_fused_transport(self, on: bool):
         """SplitExplicitStepper::UseFusedTransport (default on): the step's thickness and tracer tendencies through

@@ -1,5 +1,6 @@
 // SplitExplicitStepper.cpp -- see SplitExplicitStepper.h.
 #include "SplitExplicitStepper.h"
+#include "PressureGrad.h"
 
 namespace OMEGA {
 
@@ -49,10 +50,35 @@ void SplitExplicitStepper::attachMonotoneAdv(MonotoneAdv *M) {
    Mono = M;
 }
 
+void SplitExplicitStepper::requireGentMcWilliamsFits(const GentMcWilliams *G, const char *Where) const {
+   const std::string W = std::string(Where) + ": ";
+   OMEGA_REQUIRE(G->Mesh == Mesh && G->NVertLayers == Tend->LayerThicknessTend.Ext[1],
+                 W + "the GentMcWilliams was built for another mesh or layer count");
+   OMEGA_REQUIRE(Tend->NTracers >= 2, W + "the stepper has " + std::to_string(Tend->NTracers) +
+                                          " tracers: the column pass needs temperature and salinity (tracers 0 and 1)");
+   if (const PressureGrad *P = Tend->pressureGrad()) // two column passes on two sets of column fields: refused
+      OMEGA_REQUIRE(G->VCoord == P->VCoord && G->EqState == P->EqState,
+                    W + "the GentMcWilliams and the PressureGrad attached to the Tendencies are on different VertCoord "
+                        "or Eos objects: both run the column pass, on one set of column fields, and keeping their "
+                        "forcing arrays equal is the caller's responsibility");
+}
+
+void SplitExplicitStepper::attachGentMcWilliams(GentMcWilliams *G) {
+   if (G == nullptr) {
+      GM = nullptr;
+      return;
+   }
+   OMEGA_REQUIRE(Tend && Mesh && Trc, "SplitExplicitStepper::attachGentMcWilliams: attachData first");
+   requireGentMcWilliamsFits(G, "SplitExplicitStepper::attachGentMcWilliams");
+   GM = G;
+}
+
 void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    OMEGA_REQUIRE(Btr != nullptr, "Split-Explicit doStep: no BarotropicMode is attached: attachBarotropic first");
    if (Mono)
       requireMonotoneAdvFits(Mono, "Split-Explicit doStep");
+   if (GM)
+      requireGentMcWilliamsFits(GM, "Split-Explicit doStep");
    requireHealthyWire();
    const int CurLevel = 0, NextLevel = 1;
    const StepArrays A = stepArrays("Split-Explicit", State);
@@ -70,6 +96,10 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    Btr->subcycle(NSub, Dt / (R8)NSub, S);
    // h^{n+1} and phi^{n+1} by the transporting velocity: baroclinic u^{n} + the sub-cycle's mean flux over the thickness
    Btr->transportVelocity(A.CurU, A.NextU, S);
+   if (GM) { // ... plus the eddy-induced velocity of the stratification of h^{n}, phi^{n}
+      GM->updateColumn(A.CurH, A.CurTr, S);
+      GM->computeBolusVelocity(A.CurH, A.NextU, S);
+   }
    // (with tracers and their hyperdiffusion term off the tracer update rides in the first transport launch, which loses a
    // wave to it: measured no faster than the three calls, DESIGN.md section 4.9, so those run)
    const bool Fold = UseFusedTransport && FoldUpdates && (Tend->NTracers <= 0 || Tend->Params.TracerHyperDiffTendencyEnable);

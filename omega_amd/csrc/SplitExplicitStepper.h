@@ -53,12 +53,29 @@
 // current after the transport call, h[Next] after the thickness update -- and the VertAdv's TracerTermEnable must be
 // off (two vertical terms are refused like two horizontal ones).  With nothing attached the step is what it was.
 //
+// With a GentMcWilliams attached (attachGentMcWilliams; GentMcWilliams.h) the transporting velocity also carries the
+// eddy-induced (bolus) velocity: between steps 5 and 6 the step gains
+//   5b. GM->updateColumn(h[Cur], CurTracers);  GM->computeBolusVelocity(h[Cur], u[Next])
+// -- the column pass with the displaced volume on the step's own arrays (nothing is copied or allocated before it), then
+// the one launch that adds BolusVelocity to u[Next] on every edge's level range.  Steps 6-7 read nothing else of the flow,
+// so the thickness and tracer tendencies, an attached VertAdv (it takes its transport from step 6) and an attached
+// MonotoneAdv (it reads u[Next]) pick the bolus flow up unchanged.  Step 8 overwrites every level of u[Next]: the bolus
+// part never reaches the prognostic velocity.  Step 5b leaves the column fields of the GentMcWilliams's VertCoord and
+// Eos as a Displaced = true, KDisp = 1 pass of h[Cur], CurTracers and the GentMcWilliams's forcing leaves them.  With a
+// PressureGrad attached to the Tendencies the two objects must share one VertCoord and one Eos (anything else is
+// refused), and each runs the column pass with its own SurfacePressure / TidalPotential / SelfAttractionLoading: keeping
+// the two sets of forcing equal is the caller's responsibility -- the stepper cannot compare device arrays without
+// copying them -- or the column fields after the step are those of the GentMcWilliams's forcing, not the PressureGrad's
+// (step 1 of the next step refreshes them before anything reads them).  With nothing attached the step, its launch
+// count and its bits are what they were.
+//
 // One rank only: BarotropicMode knows no Halo, and more sub-steps than the halo is wide need an exchange per sub-step;
 // attachBarotropic refuses a stepper whose Halo has neighbours.
 #ifndef OMEGA_AMD_SPLITEXPLICITSTEPPER_H
 #define OMEGA_AMD_SPLITEXPLICITSTEPPER_H
 
 #include "BarotropicMode.h"
+#include "GentMcWilliams.h"
 #include "MonotoneAdv.h"
 #include "TimeStepper.h"
 
@@ -97,6 +114,13 @@ class SplitExplicitStepper : public TimeStepper {
    void attachMonotoneAdv(MonotoneAdv *M);
    MonotoneAdv *monotoneAdv() const { return Mono; }
 
+   /// Opt-in (after attachData): step 5b above through G; nullptr detaches.  Refuses (OmegaError) a GentMcWilliams of
+   /// another mesh or layer count, a stepper with fewer than 2 tracers (temperature and salinity are tracers 0 and 1),
+   /// and, while a PressureGrad is attached to the Tendencies, a GentMcWilliams on another VertCoord or Eos than that
+   /// PressureGrad's (checked again in every step).  The stepper keeps the pointer.
+   void attachGentMcWilliams(GentMcWilliams *G);
+   GentMcWilliams *gentMcWilliams() const { return GM; }
+
    void doStep(OceanState *State, hipStream_t S) override;
    using TimeStepper::doStep;
 
@@ -104,6 +128,9 @@ class SplitExplicitStepper : public TimeStepper {
    BarotropicMode *Btr = nullptr;
    int NSub            = 0;
    MonotoneAdv *Mono   = nullptr;
+   GentMcWilliams *GM  = nullptr;
+   /// what attachGentMcWilliams refuses and doStep checks again (a PressureGrad may have been attached since)
+   void requireGentMcWilliamsFits(const GentMcWilliams *G, const char *Where) const;
    /// what attachMonotoneAdv refuses and doStep checks again (the options may have changed since)
    void requireMonotoneAdvFits(const MonotoneAdv *M, const char *Where) const;
 };

@@ -21,6 +21,7 @@
 #include "Eos.h"
 #include "TriDiagSolvers.h"
 #include "VertMix.h"
+#include "GentMcWilliams.h"
 #include "PressureGrad.h"
 #include "MonotoneAdv.h"
 #include "VertAdv.h"
@@ -93,6 +94,9 @@ struct omg_btr {
 };
 struct omg_monoadv {
    std::unique_ptr<MonotoneAdv> A;
+};
+struct omg_gm {
+   std::unique_ptr<GentMcWilliams> G;
 };
 
 static thread_local std::string LastError;
@@ -2103,6 +2107,67 @@ int omg_stepper_attach_monotone_adv(omg_stepper *st, omg_monoadv *a) {
    OMG_TRY
    OMG_ARG(st);
    splitExplicit(st, "attachMonotoneAdv")->attachMonotoneAdv(a ? a->A.get() : nullptr);
+   OMG_CATCH
+}
+
+// ---- GentMcWilliams (GentMcWilliams.h)
+int omg_gm_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, double kappa, double grav_wave_speed, omg_gm **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   newHandle(out, [&](omg_gm &R) {
+      R.G.reset(new GentMcWilliams("Default", m->M.get(), v ? v->V.get() : nullptr, e ? e->E.get() : nullptr, kappa,
+                                   grav_wave_speed));
+   });
+   OMG_CATCH
+}
+int omg_gm_destroy(omg_gm *g) {
+   delete g;
+   return 0;
+}
+int omg_gm_update_column(omg_gm *g, const double *layer_thickness, const double *tracers, int ntracers, void *stream) {
+   OMG_TRY
+   OMG_ARG(g && layer_thickness && tracers && ntracers >= 2);
+   const HorzMesh *M = g->G->Mesh;
+   const int K       = g->G->NVertLayers;
+   g->G->updateColumn(levelView(layer_thickness, M->NCellsSize, K), tracerView(tracers, ntracers, M->NCellsSize, K),
+                      (hipStream_t)stream);
+   OMG_CATCH
+}
+/// the optional transport of the two compute calls: NULL is the empty array (no term)
+static Array2DReal gmTransport(const GentMcWilliams &G, double *Transport) {
+   return Transport ? levelView(Transport, G.Mesh->NEdgesSize, G.NVertLayers) : Array2DReal();
+}
+int omg_gm_compute(omg_gm *g, const double *layer_thickness, double *transport, void *stream) {
+   OMG_TRY
+   OMG_ARG(g && layer_thickness);
+   g->G->computeBolusVelocity(levelView(layer_thickness, g->G->Mesh->NCellsSize, g->G->NVertLayers),
+                              gmTransport(*g->G, transport), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_gm_compute_arrays(omg_gm *g, const double *layer_thickness, const double *spec_vol,
+                          const double *spec_vol_displaced, const double *z_mid, double *transport, void *stream) {
+   OMG_TRY
+   OMG_ARG(g && layer_thickness && spec_vol && spec_vol_displaced && z_mid);
+   const int N = g->G->Mesh->NCellsSize, K = g->G->NVertLayers;
+   g->G->computeBolusVelocity(levelView(layer_thickness, N, K), levelView(spec_vol, N, K),
+                              levelView(spec_vol_displaced, N, K), levelView(z_mid, N, K), gmTransport(*g->G, transport),
+                              (hipStream_t)stream);
+   OMG_CATCH
+}
+static ArrRef gmLookup(const GentMcWilliams &G, const char *Name) {
+   return findNamed<ArrRef>({{"Kappa", arrRef(G.Kappa)},
+                             {"BolusVelocity", arrRef(G.BolusVelocity)},
+                             {"StreamFunction", arrRef(G.StreamFunction)},
+                             {"SurfacePressure", arrRef(G.SurfacePressure)},
+                             {"TidalPotential", arrRef(G.TidalPotential)},
+                             {"SelfAttractionLoading", arrRef(G.SelfAttractionLoading)}},
+                            Name, "GentMcWilliams: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_gm_copy_to_host, omg_gm_copy_to_device, omg_gm_device_ptr, omg_gm, g, gmLookup(*g->G, name))
+int omg_stepper_attach_gm(omg_stepper *st, omg_gm *g) {
+   OMG_TRY
+   OMG_ARG(st);
+   splitExplicit(st, "attachGentMcWilliams")->attachGentMcWilliams(g ? g->G.get() : nullptr);
    OMG_CATCH
 }
 
