@@ -1,0 +1,240 @@
+"""One Split-Explicit step on the host: the sequence of omega_amd/csrc/SplitExplicitStepper.h and VertMixStep.h composed
+from the restatements the pieces are already pinned against -- the C oracle for the three tendencies and the tangential
+reconstruction, tests/column_reference.py for the column pass, and the NumPy restatements of PressureGrad, VertAdv,
+BarotropicMode and the stepper's glue, MonotoneAdv (2-D, 3-D, high order), GentMcWilliams and the forced VertMix solves.
+Nothing here calls a device: the mesh tables come from an oa.HorzMesh (host-only will do) and, for the high-order
+flux, from omg_monoadv_high_order_tables, as the CPU tests of the pieces take them.
+
+Arrays are host arrays in the library's local order: [NCellsSize][K], [NEdgesSize][K], [NT][NCellsSize][K].  Every
+array the product keeps after a step is kept here under the product's name; an entry no contract names keeps what it
+held, so a rig that seeds such entries alike on both sides can compare whole arrays.
+
+`deviations` names plausible mistakes of the sequence (DEVIATIONS).  They exist for tests/test_model_step.py, which shows
+that every one of them changes the state on the rigs the device is compared on: the comparison can tell the sequences
+apart."""
+import ctypes as C
+
+import numpy as np
+
+from oracle import oracle as O
+from tests import column_reference as CR
+from tests import gent_mcwilliams_reference as GR
+from tests import monotone_adv3d_reference as M3
+from tests import monotone_adv_ho_reference as HO
+from tests import monotone_adv_reference as MR
+from tests import pressure_grad_reference as PR
+from tests import split_explicit_reference as SR
+from tests import vert_adv_reference as VR
+from tests import vert_mix_forcing_reference as FR
+from tests import vert_mix_reference as XR
+from tests.barotropic_fixtures import GRAVITY, btr_mesh
+
+RHO0 = 1026.0
+COLUMN_FIELDS = ("PressureInterface", "PressureMid", "ZInterface", "ZMid", "GeopotentialMid", "SpecVol", "SpecVolDisplaced")
+BTR_FIELDS = ("SSH", "BtrVelocity", "BtrForcing", "BtrFluxMean", "BtrTendMean", "BtrThickEdge", "BclVelocity")
+DEVIATIONS = (
+    "gm_reads_h_next",            # step 5b fed h[Next] instead of h[Cur]
+    "transport_from_step_1",      # VertAdv's VerticalTransport left from step 1, not retaken in step 6
+    "mono_reads_u_cur",           # MonotoneAdv given u[Cur], not the transporting velocity
+    "mono_reads_h_cur_as_new",    # MonotoneAdv given h[Cur] as the new thickness
+    "tracers_divided_by_h_cur",   # the tracer update divided by h[Cur]
+    "bolus_left_in_velocity",     # the bolus velocity left in the prognostic velocity
+    "pressure_grad_first",        # the pressure gradient subtracted before the vertical advection
+    "mix_on_the_old_level",       # VertMixStep applied to the old level
+    "btr_velocity_reset",         # BtrVelocity reset between steps: before step 1 of every time step, where it is dead
+                                  # (step 2 rewrites it on every edge), and between steps 5 and 8 of the sequence,
+                                  # where it is live (step 8 adds the velocity the sub-cycle ended with)
+)
+
+
+def options(**over):
+    """What is attached, and how.  pgrad / gm / mix: bool; vert_adv: None or VertAdv's TracerFluxOrder; tracer_term:
+    VertAdv::TracerTermEnable; mono: None or (order, Coef3rdOrder); mono_3d: the MonotoneAdv has the VertAdv attached;
+    eos: "teos10" or "linear" with `linear` = (DRhoDT, DRhoDS, RhoT0S0); upwind: FluxThicknessUpwind (the MonotoneAdv's
+    too); mix_config: VertMix's; cd, ra, wind: VertMixStep's boundary."""
+    o = dict(pgrad=False, vert_adv=None, tracer_term=True, mono=None, mono_3d=False, gm=False, mix=False, eos="teos10",
+             linear=(-0.2, 0.8, 1000.0), upwind=False, gm_speed=0.3, mix_config=None, cd=0.0, ra=0.0, wind=False)
+    for k, v in over.items():
+        if k not in o:
+            raise KeyError(k)
+        o[k] = v
+    return o
+
+
+class HostModel:
+    """mesh: an oa.HorzMesh; g: its mesh dictionary (the periods or the radius of the high-order tables); oracle: an
+    oracle.Oracle on mesh.local_arrays() under the Tendencies' options; h, u, tr: two time levels each ([Cur, Next]: the
+    second holds the rig's seed); lo, hi: MinLayerCell / MaxLayerCell [NCellsSize]; bottom, ref: BottomDepth
+    [NCellsSize], RefLayerThickness [NCellsSize][K]; forcing: dict SurfacePressure, TidalPotential,
+    SelfAttractionLoading [NCellsSize] (one set: the stepper requires the objects' sets to be equal), Kappa,
+    NormalStressEdge [NEdgesSize], SurfaceTracerFlux [NT][NCellsSize]; column: the column fields as they stand before
+    the first step (dict of COLUMN_FIELDS); opt: options()."""
+
+    def __init__(self, mesh, g, oracle, K, nt, h, u, tr, lo, hi, bottom, ref, forcing, column, opt, dt, nsub,
+                 deviations=()):
+        for d in deviations:
+            if d not in DEVIATIONS:
+                raise KeyError(d)
+        self.mesh, self.g, self.orc, self.K, self.nt, self.opt = mesh, g, oracle, K, nt, opt
+        self.dev = frozenset(deviations)
+        self.dt_seconds, self.nsub = float(dt), int(nsub)
+        self.dt = O.coeff_seconds(1.0, self.dt_seconds)
+        self.nc, self.ne, self.nc_size, self.ne_size = mesh.NCellsAll, mesh.NEdgesAll, mesh.NCellsSize, mesh.NEdgesSize
+        self.nc_own, self.ne_own = mesh.NCellsOwned, mesh.NEdgesOwned
+        self.h, self.u, self.tr = [a.copy() for a in h], [a.copy() for a in u], [a.copy() for a in tr]
+        self.start = (self.h[0].copy(), self.u[0].copy(), self.tr[0].copy())
+        self.lo, self.hi = np.asarray(lo, np.int32), np.asarray(hi, np.int32)
+        self.bottom, self.ref = np.asarray(bottom, float), np.asarray(ref, float)
+        self.weights = CR.movement_weights("Uniform", K)
+        self.f = forcing
+        get = mesh.get_array
+        self.coe, self.dc, self.dv, self.area = get("CellsOnEdge"), get("DcEdge"), get("DvEdge"), get("AreaCell")
+        self.neoc, self.eoc = get("NEdgesOnCell"), get("EdgesOnCell")
+        self.mask = np.ascontiguousarray(get("EdgeMask")[:, 0])
+        self.lo_e, self.hi_e = PR.edge_ranges(self.coe, self.ne, self.lo, self.hi, K)
+        self.e_range = np.zeros((self.ne_size, K), bool)
+        self.e_range[: self.ne] = PR.range_mask(self.lo_e, self.hi_e, self.ne, K)
+        self.c_range = np.zeros((self.nc_size, K), bool)
+        self.c_range[: self.nc] = VR.active_mask(self.lo, self.hi, self.nc, K)
+        # what the product keeps
+        self.split = SR.Split(btr_mesh(mesh, self.bottom), self.nc_size, self.ne_size, K)
+        self.LayerThicknessTend, self.NormalVelocityTend, self.TracerTend = oracle.hTend, oracle.uTend, oracle.trTend
+        self.BolusVelocity, self.StreamFunction = np.zeros((self.ne_size, K)), np.zeros((self.ne_size, K))
+        self.VerticalTransport = np.zeros((self.nc_size, K))
+        self.ScaleIn, self.ScaleOut = np.zeros((nt, self.nc_size, K)), np.zeros((nt, self.nc_size, K))
+        self.Hess = np.zeros((nt, 3, self.nc_size, K))
+        self.VertVisc, self.VertDiff, self.BruntVaisalaFreqSq = (np.zeros((self.nc_size, K)) for _ in range(3))
+        self.TangentialVelocity = np.zeros((self.ne_size, K))
+        self.column = {k: np.array(column[k], dtype=np.float64) for k in COLUMN_FIELDS}
+        self.transporting_velocity = self.unmixed = None  # of the last step: u[Next] after 5b; (u, tracers) before the solves
+        self.mono_mesh = self.tables = None
+        if opt["mono"] is not None:
+            self.mono_mesh = MR.MonoMesh.of(mesh)
+            order, coef = opt["mono"]
+            if order != 2:
+                self.tables = HO.HoTables.of(self.mono_mesh, mesh, g, order, coef)
+        self.mix_config = XR.config(**(opt["mix_config"] or {}))
+        self.steps_done = 0
+
+    # ---- the named arrays of the BarotropicMode
+    def btr(self, name):
+        s = self.split
+        return dict(SSH=s.ssh, BtrVelocity=s.vel, BtrForcing=s.forcing, BtrFluxMean=s.flux, BtrTendMean=s.tend_mean,
+                    BtrThickEdge=s.thick, BclVelocity=s.bcl)[name]
+
+    # ---- the pieces
+    def column_pass(self, h, tr, displaced):
+        f = self.f
+        CR.column_sequence(h, tr[0], tr[1], f["SurfacePressure"], f["TidalPotential"], f["SelfAttractionLoading"],
+                           self.bottom, self.lo, self.hi, self.nc, RHO0, self.opt["eos"], self.column,
+                           1 if displaced else None, self.opt["linear"])
+
+    def take_transport(self, thickness_tend):
+        VR.vertical_transport(thickness_tend, self.ref, self.weights, self.lo, self.hi, self.nc, self.VerticalTransport)
+
+    def momentum_rhs(self, h, u, tr):
+        """step 1: NormalVelocityTend; with a VertAdv also VerticalTransport of (h, u)"""
+        o, orc = self.opt, self.orc
+        if o["vert_adv"] is not None:
+            self.take_transport(orc.compute_thickness_tendencies(h, u))
+        tend = orc.compute_velocity_tendencies(h, u)
+
+        def vert_adv():
+            if o["vert_adv"] is not None:
+                VR.add_velocity_tend(tend, h, u, self.VerticalTransport, self.coe, self.mask, self.lo_e, self.hi_e, self.ne)
+
+        def pressure_grad():
+            if o["pgrad"]:
+                self.column_pass(h, tr, False)
+                c = self.column
+                PR.pressure_grad(tend, c["PressureMid"], c["GeopotentialMid"], c["SpecVol"], self.coe, self.dc, self.mask,
+                                 self.lo_e, self.hi_e, self.ne)
+
+        for term in ((pressure_grad, vert_adv) if "pressure_grad_first" in self.dev else (vert_adv, pressure_grad)):
+            term()
+        return tend
+
+    def bolus(self, h, tr, u_transport):
+        """step 5b"""
+        self.column_pass(h, tr, True)
+        c = self.column
+        GR.bolus_velocity(h, c["SpecVol"], c["SpecVolDisplaced"], c["ZMid"], self.coe, self.dc, self.f["Kappa"], self.lo_e,
+                          self.hi_e, self.ne, RHO0, self.opt["gm_speed"], self.BolusVelocity, self.StreamFunction,
+                          u_transport)
+
+    def limited_advection(self, tend, h_old, h_new, u, tr):
+        o, M = self.opt, self.mono_mesh
+        args = (h_old, h_new, u, tr, self.nt, self.dt, o["upwind"], self.ScaleIn, self.ScaleOut)
+        vert = (self.VerticalTransport, self.lo, self.hi)
+        if self.tables is not None:
+            HO.add_tracer_tend(self.tables, tend, *args, self.Hess, vert if o["mono_3d"] else None)
+        elif o["mono_3d"]:
+            M3.add_tracer_tend(M, tend, *args, *vert)
+        else:
+            MR.add_tracer_tend(M, tend, *args)
+
+    def transport(self, h, tr, u_transport):
+        """steps 5b, 6 and 7 on the transporting velocity of step 5: h[Next] and NextTracers"""
+        o, orc, n, dev = self.opt, self.orc, self.nc, self.dev
+        h_next, tr_next = self.h[1], self.tr[1]
+        u_transport[self.ne:] = self.u[1][self.ne:]  # (the rows transportVelocity does not write)
+        if "btr_velocity_reset" in dev:  # between the sub-cycle and advanceVelocity
+            self.split.vel[:] = 0.0
+        if o["gm"]:
+            self.bolus(h_next if "gm_reads_h_next" in dev else h, tr, u_transport)
+        self.transporting_velocity = u_transport.copy()
+        # 6
+        th = orc.compute_thickness_tendencies(h, u_transport)
+        if o["vert_adv"] is not None:
+            if "transport_from_step_1" not in dev:
+                self.take_transport(th)
+            VR.add_thickness_tend(th, self.VerticalTransport, self.lo, self.hi, n)
+        h_next[:n] = h[:n] + self.dt * th[:n]
+        # 7
+        tt = orc.compute_tracer_tendencies(h, u_transport, tr)
+        if o["vert_adv"] is not None and o["tracer_term"]:
+            VR.add_tracer_tend(tt[: self.nt], h, tr, self.VerticalTransport, self.lo, self.hi, n, o["vert_adv"])
+        if o["mono"] is not None:
+            self.limited_advection(tt, h, h if "mono_reads_h_cur_as_new" in dev else h_next,
+                                   self.u[0] if "mono_reads_u_cur" in dev else u_transport, tr)
+        with np.errstate(all="ignore"):
+            den = h if "tracers_divided_by_h_cur" in dev else h_next
+            tr_next[:, :n] = (tr[:, :n] * h[:n] + self.dt * tt[: self.nt, :n]) / den[:n]
+
+    def mix(self, h, u, tr):
+        """step 9: the six calls of VertMixStep::apply, in place on u and tr"""
+        o, n = self.opt, self.nc
+        self.column_pass(h, tr, True)
+        c = self.column
+        self.BruntVaisalaFreqSq = XR.bvf(c["SpecVol"], c["SpecVolDisplaced"], c["ZMid"], self.lo, self.hi, n, RHO0)
+        O.lib().orc_tangential_recon_on_edge(C.byref(self.orc.m.s), self.ne, O._pd(self.TangentialVelocity),
+                                             O._pd(np.ascontiguousarray(u)))
+        self.VertVisc, self.VertDiff = XR.coefficients(u, self.TangentialVelocity, self.BruntVaisalaFreqSq, c["ZMid"],
+                                                       self.lo, self.hi, n, self.neoc, self.eoc, self.dc, self.dv, self.area,
+                                                       self.mix_config)
+        self.unmixed = (u.copy(), tr.copy())
+        tr[:] = FR.tracer_mix_forced(h, self.VertDiff, tr, self.nt, self.dt_seconds, self.lo, self.hi, self.nc_own,
+                                     self.f["SurfaceTracerFlux"])
+        u[:] = FR.velocity_mix_forced(h, self.VertVisc, u, self.dt_seconds, self.coe, self.lo_e, self.hi_e, self.ne_own,
+                                      cd=o["cd"], ra=o["ra"], stress=self.f["NormalStressEdge"] if o["wind"] else None,
+                                      ut=self.TangentialVelocity, edge_mask=self.mask, rho0=RHO0)
+
+    # ---- the step
+    def step(self):
+        h, u, tr = self.h[0], self.u[0], self.tr[0]
+        if "btr_velocity_reset" in self.dev:
+            self.split.vel[:] = 0.0
+        vel_tend = self.momentum_rhs(h, u, tr)                                                      # 1
+        u_new, _ = SR.step(self.split, h, u, vel_tend, self.dt, self.nsub, self.lo, self.hi, self.lo_e, self.hi_e,
+                           GRAVITY, lambda u_transport: self.transport(h, tr, u_transport))         # 2-5, 5b-7, 8
+        u_new[self.ne:] = self.u[1][self.ne:]
+        if "bolus_left_in_velocity" in self.dev:
+            u_new[self.e_range] = u_new[self.e_range] + self.BolusVelocity[self.e_range]
+        self.u[1][:] = u_new
+        if self.opt["mix"]:                                                                         # 9
+            level = 0 if "mix_on_the_old_level" in self.dev else 1
+            self.mix(self.h[level], self.u[level], self.tr[level])
+        for a in (self.h, self.u, self.tr):
+            a.reverse()
+        self.steps_done += 1
+        return self.h[0], self.u[0], self.tr[0]
