@@ -64,7 +64,7 @@
 // 3-D form below limits both.
 //
 // The 3-D form (attachVertAdv(V); same rules: FP64, -ffp-contract=off, every chain in the order written, the same max
-// and min; a NumPy restatement in the same order is bit-identical, tests/monotone_adv3d_reference.py).  Everything
+// and min; a NumPy restatement in the same order is bit-identical, tests/monotone_adv_reference.py).  Everything
 // about the horizontal edges stays as written above: Fm, FLow, FHigh, A, the slot order, the masking.
 //
 //  Interfaces of a cell c < NCellsAll with KMin .. KMax = MinLayerCell[c] .. MaxLayerCell[c] of V->VCoord,
@@ -109,7 +109,7 @@
 //
 // The high-order horizontal flux (setHorzOrder(3 or 4); same rules: FP64, -ffp-contract=off, every chain in the order
 // written, the same max and min; a NumPy restatement in the same order that reads the tables from the object is
-// bit-identical, tests/monotone_adv_ho_reference.py).  OmegaV0ShallowWater.md section 3.5.1 describes MPAS-Ocean's
+// bit-identical, tests/monotone_adv_reference.py).  OmegaV0ShallowWater.md section 3.5.1 describes MPAS-Ocean's
 // transport as "fourth order under normal conditions, and reduces to third order to preserve monotonicity"
 // (Skamarock and Gassmann 2011): the centred edge value is corrected by the second derivative of phi along the line
 // between the two cells, taken from a least-squares quadratic at each of them.  Zalesak's argument holds for any FHigh,

@@ -17,7 +17,7 @@ import omega_amd as oa
 from omega_amd.meshgen import planar_hex
 from tests import column_reference as CR
 from tests import model_step_reference as HM
-from tests import monotone_adv_ho_reference as HO
+from tests import monotone_adv_reference as MR
 from tests.meshes import named_mesh
 from tests.problem import Problem
 from tests.vert_fixtures import mix_inputs
@@ -212,7 +212,7 @@ class ModelRig:
                 self.mono.attach_vert_adv(self.va)
             order, coef = o["mono"]
             if order != 2:
-                self.mono.set_horz_order(order, coef, **HO.geometry(self.g))
+                self.mono.set_horz_order(order, coef, **MR.geometry(self.g))
             st.attach_monotone_adv(self.mono)
         if o["gm"]:
             self.gm = oa.GentMcWilliams(m, vc, self.eos, grav_wave_speed=o["gm_speed"])

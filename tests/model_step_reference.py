@@ -19,8 +19,6 @@ import numpy as np
 from oracle import oracle as O
 from tests import column_reference as CR
 from tests import gent_mcwilliams_reference as GR
-from tests import monotone_adv3d_reference as M3
-from tests import monotone_adv_ho_reference as HO
 from tests import monotone_adv_reference as MR
 from tests import pressure_grad_reference as PR
 from tests import split_explicit_reference as SR
@@ -112,7 +110,7 @@ class HostModel:
             self.mono_mesh = MR.MonoMesh.of(mesh)
             order, coef = opt["mono"]
             if order != 2:
-                self.tables = HO.HoTables.of(self.mono_mesh, mesh, g, order, coef)
+                self.tables = MR.HoTables.of(self.mono_mesh, mesh, g, order, coef)
         self.mix_config = XR.config(**(opt["mix_config"] or {}))
         self.steps_done = 0
 
@@ -163,15 +161,10 @@ class HostModel:
                           u_transport)
 
     def limited_advection(self, tend, h_old, h_new, u, tr):
-        o, M = self.opt, self.mono_mesh
-        args = (h_old, h_new, u, tr, self.nt, self.dt, o["upwind"], self.ScaleIn, self.ScaleOut)
-        vert = (self.VerticalTransport, self.lo, self.hi)
-        if self.tables is not None:
-            HO.add_tracer_tend(self.tables, tend, *args, self.Hess, vert if o["mono_3d"] else None)
-        elif o["mono_3d"]:
-            M3.add_tracer_tend(M, tend, *args, *vert)
-        else:
-            MR.add_tracer_tend(M, tend, *args)
+        o = self.opt
+        MR.add_tracer_tend(self.mono_mesh, tend, h_old, h_new, u, tr, self.nt, self.dt, o["upwind"], self.ScaleIn, self.ScaleOut,
+                           vert=(self.VerticalTransport, self.lo, self.hi) if o["mono_3d"] else None,
+                           high=(self.tables, self.Hess) if self.tables is not None else None)
 
     def transport(self, h, tr, u_transport):
         """steps 5b, 6 and 7 on the transporting velocity of step 5: h[Next] and NextTracers"""

@@ -1,11 +1,23 @@
-"""NumPy restatement of the MonotoneAdv numerical contract (omega_amd/csrc/MonotoneAdv.h).
+"""NumPy restatement of the MonotoneAdv numerical contract (omega_amd/csrc/MonotoneAdv.h): the 2-D form, the 3-D form
+and the high-order horizontal flux.  Each pass is stated once; the vertical part and the high-order correction are
+optional inputs of it, as the header adds them to the passes it has written:
+
+  vert = (wt, lo, hi)   "The 3-D form": VerticalTransport [NCellsSize][K], MinLayerCell / MaxLayerCell [NCellsSize]
+  high = (H, hess)      "The high-order horizontal flux": a HoTables and one tracer's Hess [3][NCellsSize][K]
+
+With neither (None, the default) every chain is the 2-D one as written -- not the longer one with zeros in it.
 
 Every output is the FP64 evaluation order the contract states; the library is built with -ffp-contract=off, so the
 device results equal these bit for bit.  The sums over a cell's slots are vectorised across cells, one slot at a time:
 each cell still sees its own additions in slot order.  max and min are the contract's comparisons (`kmax`, `kmin`).
+The high-order tables (FitCell, HessWeight, EdgeDirOwn, EdgeDirAcross) are read from the library: a least-squares solve
+is not restated bit for bit.
 
 Arrays are host arrays in the library's local order: cell arrays [NCellsSize][K], edge arrays [NEdgesSize][K], tracer
 arrays [NTracers][NCellsSize][K].  Rows >= NCellsAll / NEdgesAll may hold anything, NaN included: they are never read.
+Interface K is the top of layer K; values at an interface outside lo < K <= hi are selected to 0.0 and whatever the
+arithmetic made of the (possibly NaN) operands there is dropped.  Hess rows of cells that are not fit cells hold 0.0 on
+the device; here they may hold anything, NaN included: no edge term selects them.
 """
 import numpy as np
 
@@ -55,8 +67,137 @@ class MonoMesh:
                 yield r, e, self.coe[e, 0], self.coe[e, 1], self.sign[r, j]
 
 
-def edge_terms(M, e, c0, c1, h_old, u, phi, upwind):
-    """(Fm, FLow, FHigh, A) of the edges e, [len(e)][K], in edge orientation"""
+# ---- the high-order flux: tables and pass 0 ----
+
+class HoTables:
+    """The library's tables on a MonoMesh `M`, and per edge what both cells of it see: `q0[e]`, `q1[e]` the direction
+    coefficients on c0's and c1's side ([NEdgesAll][3]) and `high[e]`."""
+
+    def __init__(self, M, tables, beta):
+        self.M, self.beta = M, float(beta)
+        self.fit = np.asarray(tables["FitCell"]) != 0.0
+        self.weight, self.own, self.across = (np.asarray(tables[n]) for n in ("HessWeight", "EdgeDirOwn", "EdgeDirAcross"))
+        self.q0, self.q1 = np.zeros((M.ne, 3)), np.zeros((M.ne, 3))
+        for j in range(M.eoc.shape[1]):  # the slots of c0 hold the edge's own orientation
+            r = np.nonzero(j < M.neoc[: M.nc])[0]
+            e = M.eoc[r, j]
+            ok = (e >= 0) & (e < M.ne)
+            r, e = r[ok], e[ok]
+            first = M.coe[e, 0] == r
+            self.q0[e[first]], self.q1[e[first]] = self.own[r[first], j], self.across[r[first], j]
+            # a boundary edge stored [missing, cell] has no cell 0: it is never high and its zeros stay
+        self.high = (self.q0[:, 0] != 0.0) | (self.q0[:, 2] != 0.0)
+
+    @classmethod
+    def of(cls, M, mesh, g, order, coef=0.25):
+        """from oa.monotone_adv_high_order_tables on an oa.HorzMesh `mesh` of the mesh dictionary `g`"""
+        import omega_amd as oa
+        return cls(M, oa.monotone_adv_high_order_tables(mesh, order, coef, **geometry(g)), 0.0 if order == 4 else coef)
+
+
+def geometry(g):
+    """the keyword arguments of set_horz_order that a mesh dictionary implies"""
+    return dict(sphere_radius=float(g.get("sphere_radius", 0.0)) if g.get("on_a_sphere", False) else 0.0,
+                x_period=float(g.get("x_period", 0.0)), y_period=float(g.get("y_period", 0.0)))
+
+
+def hessians(H, phi):
+    """pass 0 for one tracer: [3][NCellsSize][K], the sum from 0.0 over the slots in slot order of
+    HessWeight[c][j][t]*(phi[n_j] - phi[c]); 0.0 on a cell that is not a fit cell (no neighbour is read), NaN on the rows
+    >= NCellsAll, which the device does not write"""
+    M = H.M
+    out = np.full((3,) + phi.shape, np.nan)
+    out[:, : M.nc] = 0.0
+    with np.errstate(all="ignore"):
+        for j in range(M.eoc.shape[1]):
+            r = np.nonzero((j < M.neoc[: M.nc]) & H.fit[: M.nc])[0]
+            if not r.size:
+                continue
+            e = M.eoc[r, j]
+            n = np.where(M.coe[e, 0] == r, M.coe[e, 1], M.coe[e, 0])
+            d = phi[n] - phi[r]
+            for t in range(3):
+                out[t, r] = out[t, r] + H.weight[r, j, t][:, None] * d
+    return out
+
+
+# ---- the 3-D form: interface quantities ----
+
+def interface_mask(lo, hi, nc, K):
+    """[nc][K] True where interface K carries flux: lo < K <= hi (a land column, hi < lo: nowhere)"""
+    k = np.arange(K)[None, :]
+    return (lo[:nc, None] < k) & (k <= hi[:nc, None])
+
+
+def _up(x):
+    """x[K-1] at K (column 0: NaN, never selected)"""
+    out = np.full_like(x, np.nan)
+    out[:, 1:] = x[:, :-1]
+    return out
+
+
+def _down(x, fill=np.nan):
+    """x[K+1] at K (the last column: fill)"""
+    out = np.full_like(x, fill)
+    out[:, :-1] = x[:, 1:]
+    return out
+
+
+def interface_terms(h_old, phi, wt, lo, hi, nc):
+    """(inside, Wv, VLow, PhiT, AV) at the top interface of every level, [nc][K]"""
+    K = h_old.shape[1]
+    inside = interface_mask(lo, hi, nc, K)
+    h, p = h_old[:nc], phi[:nc]
+    with np.errstate(all="ignore"):
+        wv = np.where(inside, wt[:nc], 0.0)
+        pu, hu = _up(p), _up(h)
+        v_low = np.where(wv > 0.0, wv * p, wv * pu)
+        phi_t = pu + (hu / (hu + h)) * (p - pu)
+        v_high = wv * phi_t
+        av = v_high - v_low
+    return inside, wv, np.where(inside, v_low, 0.0), phi_t, np.where(inside, av, 0.0)
+
+
+def interface_scale(av, inside, scale_in, scale_out):
+    """ScV at the top interface of every level (NaN where the interface carries no flux)"""
+    with np.errstate(all="ignore"):
+        sc = np.where(av >= 0.0, kmin(scale_out, _up(scale_in)), kmin(scale_in, _up(scale_out)))
+    return np.where(inside, sc, np.nan)
+
+
+def vertical_flux(h_old, phi, wt, lo, hi, nc, scale_in, scale_out, flux="limited"):
+    """FV at the top interface of every level, [nc][K], 0.0 where it carries no flux.  flux: "limited" (the contract),
+    "low" VLow, "high" VLow + AV"""
+    inside, _, v_low, _, av = interface_terms(h_old, phi, wt, lo, hi, nc)
+    with np.errstate(all="ignore"):
+        if flux == "limited":
+            f = v_low + interface_scale(av, inside, scale_in[:nc], scale_out[:nc]) * av
+        else:
+            f = v_low if flux == "low" else v_low + av
+    return np.where(inside, f, 0.0)
+
+
+def thickness_divergence(wt, lo, hi, nc):
+    """(-Wv[K] + Wv[K+1], max(Wv[K], 0) + max(-Wv[K+1], 0)): the vertical part of the thickness tendency and of the
+    outflow, [nc][K]"""
+    K = wt.shape[1]
+    wv = np.where(interface_mask(lo, hi, nc, K), wt[:nc], 0.0)
+    wb = _down(wv, 0.0)
+    return -wv + wb, kmax(wv, 0.0) + kmax(-wb, 0.0)
+
+
+def interface_limits(h_old, phi, wt, lo, hi, nc, scale_in, scale_out):
+    """ScV on the interfaces that carry flux (Wv != 0), 1-D"""
+    inside, wv, _, _, av = interface_terms(h_old, phi, wt, lo, hi, nc)
+    sc = interface_scale(av, inside, scale_in[:nc], scale_out[:nc])
+    return sc[inside & (wv != 0.0)]
+
+
+# ---- the two passes ----
+
+def edge_terms(M, e, c0, c1, h_old, u, phi, upwind, high=None):
+    """(Fm, FLow, FHigh, A) of the edges e, [len(e)][K], in edge orientation; with `high`, FHigh carries the correction
+    on the high edges"""
     h0, h1, ue = h_old[c0], h_old[c1], u[e]
     if upwind:
         h_e = np.where(ue > 0, h0, np.where(ue < 0, h1, kmax(h0, h1)))
@@ -65,7 +206,18 @@ def edge_terms(M, e, c0, c1, h_old, u, phi, upwind):
     fm = M.dv[e][:, None] * (h_e * ue)
     p0, p1 = phi[c0], phi[c1]
     f_low = np.where(fm >= 0.0, fm * p0, fm * p1)
-    f_high = fm * (0.5 * (p0 + p1))
+    if high is None:
+        f_high = fm * (0.5 * (p0 + p1))
+    else:
+        H, hess = high
+        q0, q1 = H.q0[e][:, :, None], H.q1[e][:, :, None]
+        with np.errstate(all="ignore"):
+            d0 = (q0[:, 0] * hess[0][c0] + q0[:, 1] * hess[1][c0]) + q0[:, 2] * hess[2][c0]
+            d1 = (q1[:, 0] * hess[0][c1] + q1[:, 1] * hess[1][c1]) + q1[:, 2] * hess[2][c1]
+            s, t = d0 + d1, d0 - d1
+            b = H.beta * t
+            corr = np.where(H.high[e][:, None], s + np.where(fm >= 0.0, b, -b), 0.0)
+            f_high = fm * (0.5 * (p0 + p1) - corr)
     return fm, f_low, f_high, f_high - f_low
 
 
@@ -74,7 +226,7 @@ def _signed(s, x):
     return np.where((s < 0)[:, None], -x, x)
 
 
-def scale_factors(M, h_old, h_new, u, phi, dt, upwind=False):
+def scale_factors(M, h_old, h_new, u, phi, dt, upwind=False, vert=None, high=None):
     """pass 1 for one tracer: (ScaleIn, ScaleOut, PMin, PMax), [NCellsAll][K]"""
     nc, K = M.nc, h_old.shape[1]
     p_c = phi[:nc]
@@ -83,7 +235,7 @@ def scale_factors(M, h_old, h_new, u, phi, dt, upwind=False):
     with np.errstate(all="ignore"):
         for r, e, c0, c1, s in M.slots():
             n = np.where(s < 0, c1, c0)
-            _, f_low, _, a = edge_terms(M, e, c0, c1, h_old, u, phi, upwind)
+            _, f_low, _, a = edge_terms(M, e, c0, c1, h_old, u, phi, upwind, high)
             p_max[r] = kmax(p_max[r], phi[n])
             p_min[r] = kmin(p_min[r], phi[n])
             sa = _signed(s, a)
@@ -91,9 +243,22 @@ def scale_factors(M, h_old, h_new, u, phi, dt, upwind=False):
             s_in[r] = s_in[r] + kmax(sa, 0.0)
             s_out[r] = s_out[r] + kmax(-sa, 0.0)
         inv_a = M.inv_area[:, None]
-        h_td = h_old[:nc] * p_c + dt * (div_low * inv_a)
-        p_in = dt * (s_in * inv_a)
-        p_out = dt * (s_out * inv_a)
+        if vert is None:
+            h_td = h_old[:nc] * p_c + dt * (div_low * inv_a)
+            p_in = dt * (s_in * inv_a)
+            p_out = dt * (s_out * inv_a)
+        else:
+            wt, lo, hi = vert
+            top, _, v_low, _, av = interface_terms(h_old, phi, wt, lo, hi, nc)
+            bot = _down(top, False)
+            v_low_b, av_b = _down(v_low, 0.0), _down(av, 0.0)
+            p_max = np.where(top, kmax(p_max, _up(p_c)), p_max)
+            p_min = np.where(top, kmin(p_min, _up(p_c)), p_min)
+            p_max = np.where(bot, kmax(p_max, _down(p_c)), p_max)
+            p_min = np.where(bot, kmin(p_min, _down(p_c)), p_min)
+            h_td = h_old[:nc] * p_c + dt * (((div_low * inv_a) - v_low) + v_low_b)
+            p_in = dt * (((s_in * inv_a) + kmax(-av, 0.0)) + kmax(av_b, 0.0))
+            p_out = dt * (((s_out * inv_a) + kmax(av, 0.0)) + kmax(-av_b, 0.0))
         q_in = kmax(0.0, p_max * h_new[:nc] - h_td)
         q_out = kmax(0.0, h_td - p_min * h_new[:nc])
         scale_in = np.where(p_in > 0.0, kmin(1.0, q_in / p_in), 1.0)
@@ -106,32 +271,43 @@ def edge_scale(a, scale_in, scale_out, c0, c1):
     return np.where(a >= 0.0, kmin(scale_out[c0], scale_in[c1]), kmin(scale_in[c0], scale_out[c1]))
 
 
-def flux_divergence(M, h_old, u, phi, scale_in, scale_out, upwind=False, flux="limited"):
-    """pass 2 for one tracer: (sum of s*F)*InvA, [NCellsAll][K].  flux: "limited" F = FLow + Sc*A (the contract);
-    "low" F = FLow; "high" F = FHigh (the centred flux itself)"""
+def flux_divergence(M, h_old, u, phi, scale_in, scale_out, upwind=False, flux="limited", vert=None, high=None):
+    """pass 2 for one tracer, [NCellsAll][K]: (sum of s*F)*InvA, with `vert` (((sum of s*F)*InvA) - FV[K]) + FV[K+1].
+    flux: "limited" F = FLow + Sc*A (the contract); "low" F = FLow; "high" F = FHigh, unlimited"""
     nc, K = M.nc, h_old.shape[1]
     total = np.zeros((nc, K))
     with np.errstate(all="ignore"):
         for r, e, c0, c1, s in M.slots():
-            _, f_low, f_high, a = edge_terms(M, e, c0, c1, h_old, u, phi, upwind)
+            _, f_low, f_high, a = edge_terms(M, e, c0, c1, h_old, u, phi, upwind, high)
             if flux == "limited":
                 f = f_low + edge_scale(a, scale_in, scale_out, c0, c1) * a
             else:
                 f = f_low if flux == "low" else f_high
             total[r] = total[r] + _signed(s, f)
-        return total * M.inv_area[:, None]
+        if vert is None:
+            return total * M.inv_area[:, None]
+        wt, lo, hi = vert
+        fv = vertical_flux(h_old, phi, wt, lo, hi, nc, scale_in, scale_out, flux)
+        return ((total * M.inv_area[:, None]) - fv) + _down(fv, 0.0)
 
 
-def add_tracer_tend(M, tend, h_old, h_new, u, tracers, ntracers, dt, upwind, scale_in, scale_out):
+def add_tracer_tend(M, tend, h_old, h_new, u, tracers, ntracers, dt, upwind, scale_in, scale_out, vert=None, high=None):
     """MonotoneAdv::addTracerTend in place on tend, scale_in, scale_out ([>= ntracers][NCellsSize][K]): only the entries
-    [L < ntracers][c < NCellsAll] are written"""
+    [L < ntracers][c < NCellsAll] are written.  vert: a VertAdv is attached; high = (H, hess): order 3 or 4, with pass 0
+    written to hess ([>= ntracers][3][NCellsSize][K]) in the same entries"""
     nc = M.nc
     for L in range(ntracers):
-        si, so, _, _ = scale_factors(M, h_old, h_new, u, tracers[L], dt, upwind)
+        high_L = None
+        if high is not None:
+            H, hess = high
+            hs = hessians(H, tracers[L])
+            hess[L][:, :nc] = hs[:, :nc]
+            high_L = (H, hs)
+        si, so, _, _ = scale_factors(M, h_old, h_new, u, tracers[L], dt, upwind, vert, high_L)
         scale_in[L, :nc], scale_out[L, :nc] = si, so
         # (pass 2 reads the scale factors of local cells only)
         with np.errstate(all="ignore"):
-            tend[L, :nc] = tend[L, :nc] + flux_divergence(M, h_old, u, tracers[L], si, so, upwind)
+            tend[L, :nc] = tend[L, :nc] + flux_divergence(M, h_old, u, tracers[L], si, so, upwind, vert=vert, high=high_L)
     return tend
 
 
@@ -149,9 +325,9 @@ def mass_divergence(M, h_old, u, upwind=False):
     return total * M.inv_area[:, None], out * M.inv_area[:, None]
 
 
-def edge_limits(M, h_old, u, phi, scale_in, scale_out, upwind=False):
+def edge_limits(M, h_old, u, phi, scale_in, scale_out, upwind=False, high=None):
     """Sc on every masked-in edge-level, [number of such edges][K] (what the fixtures count)"""
     e = np.nonzero(M.open_edge)[0]
     c0, c1 = M.coe[e, 0], M.coe[e, 1]
-    a = edge_terms(M, e, c0, c1, h_old, u, phi, upwind)[3]
+    a = edge_terms(M, e, c0, c1, h_old, u, phi, upwind, high)[3]
     return edge_scale(a, scale_in, scale_out, c0, c1)

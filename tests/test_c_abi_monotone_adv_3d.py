@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import omega_amd as oa
-from tests.monotone_adv3d_fixtures import Mono3Rig
+from tests.monotone_adv_fixtures import Mono3Rig
 from tests.split_explicit_fixtures import RHO0, StepRig
 
 SYMBOLS = ("omg_monoadv_attach_vert_adv", "omg_vertadv_set_tracer_term")

@@ -11,8 +11,8 @@ import pytest
 
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
-from tests import monotone_adv_ho_reference as HO
-from tests.monotone_adv_ho_fixtures import HoRig
+from tests import monotone_adv_reference as MR
+from tests.monotone_adv_fixtures import HoRig
 
 SYMBOLS = ("omg_monoadv_set_horz_order", "omg_monoadv_high_order_tables", "omg_monoadv_launch_count")
 ARRAYS = (b"Hess", b"HessWeight", b"EdgeDirOwn", b"EdgeDirAcross", b"FitCell")
@@ -82,7 +82,7 @@ def test_calls_on_a_device():
     R = HoRig("fib700_coast_ragged", K, device=True).set_order(3, 0.5)
     I = R.inputs(seed=4, ntracers=3, check=False)
     m, nc, n, me = R.mesh, R.nc_size, R.nc, R.mesh.MaxEdges
-    geo = HO.geometry(R.g)
+    geo = MR.geometry(R.g)
     geo_args = (_d(geo["sphere_radius"]), _d(geo["x_period"]), _d(geo["y_period"]))
     h = C.c_void_p()
     assert L.omg_monoadv_create(m.h, K, maxt, 0, C.byref(h)) == 0 and h

@@ -1,5 +1,5 @@
 """Properties of the 3-D form of the MonotoneAdv contract (omega_amd/csrc/MonotoneAdv.h), checked on its NumPy
-restatement (tests/monotone_adv3d_reference.py), which the device reproduces bit for bit
+restatement (tests/monotone_adv_reference.py), which the device reproduces bit for bit
 (tests/test_monotone_adv_3d_gpu.py): with a vertical transport one forward step stays inside the range of each cell's
 3-D neighbourhood, where the parent's path (the fixture asserts it) does not; it conserves the tracer content, keeps a
 constant, is the 2-D form where nothing moves vertically, and agrees with VertAdv on the interface value."""
@@ -8,11 +8,9 @@ import math
 import numpy as np
 import pytest
 
-from tests import monotone_adv3d_reference as M3
 from tests import monotone_adv_reference as MR
 from tests import vert_adv_reference as VR
-from tests.monotone_adv3d_fixtures import Mono3Rig
-from tests.monotone_adv_fixtures import CONST, CONST_VALUE, RANDOM, STEP
+from tests.monotone_adv_fixtures import CONST, CONST_VALUE, RANDOM, STEP, Mono3Rig
 
 MESHES = ("hex24x20", "ico3", "fib700_coast_ragged")
 K = 6
@@ -47,8 +45,8 @@ def margin(R, I, L):
 
 
 def forward_step(R, I, L):
-    si, so, p_min, p_max = M3.scale_factors(R.M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, I.wt, R.lo, R.hi, I.upwind)
-    tend = M3.flux_divergence(R.M, I.h_old, I.u, I.tracers[L], si, so, I.wt, R.lo, R.hi, I.upwind)
+    si, so, p_min, p_max = MR.scale_factors(R.M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, I.upwind, R.vert(I))
+    tend = MR.flux_divergence(R.M, I.h_old, I.u, I.tracers[L], si, so, I.upwind, vert=R.vert(I))
     return R.forward(I, L, tend), p_min, p_max
 
 
@@ -94,11 +92,11 @@ def test_tracer_content_is_conserved_on_the_periodic_mesh():
     assert M.open_edge.all()
     e = np.arange(M.ne)
     for L in (STEP, RANDOM):
-        si, so, _, _ = M3.scale_factors(M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, I.wt, R.lo, R.hi)
-        tend = M3.flux_divergence(M, I.h_old, I.u, I.tracers[L], si, so, I.wt, R.lo, R.hi)
+        si, so, _, _ = MR.scale_factors(M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, vert=R.vert(I))
+        tend = MR.flux_divergence(M, I.h_old, I.u, I.tracers[L], si, so, vert=R.vert(I))
         _, f_low, _, a = MR.edge_terms(M, e, M.coe[e, 0], M.coe[e, 1], I.h_old, I.u, I.tracers[L], False)
         f = f_low + MR.edge_scale(a, si, so, M.coe[e, 0], M.coe[e, 1]) * a
-        fv = M3.vertical_flux(I.h_old, I.tracers[L], I.wt, R.lo, R.hi, nc, si, so)
+        fv = MR.vertical_flux(I.h_old, I.tracers[L], I.wt, R.lo, R.hi, nc, si, so)
         assert np.abs(fv).max() > 0.0
         drift = abs(math.fsum((R.area[:nc, None] * tend).ravel()))
         bound = (n + 5) * EPS * 2.0 * (np.abs(f).sum() + (R.area[:nc, None] * np.abs(fv)).sum())
@@ -110,7 +108,7 @@ def test_tracer_content_is_conserved_on_the_periodic_mesh():
 @pytest.mark.parametrize("name", MESHES)
 def test_constant_tracer_has_no_antidiffusive_vertical_flux(name):
     R, I = rig(name)
-    inside, wv, _, phi_t, av = M3.interface_terms(I.h_old, I.tracers[CONST], I.wt, R.lo, R.hi, R.nc)
+    inside, wv, _, phi_t, av = MR.interface_terms(I.h_old, I.tracers[CONST], I.wt, R.lo, R.hi, R.nc)
     assert (wv[inside] != 0.0).all() and not av.any()  # AV = 0 exactly: PhiT == phi bit for bit
     assert (phi_t[inside] == CONST_VALUE).all()
     assert R.limited_interfaces(I, CONST) == (0.0, 1.0)
@@ -136,7 +134,7 @@ def test_zero_transport_is_the_2d_form(name):
     got = R.reference(I, 3)
     assert all(np.isfinite(a[:, :nc]).all() for a in got)
     for L in (STEP, RANDOM, CONST):
-        _, _, p_min, p_max = M3.scale_factors(R.M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, I.wt, R.lo, R.hi)
+        _, _, p_min, p_max = MR.scale_factors(R.M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, vert=R.vert(I))
         _, _, q_min, q_max = MR.scale_factors(R.M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt)
         same = (p_min == q_min) & (p_max == q_max)
         assert same.any()
@@ -160,7 +158,7 @@ def test_interface_value_is_vert_advs(name):
     values no larger than max|phi|, so they differ by at most 10 eps max|phi|"""
     R, I = rig(name)
     nc = R.nc
-    inside, _, _, phi_t, _ = M3.interface_terms(I.h_old, I.tracers[RANDOM], I.wt, R.lo, R.hi, nc)
+    inside, _, _, phi_t, _ = MR.interface_terms(I.h_old, I.tracers[RANDOM], I.wt, R.lo, R.hi, nc)
     want = VR.interface_value(I.h_old, I.tracers[RANDOM], I.wt, 2, nc)
     diff = np.abs(phi_t - want)[inside].max()
     print(name, "PhiT differs from VertAdv's by", diff)
@@ -180,13 +178,13 @@ def test_no_vertical_term_without_an_interface():
     cells = np.arange(0, R.nc, 5)
     lo[cells], hi[cells] = 2, 2
     J = R.inputs(seed=11, check=False)
-    keep = M3.interface_mask(lo, hi, R.nc, K)
+    keep = MR.interface_mask(lo, hi, R.nc, K)
     J.wt[: R.nc][~keep] = np.nan
-    vdiv, _ = M3.thickness_divergence(J.wt, lo, hi, R.nc)
+    vdiv, _ = MR.thickness_divergence(J.wt, lo, hi, R.nc)
     assert not vdiv[cells].any()
     for L in (STEP, RANDOM):
-        fv = M3.vertical_flux(J.h_old, J.tracers[L], J.wt, lo, hi, R.nc, np.ones((R.nc, K)), np.ones((R.nc, K)))
+        fv = MR.vertical_flux(J.h_old, J.tracers[L], J.wt, lo, hi, R.nc, np.ones((R.nc, K)), np.ones((R.nc, K)))
         assert not fv[cells].any() and fv.any()
-        _, _, p_min, p_max = M3.scale_factors(R.M, J.h_old, J.h_new, J.u, J.tracers[L], J.dt, J.wt, lo, hi)
+        _, _, p_min, p_max = MR.scale_factors(R.M, J.h_old, J.h_new, J.u, J.tracers[L], J.dt, vert=(J.wt, lo, hi))
         _, _, q_min, q_max = MR.scale_factors(R.M, J.h_old, J.h_new, J.u, J.tracers[L], J.dt)
         assert np.array_equal(p_min[cells], q_min[cells]) and np.array_equal(p_max[cells], q_max[cells])

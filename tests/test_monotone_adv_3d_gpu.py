@@ -2,15 +2,14 @@
 kernels/MonotoneAdvKernels.hip, Vert = true), VertAdv::TracerTermEnable and the attachment to the Split-Explicit
 stepper.
 
-The yardstick of the call is the restatement (tests/monotone_adv3d_reference.py), compared as
+The yardstick of the call is the restatement (tests/monotone_adv_reference.py), compared as
 tests/test_monotone_adv_gpu.py compares the 2-D form: outputs seeded with NaN and read back raw.  VerticalTransport is
-NaN wherever no flux passes (tests/monotone_adv3d_fixtures.py) and in its row padding, like the padding of every input."""
+NaN wherever no flux passes (tests/monotone_adv_fixtures.py) and in its row padding, like the padding of every input."""
 import numpy as np
 import pytest
 
 import omega_amd as oa
-from tests.monotone_adv3d_fixtures import Mono3Rig
-from tests.monotone_adv_fixtures import RANDOM, Inputs
+from tests.monotone_adv_fixtures import RANDOM, Inputs, Mono3Rig
 from tests.split_explicit_fixtures import RHO0, StepRig
 from tests.test_monotone_adv_3d import margin_value
 from tests.test_monotone_adv_gpu import MAXT, NO_ADV, Dev, assert_bits, mono_step_by_hand, read_raw

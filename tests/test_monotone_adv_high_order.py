@@ -1,7 +1,7 @@
 """The high-order horizontal flux of MonotoneAdv (omega_amd/csrc/MonotoneAdv.h, "The high-order horizontal flux") on
 the CPU: the tables the library builds on the host (omg_monoadv_high_order_tables: what MonotoneAdv::setHorzOrder
 uploads; a MonotoneAdv itself needs a device), and the properties of the contract on its NumPy restatement
-(tests/monotone_adv_ho_reference.py), which the device reproduces bit for bit
+(tests/monotone_adv_reference.py), which the device reproduces bit for bit
 (tests/test_monotone_adv_high_order_gpu.py)."""
 import math
 
@@ -10,11 +10,9 @@ import pytest
 
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
-from tests import monotone_adv_ho_reference as HO
 from tests import monotone_adv_reference as MR
 from tests.meshes import named_mesh
-from tests.monotone_adv_fixtures import CONST, CONST_VALUE, RANDOM, STEP, Inputs, MonoRig
-from tests.monotone_adv_ho_fixtures import ORDERS, HoRig
+from tests.monotone_adv_fixtures import CONST, CONST_VALUE, ORDERS, RANDOM, STEP, HoRig, Inputs, MonoRig
 
 MESHES = ("hex24x20", "ico3", "fib700_coast_ragged")
 K = 3
@@ -44,7 +42,7 @@ class NumpyFit:
 
     def __init__(self, R):
         M, m, nc, ne = R.M, R.mesh, R.nc, R.ne
-        geo = HO.geometry(R.g)
+        geo = MR.geometry(R.g)
         X = np.stack([m.get_array(a + "Cell") for a in "XYZ"], axis=1)
         rad = geo["sphere_radius"]
         self.cell, self.nbr, self.d, self.L, self.P, self.sv = [], {}, {}, {}, {}, {}
@@ -233,7 +231,7 @@ def divergence_error(n, order, coef):
     else:
         R.set_order(order, coef)
         assert R.H.high.all()
-        got = HO.flux_divergence(R.H, h, u, phi, HO.hessians(R.H, phi), None, None, flux="high")
+        got = MR.flux_divergence(M, h, u, phi, None, None, flux="high", high=(R.H, MR.hessians(R.H, phi)))
     return float(np.abs(got[:, 0] + (ux * px + uy * py)).max())
 
 
@@ -255,8 +253,8 @@ def test_order_of_accuracy():
 def forward_step(R, I, L, flux="limited", hess=None):
     nc = R.nc
     hs = R.hess(I, L) if hess is None else hess
-    si, so, p_min, p_max = HO.scale_factors(R.H, I.h_old, I.h_new, I.u, I.tracers[L], hs, I.dt, I.upwind)
-    tend = HO.flux_divergence(R.H, I.h_old, I.u, I.tracers[L], hs, si, so, I.upwind, flux)
+    si, so, p_min, p_max = MR.scale_factors(R.M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, I.upwind, high=(R.H, hs))
+    tend = MR.flux_divergence(R.M, I.h_old, I.u, I.tracers[L], si, so, I.upwind, flux, high=(R.H, hs))
     return (I.h_old[:nc] * I.tracers[L, :nc] + I.dt * tend) / I.h_new[:nc], p_min, p_max
 
 
@@ -312,7 +310,7 @@ def test_unlimited_high_order_flux_leaves_the_range(name, order, coef):
     assert over > 1.0e-2
     # and it is not the centred flux: the correction is at work
     centred = MR.flux_divergence(R.M, I.h_old, I.u, I.tracers[STEP], None, None, flux="high")
-    high = HO.flux_divergence(R.H, I.h_old, I.u, I.tracers[STEP], R.hess(I, STEP), None, None, flux="high")
+    high = MR.flux_divergence(R.M, I.h_old, I.u, I.tracers[STEP], None, None, flux="high", high=(R.H, R.hess(I, STEP)))
     assert not np.array_equal(centred, high)
 
 
@@ -325,9 +323,9 @@ def test_tracer_content_is_conserved_on_the_periodic_mesh(order, coef):
     e = np.arange(M.ne)
     for L in (STEP, RANDOM):
         hs = R.hess(I, L)
-        si, so, _, _ = HO.scale_factors(R.H, I.h_old, I.h_new, I.u, I.tracers[L], hs, I.dt)
-        tend = HO.flux_divergence(R.H, I.h_old, I.u, I.tracers[L], hs, si, so)
-        _, f_low, _, a = HO.edge_terms(R.H, e, M.coe[e, 0], M.coe[e, 1], I.h_old, I.u, I.tracers[L], hs, False)
+        si, so, _, _ = MR.scale_factors(M, I.h_old, I.h_new, I.u, I.tracers[L], I.dt, high=(R.H, hs))
+        tend = MR.flux_divergence(M, I.h_old, I.u, I.tracers[L], si, so, high=(R.H, hs))
+        _, f_low, _, a = MR.edge_terms(M, e, M.coe[e, 0], M.coe[e, 1], I.h_old, I.u, I.tracers[L], False, (R.H, hs))
         f = f_low + MR.edge_scale(a, si, so, M.coe[e, 0], M.coe[e, 1]) * a
         for k in range(K):
             drift = abs(math.fsum(R.area[:nc] * tend[:, k]))
@@ -343,7 +341,7 @@ def test_constant_tracer_stays_constant(name, order, coef):
     hs = R.hess(I, CONST)
     assert not hs[:, : R.nc].any()  # Hess == 0.0 exactly
     e = np.nonzero(R.M.open_edge)[0]
-    a = HO.edge_terms(R.H, e, R.M.coe[e, 0], R.M.coe[e, 1], I.h_old, I.u, I.tracers[CONST], hs, False)[3]
+    a = MR.edge_terms(R.M, e, R.M.coe[e, 0], R.M.coe[e, 1], I.h_old, I.u, I.tracers[CONST], False, (R.H, hs))[3]
     assert not a.any()  # A = 0 exactly
     new, p_min, p_max = forward_step(R, I, CONST)
     assert (p_min == CONST_VALUE).all() and (p_max == CONST_VALUE).all()
@@ -363,7 +361,7 @@ def test_an_edge_that_is_not_high_has_the_centred_flux(order, coef):
     hs = R.hess(I, RANDOM)
     for e, same in ((low, True), (high, False)):
         c0, c1 = M.coe[e, 0], M.coe[e, 1]
-        got = HO.edge_terms(H, e, c0, c1, I.h_old, I.u, I.tracers[RANDOM], hs, False)[2]
+        got = MR.edge_terms(M, e, c0, c1, I.h_old, I.u, I.tracers[RANDOM], False, (H, hs))[2]
         centred = MR.edge_terms(M, e, c0, c1, I.h_old, I.u, I.tracers[RANDOM], False)[2]
         assert np.array_equal(got, centred) == same
     # NaN in the Hess rows of the cells that are not fit cells changes nothing

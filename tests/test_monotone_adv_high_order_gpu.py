@@ -1,7 +1,7 @@
 """The high-order horizontal flux of MonotoneAdv on the GPU (MonotoneAdv::setHorzOrder; omega_amd/csrc/MonotoneAdv.h,
 kernels/MonotoneAdvKernels.hip: MonoHessBody and the High = true forms of the two bodies).
 
-The yardstick of the call is the restatement (tests/monotone_adv_ho_reference.py) on the tables read back from the
+The yardstick of the call is the restatement (tests/monotone_adv_reference.py) on the tables read back from the
 object, compared as tests/test_monotone_adv_gpu.py compares the centred form: Hess, ScaleIn, ScaleOut and the tendency
 are seeded with NaN and read back raw; every entry must hold the restatement's bits or its seed."""
 import numpy as np
@@ -9,10 +9,9 @@ import pytest
 
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
-from tests import monotone_adv_ho_reference as HO
-from tests.monotone_adv_fixtures import RANDOM, Inputs, MonoRig
+from tests import monotone_adv_reference as MR
+from tests.monotone_adv_fixtures import ORDERS, RANDOM, Ho3Rig, HoRig, Inputs, MonoRig
 from tests.monotone_adv_reference import MonoMesh
-from tests.monotone_adv_ho_fixtures import ORDERS, Ho3Rig, HoRig
 from tests.split_explicit_fixtures import StepRig
 from tests.test_monotone_adv_3d_gpu import Dev3
 from tests.test_monotone_adv_3d_gpu import LEVELS as LEVELS_3D
@@ -36,12 +35,12 @@ class _Ho:
 
     def setup_ho(self, order, coef):
         R = self.R
-        self.mono.set_horz_order(order, coef, **HO.geometry(R.g))
+        self.mono.set_horz_order(order, coef, **MR.geometry(R.g))
         tabs = {n: self.mono.get(n) for n in TABLES}
-        host = oa.monotone_adv_high_order_tables(R.mesh, order, coef, **HO.geometry(R.g))
+        host = oa.monotone_adv_high_order_tables(R.mesh, order, coef, **MR.geometry(R.g))
         for n in TABLES:  # what was uploaded is what the host builder gives
             assert_bits(tabs[n], host[n], n)
-        R.H = HO.HoTables(R.M, tabs, 0.0 if order == 4 else coef)
+        R.H = MR.HoTables(R.M, tabs, 0.0 if order == 4 else coef)
         self.hshape = (self.maxt, 3, R.nc_size, self.pitch)
         return self
 
@@ -121,7 +120,7 @@ def test_bit_exact_on_nan_seeded_arrays(name, K, nt, order, coef, upwind):
 @pytest.mark.parametrize("name", ("hex24x20", "fib700_coast_ragged"))
 def test_the_3d_form_is_bit_exact(name, K, nt, order, coef):
     """Vert = true, High = true: the 3-D restatement fed the high-order FHigh, on the fixtures of
-    tests/monotone_adv3d_fixtures.py"""
+    tests/monotone_adv_fixtures.py"""
     case(name, K, False, order, coef, vert=True).check(nt)
 
 
@@ -143,7 +142,7 @@ def test_order_2_is_unchanged():
     two_launches_and_the_same_bits("never configured")
     D.mono.set_horz_order(2)
     two_launches_and_the_same_bits("order 2")
-    D.mono.set_horz_order(4, **HO.geometry(R.g))
+    D.mono.set_horz_order(4, **MR.geometry(R.g))
     before = D.mono.launch_count()
     D.seed(4)
     D.run(4)
@@ -152,7 +151,7 @@ def test_order_2_is_unchanged():
     assert not np.array_equal(high[0][:4, : R.nc, : R.K], never[0][:4, : R.nc, : R.K])
     D.mono.set_horz_order(2)
     two_launches_and_the_same_bits("order 4 and back to 2")
-    D.mono.set_horz_order(3, 0.25, **HO.geometry(R.g))  # Hess and the tables are reused
+    D.mono.set_horz_order(3, 0.25, **MR.geometry(R.g))  # Hess and the tables are reused
     D.mono.set_horz_order(2, float("nan"))  # (the coefficient is looked at at order 3 only)
     two_launches_and_the_same_bits("order 3 and back to 2")
 
@@ -166,7 +165,7 @@ def test_calls_create_no_device_resource():
         D.run(nt)
     D.mono.set_horz_order(2)
     D.run(2)
-    D.mono.set_horz_order(4, **HO.geometry(D.R.g))  # the second time: nothing new
+    D.mono.set_horz_order(4, **MR.geometry(D.R.g))  # the second time: nothing new
     D.run(2)
     oa.device_synchronize()
     assert oa.device_resource_count() == before
@@ -232,7 +231,7 @@ def test_two_part_decomposition_matches_on_owned_cells():
 
 
 def step_geometry():
-    return HO.geometry(planar_hex(8, 8, 30.0e3))  # StepRig's mesh
+    return MR.geometry(planar_hex(8, 8, 30.0e3))  # StepRig's mesh
 
 
 def test_attached_step_at_order_4_equals_the_calls_by_hand():
@@ -290,7 +289,7 @@ def test_eight_steps_keep_a_step_tracer_in_its_range():
     courant = dt * u_max * 3.0 * dv.max() / area.min()
     print("Courant estimate", courant, "min h", h_min)
     assert np.isfinite(tr).all() and h_min > 0.0 and courant < 0.5 and mono.launch_count() == 3 * steps
-    H = HO.HoTables(MonoMesh.of(m), {n: mono.get(n) for n in TABLES}, 0.0)
+    H = MR.HoTables(MonoMesh.of(m), {n: mono.get(n) for n in TABLES}, 0.0)
     n = m.get_array("EdgesOnCell").shape[1]
     for L in range(2):
         lo, hi = x.tr[L, : m.NCellsAll].min(), x.tr[L, : m.NCellsAll].max()
@@ -322,5 +321,5 @@ def test_refusals():
     with pytest.raises(E, match="after setHorzOrder"):  # a refused call configured nothing
         mono.get("Hess")
     assert mono.launch_count() == 0
-    mono.set_horz_order(3, 1.0, **HO.geometry(R.g))
+    mono.set_horz_order(3, 1.0, **MR.geometry(R.g))
     assert mono.get("Hess").shape == (1, 3, R.nc_size, 2) and mono.get("FitCell")[: R.nc].all()

@@ -1,9 +1,11 @@
 #!/bin/bash
-# MonotoneAdv at QU30 size (tools/probes/monotone_adv_diag.py): device-event timing of the transport call with the built-in
-# centred advection, of the same call without it followed by MonotoneAdv::addTracerTend, of addTracerTend alone, and of one
-# Split-Explicit step without and with the attachment, each twice in the same process (no profiler), bounded by timeout.
-# A run that fails or times out ends the script with its log tail and a non-zero exit: no further GPU step after it.
-#   usage: [OUT_DIR=dir] bash tools/profile_monotone_adv.sh <tag> [monotone_adv_diag.py args]
+# MonotoneAdv at QU30 size (tools/probes/monotone_adv_diag.py --form 2d|3d|ho, which lists the cases of each form):
+# device-event timing of addTracerTend against the path the form replaces and of one Split-Explicit step each way, each
+# twice in the same process (no profiler).  For the forms 3d and ho then, as a step of its own, rocprofv3 --kernel-trace
+# --stats of addTracerTend alone (--only-kernels), which splits each call into its launches.  Every step is bounded by
+# timeout.  A run that fails or times out ends the script with its log tail and a non-zero exit: no further GPU step
+# after it.
+#   usage: [OUT_DIR=dir] bash tools/profile_monotone_adv.sh <tag> [--form 2d|3d|ho] [monotone_adv_diag.py args]
 #   -> $OUT_DIR/<tag>_*   (OUT_DIR defaults to build/profile_out, which git ignores)
 set -o pipefail
 TAG=${1:?tag}; shift
@@ -11,13 +13,50 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=${OUT_DIR:-build/profile_out}
 mkdir -p $OUT
-timeout -k 10 500 python3 tools/probes/monotone_adv_diag.py "$@" --out $OUT/${TAG}_monotone_adv_diag_qu30.json > $OUT/${TAG}_monotone_adv_diag.log 2>&1
-rc=$?
-echo "[monotone_adv] diag rc=$rc"
-if [ $rc -ne 0 ]; then
-   echo "[monotone_adv] diag FAILED (rc $rc; 124 = timeout): last lines of its log" >&2
-   tail -20 $OUT/${TAG}_monotone_adv_diag.log >&2
-   exit $rc
-fi
-cat $OUT/${TAG}_monotone_adv_diag_qu30.json
-exit 0
+FORM=2d
+prev=
+for arg in "$@"; do
+   [ "$prev" = --form ] && FORM=$arg
+   case $arg in --form=*) FORM=${arg#--form=};; esac
+   prev=$arg
+done
+case $FORM in
+   2d) NAME=monotone_adv;;
+   3d) NAME=monotone_adv3d;;
+   ho) NAME=monotone_adv_ho;;
+   *) echo "unknown form '$FORM'" >&2; exit 2;;
+esac
+
+step() {  # <label> <seconds> <log> <command...>: the command under its own time limit; the script ends if it fails
+   local label=$1 limit=$2 log=$3; shift 3
+   timeout -k 10 $limit "$@" > $log 2>&1
+   local rc=$?
+   echo "[$NAME] $label rc=$rc"
+   if [ $rc -ne 0 ]; then
+      echo "[$NAME] $label FAILED (rc $rc; 124 = timeout): last lines of its log" >&2
+      tail -20 $log >&2
+      exit $rc
+   fi
+}
+
+JSON=$OUT/${TAG}_${NAME}_diag_qu30.json
+step diag 540 $OUT/${TAG}_${NAME}_diag.log python3 tools/probes/monotone_adv_diag.py "$@" --out $JSON
+cat $JSON
+[ $FORM = 2d ] && exit 0
+step trace 300 $OUT/${TAG}_${NAME}_trace.log rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_${NAME}_trace -o t -- \
+   python3 tools/probes/monotone_adv_diag.py "$@" --only-kernels --iters 20
+# the tile kernels' mean durations go into the record as "kernel_trace_ms"
+python3 - $OUT/${TAG}_${NAME}_trace $JSON <<'PY'
+import csv, glob, json, re, sys
+rows = {}
+for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):
+    for r in csv.DictReader(open(f)):
+        m = re.search(r"(Mono\w+Body\w*(?:<[\w, ]+>)?)", r["Name"])
+        if m:
+            rows[m.group(1)] = {"calls": int(r["Calls"]), "mean_ms": float(r["AverageNs"]) / 1.0e6}
+rec = json.load(open(sys.argv[2]))
+rec["kernel_trace_ms"] = rows
+open(sys.argv[2], "w").write(json.dumps(rec) + "\n")
+print(json.dumps(rows))
+PY
+exit $?
