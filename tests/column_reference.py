@@ -11,6 +11,7 @@ write into the arrays they are given and leave every entry outside the active ra
 import numpy as np
 
 GRAVITY = 9.80616  # VertCoord's own g (not the 9.80665 of the tendencies)
+RHO0 = 1026.0  # the reference density every test hands to its VertCoord (and to the restatements)
 
 
 def local_layer_ranges(cell_id, min_level_global, max_level_global, n_all, n_size, nvertlayers):

@@ -18,11 +18,12 @@ from omega_amd.meshgen import planar_hex
 from tests import column_reference as CR
 from tests import model_step_reference as HM
 from tests import monotone_adv_reference as MR
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
 from tests.problem import Problem
+from tests.rank_rig import raw
 from tests.vert_fixtures import mix_inputs
 
-RHO0 = HM.RHO0
 NT, NSUB, DT = 2, 3, 20.0
 PAD = -3.25
 CD, RA = 2.5e-3, 1.0e-5
@@ -102,12 +103,6 @@ def column_seed(n_size, K):
     return {"PressureInterface": pint, "PressureMid": pint[:, :K] + 500.0, "ZInterface": zint, "ZMid": zint[:, :K] - 5.0,
             "GeopotentialMid": 9.8 * (zint[:, :K] - 5.0), "SpecVol": 9.7e-4 + 1.0e-8 * k[:, :K] + 0.0 * r,
             "SpecVolDisplaced": 9.7e-4 + 2.0e-8 * k[:, :K] + 0.0 * r, "LayerThicknessTarget": 5.0 + k[:, :K] + 0.0 * r}
-
-
-def _raw(ptr, shape):
-    buf = np.empty(shape)
-    oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(ptr), oa.C.c_size_t(buf.nbytes))
-    return buf
 
 
 class ModelRig:
@@ -230,8 +225,8 @@ class ModelRig:
     def raw_state(self, level):
         """(h, u, tracers) of a time level as the device holds them, row padding included"""
         p, P = self.p, oa.level_pitch(self.K)
-        return (_raw(p.state.device_ptr(0, level), (self.nc_size, P)), _raw(p.state.device_ptr(1, level), (self.ne_size, P)),
-                _raw(p.tracers.device_ptr(level), (NT, self.nc_size, P)))
+        return (raw(p.state.device_ptr(0, level), (self.nc_size, P)), raw(p.state.device_ptr(1, level), (self.ne_size, P)),
+                raw(p.tracers.device_ptr(level), (NT, self.nc_size, P)))
 
     def device_array(self, name):
         """a named array of the product after a step, as the HostModel attribute of that name is laid out"""

@@ -26,8 +26,8 @@ from tests import vert_adv_reference as VR
 from tests import vert_mix_forcing_reference as FR
 from tests import vert_mix_reference as XR
 from tests.barotropic_fixtures import GRAVITY, btr_mesh
+from tests.column_reference import RHO0
 
-RHO0 = 1026.0
 COLUMN_FIELDS = ("PressureInterface", "PressureMid", "ZInterface", "ZMid", "GeopotentialMid", "SpecVol", "SpecVolDisplaced")
 BTR_FIELDS = ("SSH", "BtrVelocity", "BtrForcing", "BtrFluxMean", "BtrTendMean", "BtrThickEdge", "BclVelocity")
 DEVIATIONS = (

@@ -5,77 +5,28 @@ import numpy as np
 
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
-from tests import barotropic_reference as BR
-from tests import column_reference as CR
-from tests.barotropic_fixtures import btr_mesh
+from tests.barotropic_fixtures import BtrRig
+from tests.column_reference import RHO0
 from tests.problem import Problem
-from tests.vert_fixtures import mix_inputs
-
-RHO0 = 1026.0
-EDGE_1D = ("BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean", "BtrTendMean")
 
 
-class CallRig:
-    """One rank's VertCoord and BarotropicMode on random inputs in local order, layer ranges with land and KMin > 0
-    (tests.vert_fixtures.mix_inputs); after tests/test_barotropic_gpu.py's Rig"""
+class CallRig(BtrRig):
+    """tests.barotropic_fixtures.BtrRig with the fields of the three new calls (its own draws) and BtrTendMean among
+    the per-edge arrays"""
+
+    EDGE_1D = BtrRig.EDGE_1D + ("BtrTendMean",)
 
     def __init__(self, g, K, seed=7):
-        self.K = K
-        self.decomp = oa.Decomp(oa.GlobalMesh(g), 1, 0, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K)
-        self.n_all, self.n_size, self.e_all, self.e_size = m.NCellsAll, m.NCellsSize, m.NEdgesAll, m.NEdgesSize
-        cid, eid = self.decomp.get_array("CellID"), self.decomp.get_array("EdgeID")
-        G = mix_inputs(g, K, seed, False, 2)
-        rng = np.random.default_rng(seed + 50)
-        nc, ne = int(g["nCells"]), int(g["nEdges"])
-        crow, erow = cid[: self.n_all] - 1, eid[: self.e_all] - 1
-
-        def loc(x, rows, n_size):
-            out = np.full((n_size,) + x.shape[1:], np.nan)  # NaN on the sentinel row
-            out[: len(rows)] = x[rows]
-            return out
-
-        self.h, self.u = loc(G["h"], crow, self.n_size), loc(G["un"], erow, self.e_size)
-        self.tend = loc(rng.uniform(-1.0e-5, 1.0e-5, (ne, K)), erow, self.e_size)
-        self.u_old = loc(rng.uniform(-0.1, 0.1, (ne, K)), erow, self.e_size)
-        self.bot, self.ssh0 = loc(rng.uniform(100.0, 6000.0, nc), crow, self.n_size), loc(rng.uniform(-0.5, 0.5, nc), crow, self.n_size)
-        self.vel0, self.flux0 = loc(rng.uniform(-0.1, 0.1, ne), erow, self.e_size), loc(rng.uniform(-50.0, 50.0, ne), erow, self.e_size)
-        self.vc = oa.VertCoord(m, K, RHO0, "Uniform", G["min_level"], G["max_level"], decomp=self.decomp)
-        self.vc.set("BottomDepth", self.bot)
-        self.lo, self.hi = CR.local_layer_ranges(cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
-        self.lo_e, self.hi_e = self.vc.get("MinLayerEdgeBot"), self.vc.get("MaxLayerEdgeTop")
-        self.coe = m.get_array("CellsOnEdge")
-        self.active = np.zeros((self.n_size, K), bool)
-        self.active[: self.n_all] = BR.range_mask(self.lo, self.hi, self.n_all, K)
-        self.e_active = np.zeros((self.e_size, K), bool)
-        self.e_active[: self.e_all] = BR.range_mask(self.lo_e, self.hi_e, self.e_all, K)
+        super().__init__(g, K, seed=seed)
         self.e_outside = np.zeros((self.e_size, K), bool)
         self.e_outside[: self.e_all] = ~self.e_active[: self.e_all]
-        self.M = btr_mesh(m, self.bot)
-        self.bm = oa.BarotropicMode(m, self.vc)
 
-    def padded(self, a):
-        pad = np.full(a.shape[:-1] + (oa.level_pitch(self.K),), np.nan)
-        pad[..., : self.K] = a
-        return pad
-
-    def dev(self, a):
-        return oa.DeviceBuffer(self.padded(a))
-
-    def poison(self):
-        for name in EDGE_1D:
-            self.bm.set(name, np.full(self.e_size, np.nan))
-        self.bm.set("SSH", np.full(self.n_size, np.nan))
-        oa.copy_to_device(self.bm.device_ptr("BclVelocity"), np.full((self.e_size, oa.level_pitch(self.K)), np.nan))
-
-    def bcl_padded(self):
-        buf = np.empty((self.e_size, oa.level_pitch(self.K)))
-        oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(self.bm.device_ptr("BclVelocity")),
-                                  oa.C.c_size_t(buf.nbytes))
-        return buf
-
-    def state(self):
-        return {n: self.bm.get(n) for n in EDGE_1D + ("SSH",)} | {"BclVelocity": self.bcl_padded()}
+    def draw(self, rng, nc, ne):
+        K = self.K
+        self.tend = self.edges(rng.uniform(-1.0e-5, 1.0e-5, (ne, K)), np.nan)
+        self.u_old = self.edges(rng.uniform(-0.1, 0.1, (ne, K)), np.nan)
+        self.bot, self.ssh0 = self.cells(rng.uniform(100.0, 6000.0, nc), np.nan), self.cells(rng.uniform(-0.5, 0.5, nc), np.nan)
+        self.vel0, self.flux0 = self.edges(rng.uniform(-0.1, 0.1, ne), np.nan), self.edges(rng.uniform(-50.0, 50.0, ne), np.nan)
 
 
 class StepRig:

@@ -8,17 +8,15 @@ import pytest
 
 import omega_amd as oa
 from tests import barotropic_reference as BR
-from tests import column_reference as CR
-from tests.barotropic_fixtures import GRAVITY, btr_mesh
+from tests.barotropic_fixtures import GRAVITY, BtrRig
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
-from tests.vert_fixtures import mix_inputs, same as _same
+from tests.vert_fixtures import same as _same
 
 pytestmark = pytest.mark.gpu
 
-RHO0 = 1026.0
 MESHES = ("hex24x20", "ico2", "fib700_coast_ragged")
 LEVELS = (1, 3, 16, 17, 65)  # compact rows, odd pitch, whole lines, padded rows, more levels than a wavefront
-EDGE_1D = ("BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean")
 DT = 20.0
 
 
@@ -27,96 +25,10 @@ def _device():
     oa.device_init(0)
 
 
-class Rig:
-    """One rank's VertCoord and BarotropicMode on random global inputs in local order (layer ranges with land and
-    KMin > 0 from tests.vert_fixtures.mix_inputs, `full`: every layer active)"""
-
-    def __init__(self, g, K, nparts=1, rank=0, full=False, seed=7):
-        self.K = K
-        self.decomp = oa.Decomp(oa.GlobalMesh(g), nparts, rank, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K)
-        self.n_own, self.n_all, self.n_size = m.NCellsOwned, m.NCellsAll, m.NCellsSize
-        self.e_own, self.e_all, self.e_size = m.NEdgesOwned, m.NEdgesAll, m.NEdgesSize
-        self.cid, self.eid = self.decomp.get_array("CellID"), self.decomp.get_array("EdgeID")
-        G = mix_inputs(g, K, seed, full, 2)
-        rng = np.random.default_rng(seed + 50)
-        nc, ne = int(g["nCells"]), int(g["nEdges"])
-        G.update(bot=rng.uniform(100.0, 6000.0, nc), ssh=rng.uniform(-0.5, 0.5, nc), vel=rng.uniform(-0.1, 0.1, ne),
-                 forcing=rng.uniform(-1.0e-5, 1.0e-5, ne), tend=rng.uniform(-1.0e-5, 1.0e-5, (ne, K)))
-        crow, erow = self.cid[: self.n_all] - 1, self.eid[: self.e_all] - 1
-
-        def loc(x, rows, n_size):
-            out = np.full((n_size,) + x.shape[1:], np.nan)  # NaN on the sentinel row
-            out[: len(rows)] = x[rows]
-            return out
-
-        self.h, self.u, self.tend = loc(G["h"], crow, self.n_size), loc(G["un"], erow, self.e_size), loc(G["tend"], erow, self.e_size)
-        self.bot, self.ssh0 = loc(G["bot"], crow, self.n_size), loc(G["ssh"], crow, self.n_size)
-        self.vel0, self.forcing0 = loc(G["vel"], erow, self.e_size), loc(G["forcing"], erow, self.e_size)
-        self.vc = oa.VertCoord(m, K, RHO0, "Uniform", G["min_level"], G["max_level"], decomp=self.decomp)
-        self.vc.set("BottomDepth", self.bot)
-        self.lo, self.hi = CR.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
-        self.lo_e, self.hi_e = self.vc.get("MinLayerEdgeBot"), self.vc.get("MaxLayerEdgeTop")
-        self.coe = m.get_array("CellsOnEdge")
-        self.active = np.zeros((self.n_size, K), bool)
-        self.active[: self.n_all] = BR.range_mask(self.lo, self.hi, self.n_all, K)
-        self.e_active = np.zeros((self.e_size, K), bool)
-        self.e_active[: self.e_all] = BR.range_mask(self.lo_e, self.hi_e, self.e_all, K)
-        self.M = btr_mesh(m, self.bot)
-        self.vel0[: self.e_all][self.M.mask[: self.e_all] == 0.0] = 0.0  # no flow through a shut edge
-        self.bm = oa.BarotropicMode(m, self.vc)
-        for name in EDGE_1D + ("SSH", "BclVelocity"):
-            assert np.all(self.bm.get(name) == 0.0)  # zero at construction
-
-    def seeded(self, a, edge=False):
-        m = self.e_active if edge else self.active
-        return np.where(m, a, np.nan)
-
-    def padded(self, a):
-        pad = np.full(a.shape[:-1] + (oa.level_pitch(self.K),), np.nan)
-        pad[..., : self.K] = a
-        return pad
-
-    def dev(self, a):
-        return oa.DeviceBuffer(self.padded(a))
-
-    def poison(self):
-        for name in EDGE_1D:
-            self.bm.set(name, np.full(self.e_size, np.nan))
-        self.bm.set("SSH", np.full(self.n_size, np.nan))
-        oa.copy_to_device(self.bm.device_ptr("BclVelocity"), np.full((self.e_size, oa.level_pitch(self.K)), np.nan))
-
-    def bcl_padded(self):
-        buf = np.empty((self.e_size, oa.level_pitch(self.K)))
-        oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(self.bm.device_ptr("BclVelocity")),
-                                  oa.C.c_size_t(buf.nbytes))
-        return buf
-
-    def state(self):
-        return {n: self.bm.get(n) for n in EDGE_1D + ("SSH",)} | {"BclVelocity": self.bcl_padded()}
-
-    def nan_state(self):
-        out = {n: np.full(self.e_size, np.nan) for n in EDGE_1D}
-        out["SSH"] = np.full(self.n_size, np.nan)
-        out["BclVelocity"] = np.full((self.e_size, self.K), np.nan)
-        return out
-
-    def check(self, want, what):
-        got = self.state()
-        for n in want:
-            _same(got[n], self.padded(want[n]) if n == "BclVelocity" else want[n], f"{n} ({what})")
-
-    def load_2d(self):
-        """SSH, BtrVelocity, BtrForcing on the local elements, NaN beyond; BtrFluxMean NaN everywhere"""
-        self.poison()
-        self.bm.set("SSH", self.ssh0), self.bm.set("BtrVelocity", self.vel0), self.bm.set("BtrForcing", self.forcing0)
-        return self.ssh0.copy(), self.vel0.copy(), self.forcing0.copy(), np.full(self.e_size, np.nan)
-
-
 @pytest.mark.parametrize("K", LEVELS)
 @pytest.mark.parametrize("mesh", MESHES)
 def test_column_calls_bit_exact_on_nan_seeded_arrays(mesh, K):
-    x = Rig(named_mesh(mesh), K)
+    x = BtrRig(named_mesh(mesh), K)
     h, u, t = x.seeded(x.h), x.seeded(x.u, edge=True), x.seeded(x.tend, edge=True)
     bh, bu, bt = x.dev(h), x.dev(u), x.dev(t)
     # splitVelocity alone
@@ -168,7 +80,7 @@ def test_column_calls_bit_exact_on_nan_seeded_arrays(mesh, K):
 @pytest.mark.parametrize("nsub", [1, 2, 7])
 @pytest.mark.parametrize("mesh", MESHES)
 def test_subcycle_bit_exact(mesh, nsub):
-    x = Rig(named_mesh(mesh), 3)
+    x = BtrRig(named_mesh(mesh), 3)
     ssh, vel, forcing, flux = x.load_2d()
     x.bm.subcycle(nsub, DT)
     oa.device_synchronize()
@@ -187,7 +99,7 @@ def test_subcycle_bit_exact(mesh, nsub):
 
 
 def test_two_sub_steps_are_two_calls_of_one():
-    x = Rig(named_mesh("fib700_coast_ragged"), 3)
+    x = BtrRig(named_mesh("fib700_coast_ragged"), 3)
     x.load_2d()
     x.bm.subcycle(2, DT)
     oa.device_synchronize()
@@ -210,7 +122,7 @@ def test_stream_and_null_stream_forms_agree():
     s = oa.Stream()
     out = []
     for st in (None, s):
-        x = Rig(g, 17)
+        x = BtrRig(g, 17)
         bh, bu, bt = x.dev(x.h), x.dev(x.u), x.dev(x.tend)
         x.poison()
         x.bm.split_velocity(bh.ptr, bu.ptr, stream=st)
@@ -234,7 +146,7 @@ def test_stream_and_null_stream_forms_agree():
 
 
 def test_no_call_allocates():
-    x = Rig(named_mesh("hex24x20"), 16)
+    x = BtrRig(named_mesh("hex24x20"), 16)
     bh, bu, bt, r = x.dev(x.h), x.dev(x.u), x.dev(x.tend), x.dev(x.u)
 
     def calls():
@@ -254,7 +166,7 @@ def test_no_call_allocates():
 
 def test_refusals():
     g = named_mesh("hex24x20")
-    x, y = Rig(g, 16), Rig(g, 15)
+    x, y = BtrRig(g, 16), BtrRig(g, 15)
     with pytest.raises(oa.OmegaAmdError, match="another mesh"):
         oa.BarotropicMode(x.mesh, y.vc)
     with pytest.raises(oa.OmegaAmdError, match="VertCoord is NULL"):
@@ -312,7 +224,7 @@ def test_two_part_decomposition_matches_one_part(mesh, K):
     g = named_mesh(mesh)
 
     def run(nparts, rank):
-        x = Rig(g, K, nparts=nparts, rank=rank)
+        x = BtrRig(g, K, nparts=nparts, rank=rank)
         bh, bu, bt = x.dev(x.h), x.dev(x.u), x.dev(x.tend)
         x.bm.split_velocity(bh.ptr, bu.ptr, with_ssh=True)
         x.bm.compute_forcing(bh.ptr, bt.ptr)

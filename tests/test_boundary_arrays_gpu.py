@@ -13,6 +13,7 @@ import pytest
 
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
+from tests.rank_rig import raw
 from tests.vert_fixtures import EOS_OUT, MIX_OUT
 
 pytestmark = pytest.mark.gpu
@@ -82,12 +83,6 @@ def message(text=None):
     return m.group(1)
 
 
-def raw_read(ptr, n):
-    out = np.empty(n)
-    oa._chk(oa.lib().omg_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(out.nbytes)))
-    return out
-
-
 def test_named_arrays(rig):
     rng = np.random.default_rng(17)
     all_cases = cases(rig)
@@ -103,7 +98,7 @@ def test_named_arrays(rig):
             p = obj.device_ptr(name)
             assert p, what
             first = v.reshape(-1, shape[-1])[0]
-            assert np.array_equal(raw_read(p, first.size), first), what
+            assert np.array_equal(raw(p, first.size), first), what
         with pytest.raises(oa.OmegaAmdError, match="size mismatch"):
             obj.set(name, np.zeros(v.size + 1, dtype=dtype))
         out = np.zeros(shape, dtype=dtype)

@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 import omega_amd as oa
+from tests.column_reference import RHO0
 from tests.monotone_adv_fixtures import Mono3Rig
-from tests.split_explicit_fixtures import RHO0, StepRig
+from tests.split_explicit_fixtures import StepRig
 
 SYMBOLS = ("omg_monoadv_attach_vert_adv", "omg_vertadv_set_tracer_term")
 

@@ -13,10 +13,10 @@ from omega_amd.meshgen import planar_hex
 from tests import column_reference as CR
 from tests import gent_mcwilliams_reference as GR
 from tests import pressure_grad_reference as PR
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
 from tests.vert_fixtures import mix_inputs
 
-RHO0 = 1026.0
 EPS = np.finfo(np.float64).eps
 KAPPA, SPEED = 600.0, 0.3
 

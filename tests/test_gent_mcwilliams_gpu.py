@@ -15,14 +15,15 @@ from omega_amd.meshgen import planar_hex
 from tests import gent_mcwilliams_reference as GR
 from tests import pressure_grad_reference as PR
 from tests import vert_mix_reference as MR
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
+from tests.rank_rig import RankRig, raw
 from tests.split_explicit_fixtures import StepRig
 from tests.vert_fixtures import (FUSED, STAGE_SPEC_VOL_DISP, column_limit, level_pitch, mix_inputs, pcr_levels,
-                                 same as _same)
+                                 same as _same, systems_launch)
 
 pytestmark = pytest.mark.gpu
 
-RHO0 = 1026.0
 NT = 2
 EPS = np.finfo(np.float64).eps
 KAPPA, SPEED = 450.0, 0.25
@@ -36,22 +37,13 @@ LDS_BYTES, MAX_ROWS, LANES, LDS_ARRAYS = 65536, 1024, 256, 7
 def gm_launch(K):
     """launchBolusVelocity (kernels/GMKernels.hip), restated: columns per workgroup, the lanes they occupy, the lanes of
     the workgroup, its pad lanes and its dynamic LDS (seven doubles per occupied lane)"""
-    sys = LANES // K if K <= LANES else 1
-    rows = sys * K
-    threads = (rows + 63) // 64 * 64
+    sys, rows, threads = systems_launch(K)
     return dict(Sys=sys, Rows=rows, Threads=threads, PadLanes=threads - rows, LdsBytes=LDS_ARRAYS * rows * 8)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _device():
     oa.device_init(0)
-
-
-def _raw(ptr, shape):
-    """raw device memory as a host array (padding included)"""
-    buf = np.empty(shape)
-    oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(ptr), oa.C.c_size_t(buf.nbytes))
-    return buf
 
 
 def synthetic_fields(rng, h):
@@ -65,48 +57,34 @@ def synthetic_fields(rng, h):
     return 1.0 / rho, 1.0 / disp, z
 
 
-class Rig:
+class Rig(RankRig):
     """One rank's VertCoord, Eos and GentMcWilliams on global inputs (tests.vert_fixtures.mix_inputs: layer ranges with
     land, KMin > 0, single layers) in local order, a per-edge Kappa with zeros in it, and the column fields: from
     update_column up to the column pass's limit, synthetic beyond it (handed to the array form)."""
 
     def __init__(self, g, K, eos_kind, seed=7, full=False):
-        self.K, self.P = K, level_pitch(K)
-        self.gm_mesh = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm_mesh, 1, 0, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K)
-        self.n_all, self.n_size, self.e_all, self.e_size = m.NCellsAll, m.NCellsSize, m.NEdgesAll, m.NEdgesSize
-        cid = self.decomp.get_array("CellID")
+        super().__init__(g, K)
+        self.P = level_pitch(K)
+        m = self.mesh
         G = mix_inputs(g, K, seed, full, NT)
         rng = self.rng = np.random.default_rng(seed + 100)
         n = int(g["nCells"])
-        crow = cid[: self.n_all] - 1
-
-        def loc(x):
-            out = np.zeros((self.n_size,) + x.shape[1:])
-            out[: self.n_all] = x[crow]
-            return out
-
-        self.h = loc(G["h"])
-        self.tr = np.stack([loc(t) for t in G["tr"]])
-        self.vc = oa.VertCoord(m, K, RHO0, "Uniform", G["min_level"], G["max_level"], decomp=self.decomp)
-        self.vc.set("BottomDepth", loc(rng.uniform(100.0, 6000.0, n)))
+        self.h, self.tr = self.cells(G["h"]), self.cells(G["tr"])
+        self.layers(G["min_level"], G["max_level"])
+        self.vc.set("BottomDepth", self.cells(rng.uniform(100.0, 6000.0, n)))
         self.eos = oa.Eos(m, K, eos_kind)
         self.gm = oa.GentMcWilliams(m, self.vc, self.eos, kappa=KAPPA, grav_wave_speed=SPEED)
         assert np.all(self.gm.get("Kappa") == KAPPA)  # GMKappa at construction
         for name, v in (("SurfacePressure", rng.uniform(0.9e5, 1.1e5, n)), ("TidalPotential", rng.uniform(-1.0, 1.0, n)),
                         ("SelfAttractionLoading", rng.uniform(-0.1, 0.1, n))):
             assert np.all(self.gm.get(name) == 0.0)  # zero at construction
-            self.gm.set(name, loc(v))
+            self.gm.set(name, self.cells(v))
         for name in ("BolusVelocity", "StreamFunction"):
-            assert np.all(_raw(self.gm.device_ptr(name), (self.e_size, self.P)) == 0.0)
+            assert np.all(raw(self.gm.device_ptr(name), (self.e_size, self.P)) == 0.0)
         self.kappa = rng.uniform(100.0, 900.0, self.e_size)
         self.kappa[::7] = 0.0
         self.gm.set("Kappa", self.kappa)
         self.coe, self.dc = m.get_array("CellsOnEdge"), m.get_array("DcEdge")
-        self.lo, self.hi = self.vc.get("MinLayerEdgeBot"), self.vc.get("MaxLayerEdgeTop")
-        self.in_range = np.zeros((self.e_size, K), bool)
-        self.in_range[: self.e_all] = PR.range_mask(self.lo, self.hi, self.e_all, K)
         self.column_pass = K <= COLUMN_LIMIT
         self.synthetic = None if self.column_pass else synthetic_fields(rng, self.h)
 
@@ -114,11 +92,6 @@ class Rig:
         """both outputs NaN everywhere, padding and sentinel row included"""
         for name in ("BolusVelocity", "StreamFunction"):
             oa.copy_to_device(self.gm.device_ptr(name), np.full((self.e_size, self.P), np.nan))
-
-    def padded(self, a):
-        pad = np.full((self.e_size, self.P), np.nan)
-        pad[:, : self.K] = a
-        return pad
 
     def update_column(self, stream=None):
         for name in ("SpecVol", "SpecVolDisplaced"):
@@ -142,18 +115,18 @@ class Rig:
         oa.device_synchronize()
 
     def outputs(self):
-        return {name: _raw(self.gm.device_ptr(name), (self.e_size, self.P)) for name in ("BolusVelocity", "StreamFunction")}
+        return {name: raw(self.gm.device_ptr(name), (self.e_size, self.P)) for name in ("BolusVelocity", "StreamFunction")}
 
     def restated(self, transport=None):
         u, psi = np.full((self.e_size, self.K), np.nan), np.full((self.e_size, self.K), np.nan)
-        GR.bolus_velocity(self.h, *self.fields(), self.coe, self.dc, self.kappa, self.lo, self.hi, self.e_all, RHO0, SPEED,
-                          u, psi, transport)
+        GR.bolus_velocity(self.h, *self.fields(), self.coe, self.dc, self.kappa, self.lo_e, self.hi_e, self.e_all, RHO0,
+                          SPEED, u, psi, transport)
         return u, psi
 
     def seeded_transport(self, seed=1):
         rng = np.random.default_rng(seed)
         t = np.full((self.e_size, self.K), np.nan)
-        t[self.in_range] = rng.uniform(-0.1, 0.1, int(self.in_range.sum()))
+        t[self.e_active] = rng.uniform(-0.1, 0.1, int(self.e_active.sum()))
         return t, oa.DeviceBuffer(self.padded(t))
 
 
@@ -183,17 +156,17 @@ def test_bit_exact_on_nan_seeded_outputs(mesh, K, eos_kind):
     got = x.outputs()
     _same(got["BolusVelocity"], x.padded(want_u), "BolusVelocity")
     _same(got["StreamFunction"], x.padded(want_psi), "StreamFunction")
-    assert np.isfinite(want_u[x.in_range]).all() and np.isfinite(want_psi[x.in_range]).all() and x.in_range.any()
-    assert np.isnan(want_u[~x.in_range]).all()
+    assert np.isfinite(want_u[x.e_active]).all() and np.isfinite(want_psi[x.e_active]).all() and x.e_active.any()
+    assert np.isnan(want_u[~x.e_active]).all()
     # ... and the case is what it is there for
     n = x.e_all
-    nlay = x.in_range[:n].sum(axis=1)
+    nlay = x.e_active[:n].sum(axis=1)
     shape = gm_launch(K)
     assert (nlay == 0).any()  # edges next to land (an empty range) are left alone
     assert (nlay == 1).any()  # Lo == Hi: no system, 0 / hE
     assert nlay.max() == K    # a full column: pcr_levels(K - 1) levels
     if K > 2:
-        assert np.abs(want_u[x.in_range]).max() > 0.0 and (x.lo[:n][nlay > 0] > 0).any()
+        assert np.abs(want_u[x.e_active]).max() > 0.0 and (x.lo_e[:n][nlay > 0] > 0).any()
     if shape["Sys"] > 1 and K > 1:  # columns of different depth share a workgroup
         assert any(len(set(nlay[i: i + shape["Sys"]])) > 1 for i in range(0, n, shape["Sys"]))
     if "coast" in mesh:
@@ -248,12 +221,12 @@ def test_a_given_transport_takes_the_bolus_velocity(mesh, K):
     for name, v in x.outputs().items():
         _same(v, base[name], name)
     want = t.copy()
-    want[x.in_range] = (t + base["BolusVelocity"][:, :K])[x.in_range]
+    want[x.e_active] = (t + base["BolusVelocity"][:, :K])[x.e_active]
     _same(buf.to_host(), x.padded(want), "Transport")  # NaN outside the ranges, in the padding and on the sentinel row
-    assert not np.array_equal(want[x.in_range], t[x.in_range])
+    assert not np.array_equal(want[x.e_active], t[x.e_active])
     got = x.gm.compute(x.h, np.nan_to_num(t))  # the numpy form of the binding
-    _same(got[x.in_range], want[x.in_range], "Transport (numpy form)")
-    assert np.all(got[~x.in_range] == 0.0)
+    _same(got[x.e_active], want[x.e_active], "Transport (numpy form)")
+    assert np.all(got[~x.e_active] == 0.0)
 
 
 def test_update_column_leaves_the_fields_of_vertmix_n2():
@@ -272,7 +245,7 @@ def test_update_column_leaves_the_fields_of_vertmix_n2():
     _same(dev, host, "BruntVaisalaFreqSq")
     # ... and the contract's N2_c on the edges is that expression on the edge's two cells
     checked = 0
-    for s in GR.edge_systems(x.h, sv, svd, zm, x.coe, x.dc, x.kappa, x.lo, x.hi, x.e_all, RHO0, SPEED):
+    for s in GR.edge_systems(x.h, sv, svd, zm, x.coe, x.dc, x.kappa, x.lo_e, x.hi_e, x.e_all, RHO0, SPEED):
         if s["he"].shape[1] < 2:
             continue
         for side, n2 in enumerate(s["n2_cells"]):

@@ -21,6 +21,7 @@ import pytest
 import omega_amd as oa
 from tests.meshes import named_mesh
 from tests.problem import Problem, poison_tendencies
+from tests.rank_rig import raw
 from tests.split_explicit_fixtures import StepRig
 from tests.vert_adv_fixtures import adv_inputs
 
@@ -51,17 +52,11 @@ def assert_bits(got, want, name):
     assert not bad.any(), f"{name}: {bad.sum()} of {bad.size} values differ, first at {np.argwhere(bad)[0]}"
 
 
-def read_raw(ptr, shape):
-    buf = np.empty(shape)
-    oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(ptr), oa.C.c_size_t(buf.nbytes))
-    return buf
-
-
 def raw_tendencies(P):
     """the three whole device arrays (planes, rows, pitch), as poison_tendencies lays them out"""
     pitch = oa.level_pitch(P.K)
     m = P.mesh
-    return [read_raw(P.tend.device_ptr(w)[0], (planes, rows, pitch))
+    return [raw(P.tend.device_ptr(w)[0], (planes, rows, pitch))
             for w, rows, planes in ((0, m.NCellsSize, 1), (1, m.NEdgesSize, 1), (2, m.NCellsSize, max(P.NT, 1)))]
 
 
@@ -191,8 +186,8 @@ class Outputs:
 
     def read(self):
         oa.device_synchronize()
-        h = read_raw(self.h_next, self.h_shape)
-        tr = read_raw(self.tr_next, self.tr_shape) if self.P.NT > 0 else None
+        h = raw(self.h_next, self.h_shape)
+        tr = raw(self.tr_next, self.tr_shape) if self.P.NT > 0 else None
         return h, tr, raw_tendencies(self.P)
 
     def sequence(self, coeff):

@@ -9,10 +9,12 @@ import numpy as np
 import pytest
 
 import omega_amd as oa
+from tests.column_reference import RHO0
 from tests.monotone_adv_fixtures import RANDOM, Inputs, Mono3Rig
-from tests.split_explicit_fixtures import RHO0, StepRig
+from tests.rank_rig import raw
+from tests.split_explicit_fixtures import StepRig
 from tests.test_monotone_adv_3d import margin_value
-from tests.test_monotone_adv_gpu import MAXT, NO_ADV, Dev, assert_bits, mono_step_by_hand, read_raw
+from tests.test_monotone_adv_gpu import MAXT, NO_ADV, Dev, assert_bits, mono_step_by_hand
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +42,7 @@ class Dev3(Dev):
 
     def check(self, nt, stream=None):
         got = super().check(nt, stream)
-        assert_bits(read_raw(self.va.device_ptr("VerticalTransport"), self.wt.shape), self.wt, "VerticalTransport")
+        assert_bits(raw(self.va.device_ptr("VerticalTransport"), self.wt.shape), self.wt, "VerticalTransport")
         return got
 
 

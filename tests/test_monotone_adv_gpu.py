@@ -12,6 +12,7 @@ import pytest
 import omega_amd as oa
 from tests import monotone_adv_reference as MR
 from tests.monotone_adv_fixtures import RANDOM, STEP, Inputs, MonoRig
+from tests.rank_rig import raw
 from tests.split_explicit_fixtures import StepRig
 from tests.test_monotone_adv import margin, margin_value
 
@@ -36,12 +37,6 @@ def assert_bits(got, want, name):
     assert got.shape == want.shape, name
     bad = ~bits_equal(np.ascontiguousarray(got), np.ascontiguousarray(want))
     assert not bad.any(), f"{name}: {bad.sum()} of {bad.size} values differ, first at {np.argwhere(bad)[0]}"
-
-
-def read_raw(ptr, shape):
-    buf = np.empty(shape)
-    oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(ptr), oa.C.c_size_t(buf.nbytes))
-    return buf
 
 
 class Dev:
@@ -80,8 +75,8 @@ class Dev:
 
     def read(self):
         oa.device_synchronize()
-        return (self.tend.to_host(), read_raw(self.mono.device_ptr("ScaleIn"), self.shape),
-                read_raw(self.mono.device_ptr("ScaleOut"), self.shape))
+        return (self.tend.to_host(), raw(self.mono.device_ptr("ScaleIn"), self.shape),
+                raw(self.mono.device_ptr("ScaleOut"), self.shape))
 
     def reference(self):
         """the restatement for all planes, from tend0, once"""

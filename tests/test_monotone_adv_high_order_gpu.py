@@ -12,10 +12,11 @@ from omega_amd.meshgen import planar_hex
 from tests import monotone_adv_reference as MR
 from tests.monotone_adv_fixtures import ORDERS, RANDOM, Ho3Rig, HoRig, Inputs, MonoRig
 from tests.monotone_adv_reference import MonoMesh
+from tests.rank_rig import raw
 from tests.split_explicit_fixtures import StepRig
 from tests.test_monotone_adv_3d_gpu import Dev3
 from tests.test_monotone_adv_3d_gpu import LEVELS as LEVELS_3D
-from tests.test_monotone_adv_gpu import LEVELS, NO_ADV, Dev, assert_bits, mono_step_by_hand, read_raw
+from tests.test_monotone_adv_gpu import LEVELS, NO_ADV, Dev, assert_bits, mono_step_by_hand
 from tests.test_monotone_adv_high_order import growth, margin_value
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +52,7 @@ class _Ho:
         return t, s
 
     def read(self):
-        return super().read() + (read_raw(self.mono.device_ptr("Hess"), self.hshape),)
+        return super().read() + (raw(self.mono.device_ptr("Hess"), self.hshape),)
 
     def reference(self):
         if not hasattr(self, "_ref_ho"):
@@ -82,7 +83,7 @@ class DevHo(_Ho, Dev):
 class DevHo3(_Ho, Dev3):
     def check(self, nt, stream=None):
         got = super().check(nt, stream)
-        assert_bits(read_raw(self.va.device_ptr("VerticalTransport"), self.wt.shape), self.wt, "VerticalTransport")
+        assert_bits(raw(self.va.device_ptr("VerticalTransport"), self.wt.shape), self.wt, "VerticalTransport")
         return got
 
 

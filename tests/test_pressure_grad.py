@@ -9,10 +9,10 @@ import omega_amd as oa
 from omega_amd.meshgen import planar_hex
 from tests import column_reference as CR
 from tests import pressure_grad_reference as PR
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
 from tests.vert_fixtures import column_levels
 
-RHO0 = 1026.0
 G = CR.GRAVITY
 EPS = np.finfo(np.float64).eps
 

@@ -9,14 +9,14 @@ import pytest
 
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
-from tests import column_reference as CR
 from tests import pressure_grad_reference as PR
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
+from tests.rank_rig import RankRig
 from tests.vert_fixtures import EOS_OUT, VC_OUT, mix_inputs, same as _same
 
 pytestmark = pytest.mark.gpu
 
-RHO0 = 1026.0
 NT = 2
 EPS = np.finfo(np.float64).eps
 MESHES = ("hex24x20", "fib700_coast_ragged")
@@ -37,34 +37,20 @@ def forcing_inputs(g, seed):
                 bot=rng.uniform(100.0, 6000.0, n))
 
 
-class Rig:
+class Rig(RankRig):
     """One rank's VertCoord, Eos, OceanState, Tracers (T, S) and PressureGrad -- with `config` also AuxiliaryState and
     Tendencies -- on global inputs G (default: tests.vert_fixtures.mix_inputs, layer ranges with land) and forcing F
     in local order."""
 
     def __init__(self, g, K, eos_kind, nparts=1, rank=0, seed=7, full=False, G=None, F=None, linear=(-0.2, 0.8, 1000.0),
                  rho0=RHO0, config=None):
-        self.K = K
-        self.gm = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm, nparts, rank, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K)
-        self.n_all, self.n_size = m.NCellsAll, m.NCellsSize
-        self.e_own, self.e_all, self.e_size = m.NEdgesOwned, m.NEdgesAll, m.NEdgesSize
-        self.cid, self.eid = self.decomp.get_array("CellID"), self.decomp.get_array("EdgeID")
+        super().__init__(g, K, nparts, rank)
+        m = self.mesh
         G = self.G = mix_inputs(g, K, seed, full, NT) if G is None else G
         F = self.F = forcing_inputs(g, seed) if F is None else F
-        crow, erow = self.cid[: self.n_all] - 1, self.eid[: self.e_all] - 1
-
-        def loc(x, rows, n_size):
-            out = np.zeros((n_size,) + x.shape[1:])
-            out[: len(rows)] = x[rows]
-            return out
-
-        self.h = loc(G["h"], crow, self.n_size)
-        self.tr = np.stack([loc(t, crow, self.n_size) for t in G["tr"]])
-        self.un = loc(G["un"], erow, self.e_size)
-        self.ps, self.tidal, self.sal, self.bot = (loc(F[k], crow, self.n_size) for k in ("ps", "tidal", "sal", "bot"))
-        self.vc = oa.VertCoord(m, K, rho0, "Uniform", G["min_level"], G["max_level"], decomp=self.decomp)
+        self.h, self.tr, self.un = self.cells(G["h"]), self.cells(G["tr"]), self.edges(G["un"])
+        self.ps, self.tidal, self.sal, self.bot = (self.cells(F[k]) for k in ("ps", "tidal", "sal", "bot"))
+        self.layers(G["min_level"], G["max_level"], rho0=rho0)
         self.vc.set("BottomDepth", self.bot)
         self.eos = oa.Eos(m, K, eos_kind, *linear)
         self.state = oa.OceanState(m, None, K, 2)
@@ -77,12 +63,6 @@ class Rig:
             self.pg.set(name, v)
         self.coe, self.dc = m.get_array("CellsOnEdge"), m.get_array("DcEdge")
         self.mask = np.ascontiguousarray(m.get_array("EdgeMask")[:, 0])
-        self.lo, self.hi = self.vc.get("MinLayerEdgeBot"), self.vc.get("MaxLayerEdgeTop")
-        lo_c, hi_c = CR.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
-        lo, hi = PR.edge_ranges(self.coe, self.e_all, lo_c, hi_c, K)
-        assert np.array_equal(lo, self.lo) and np.array_equal(hi, self.hi)
-        self.in_range = np.zeros((self.e_size, K), bool)
-        self.in_range[: self.e_all] = PR.range_mask(self.lo, self.hi, self.e_all, K)
         if config is not None:
             cfg = oa.default_config(**config)
             self.aux = oa.AuxiliaryState(m, None, K, NT)
@@ -115,17 +95,12 @@ class Rig:
         levels, the sentinel row, the pitch padding"""
         rng = np.random.default_rng(seed)
         t = np.full((self.e_size, self.K), np.nan)
-        t[self.in_range] = rng.uniform(-1.0e-3, 1.0e-3, int(self.in_range.sum()))
+        t[self.e_active] = rng.uniform(-1.0e-3, 1.0e-3, int(self.e_active.sum()))
         return t, oa.DeviceBuffer(self.padded(t))
-
-    def padded(self, t):
-        pad = np.full((self.e_size, oa.level_pitch(self.K)), np.nan)
-        pad[:, : self.K] = t
-        return pad
 
     def restated(self, tend, fields=None):
         p, geo, sv = self.fields() if fields is None else fields
-        return PR.pressure_grad(tend.copy(), p, geo, sv, self.coe, self.dc, self.mask, self.lo, self.hi, self.e_all)
+        return PR.pressure_grad(tend.copy(), p, geo, sv, self.coe, self.dc, self.mask, self.lo_e, self.hi_e, self.e_all)
 
 
 @pytest.mark.parametrize("mesh,K,eos_kind", CASES)
@@ -138,10 +113,10 @@ def test_bit_exact_on_nan_seeded_arrays(mesh, K, eos_kind):
     oa.device_synchronize()
     want = x.restated(t)
     _same(buf.to_host(), x.padded(want), "Tend")
-    assert np.isfinite(want[x.in_range]).all() and x.in_range.any()
-    assert not np.array_equal(want[x.in_range], t[x.in_range])
+    assert np.isfinite(want[x.e_active]).all() and x.e_active.any()
+    assert not np.array_equal(want[x.e_active], t[x.e_active])
     if "coast" in mesh:
-        assert (~x.in_range[: x.e_all]).all(axis=1).any()  # edges next to land are left alone
+        assert (~x.e_active[: x.e_all]).all(axis=1).any()  # edges next to land are left alone
 
 
 @pytest.mark.parametrize("mesh,K,eos_kind", CASES)

@@ -9,8 +9,9 @@ import pytest
 import omega_amd as oa
 from tests import split_explicit_reference as SR
 from tests.barotropic_fixtures import GRAVITY, closed_basin
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
-from tests.split_explicit_fixtures import RHO0, CallRig, StepRig, step_by_hand
+from tests.split_explicit_fixtures import CallRig, StepRig, step_by_hand
 from tests.vert_fixtures import same
 
 pytestmark = pytest.mark.gpu

@@ -15,6 +15,7 @@ import pytest
 import omega_amd as oa
 from tests.meshes import named_mesh
 from tests.problem import Problem, poison_tendencies
+from tests.rank_rig import raw
 from tests.split_explicit_fixtures import StepRig
 from tests.vert_adv_fixtures import adv_inputs
 
@@ -46,9 +47,7 @@ def raw_tendency(P, which):
     """the whole device array (planes, rows, pitch), row padding included"""
     ptr, _ = P.tend.device_ptr(which)
     rows = P.mesh.NEdgesSize if which == 1 else P.mesh.NCellsSize
-    buf = np.empty((max(P.NT, 1) if which == 2 else 1, rows, oa.level_pitch(P.K)))  # as poison_tendencies lays them out
-    oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(ptr), oa.C.c_size_t(buf.nbytes))
-    return buf
+    return raw(ptr, (max(P.NT, 1) if which == 2 else 1, rows, oa.level_pitch(P.K)))  # as poison_tendencies lays them out
 
 
 def second_level(P):

@@ -5,61 +5,21 @@ rules.  Every test that draws random inputs asserts the fixture condition: a tra
 import numpy as np
 import pytest
 
-import omega_amd as oa
-from tests import column_reference as CR
 from tests import vert_adv_reference as VR
 from tests.meshes import named_mesh
-from tests.pressure_grad_reference import edge_ranges
-from tests.vert_adv_fixtures import adv_inputs, assert_both_signs, sign_fractions
+from tests.vert_adv_fixtures import AdvRig, assert_both_signs, sign_fractions
 
 EPS = np.finfo(np.float64).eps
 MESHES = ("hex24x20", "fib700_coast_ragged")
 
 
-class Host:
-    """One rank's host-only mesh in the library's local order with the inputs of adv_inputs in that order"""
-
-    def __init__(self, g, K, nt=2, weights="Uniform", full=False):
-        self.K, self.nt = K, nt
-        self.gm = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm, 1, 0, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K, host_only=True)
-        self.n_all, self.n_size, self.e_all, self.e_size = m.NCellsAll, m.NCellsSize, m.NEdgesAll, m.NEdgesSize
-        self.cid, self.eid = self.decomp.get_array("CellID"), self.decomp.get_array("EdgeID")
-        G = self.G = adv_inputs(g, K, nt)
-        if full:
-            G["min_level"][:], G["max_level"][:] = 1, K
-        crow, erow = self.cid[: self.n_all] - 1, self.eid[: self.e_all] - 1
-
-        def loc(x, rows, n_size):
-            out = np.zeros((n_size,) + x.shape[1:])
-            out[: len(rows)] = x[rows]
-            return out
-
-        self.d, self.ref, self.h = (loc(G[k], crow, self.n_size) for k in ("d", "ref", "h"))
-        self.tr = np.stack([loc(t, crow, self.n_size) for t in G["tr"]])
-        self.u = loc(G["un"], erow, self.e_size)
-        self.w = CR.movement_weights(weights, K)
-        self.lo, self.hi = CR.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
-        self.coe = m.get_array("CellsOnEdge")
-        self.mask = np.ascontiguousarray(m.get_array("EdgeMask")[:, 0])
-        self.lo_e, self.hi_e = edge_ranges(self.coe, self.e_all, self.lo, self.hi, K)
-        self.active = np.zeros((self.n_size, K), bool)
-        self.active[: self.n_all] = VR.active_mask(self.lo, self.hi, self.n_all, K)
-
-    def transport(self, d=None, ref=None):
-        wt = np.zeros((self.n_size, self.K))
-        return VR.vertical_transport(self.d if d is None else d, self.ref if ref is None else ref, self.w, self.lo,
-                                     self.hi, self.n_all, wt)
-
-
 def test_fixture_transport_has_both_signs():
     for mesh in MESHES:
         for K in (2, 15, 16, 37, 80):
-            x = Host(named_mesh(mesh), K)
+            x = AdvRig(named_mesh(mesh), K, device=False)
             cnt = assert_both_signs(x.transport(), x.lo, x.hi, x.n_all)
             assert cnt > 0
-    x = Host(named_mesh("hex24x20"), 1)
+    x = AdvRig(named_mesh("hex24x20"), 1, device=False)
     assert sign_fractions(x.transport(), x.lo, x.hi, x.n_all)[2] == 0  # one level: no interior interface
 
 
@@ -72,7 +32,7 @@ def test_column_is_closed(mesh, weights):
     magnitude <= 5 S adds at most K * 5 S * eps/2 per partial sum over K sums; with K levels that is within
     (3 K + 2.5 K) eps S <= 6 K eps S.  (Fixed weights need KMin = 0: full columns.)"""
     K = 12
-    x = Host(named_mesh(mesh), K, weights=weights, full=weights == "Fixed")
+    x = AdvRig(named_mesh(mesh), K, weights=weights, full=weights == "Fixed", device=False)
     wt = x.transport()
     assert_both_signs(wt, x.lo, x.hi, x.n_all)
     rows = np.nonzero(x.active.any(axis=1))[0]
@@ -92,7 +52,7 @@ def test_fixed_weights_give_a_z_level_grid():
     (D[K] - Wt[K]) + Wt[K+1] is the rounding error of that one addition and of the two operations that undo it:
     at most 3 * eps/2 * max(|Wt[K]|, |Wt[K+1]|, |D[K]|) <= 1.5 eps sum|D|.  The top layer takes SumD."""
     K = 15
-    x = Host(named_mesh("hex24x20"), K, weights="Fixed", full=True)
+    x = AdvRig(named_mesh("hex24x20"), K, weights="Fixed", full=True, device=False)
     wt = x.transport()
     assert_both_signs(wt, x.lo, x.hi, x.n_all)
     tend = VR.add_thickness_tend(x.d.copy(), wt, x.lo, x.hi, x.n_all)
@@ -109,7 +69,7 @@ def test_lagrangian_limit(mesh):
     SumD = a SumWh (1 + K eps) at worst, so |D[K] - TT[K]| <= (K + 3) eps |D[K]| and the K-term sum Acc stays within
     K (K + 4) eps max|D|."""
     K = 16
-    x = Host(named_mesh(mesh), K)
+    x = AdvRig(named_mesh(mesh), K, device=False)
     rng = np.random.default_rng(3)
     a = rng.uniform(-1.0e-4, 1.0e-4, x.n_size)
     d = a[:, None] * (x.w[None, :] * x.ref)
@@ -127,7 +87,7 @@ def test_constant_tracer_follows_thickness(mesh, order):
     more rounding, the two operations of the update two more, and the thickness update they are compared with has two
     of its own: within 8 eps |phi0| (|Wt[K]| + |Wb|)."""
     K, phi0 = 16, 34.7
-    x = Host(named_mesh(mesh), K)
+    x = AdvRig(named_mesh(mesh), K, device=False)
     wt = x.transport()
     assert_both_signs(wt, x.lo, x.hi, x.n_all)
     tr = np.full((2, x.n_size, K), phi0)
@@ -146,7 +106,7 @@ def test_constant_tracer_follows_thickness(mesh, order):
 def test_vertically_uniform_flow_feels_no_force(mesh):
     """u[e][K] = u_e: UTop = 0.5 (u + u) = u exactly, both fluxes are exactly zero and the tendency keeps its bits"""
     K = 15
-    x = Host(named_mesh(mesh), K)
+    x = AdvRig(named_mesh(mesh), K, device=False)
     wt = x.transport()
     assert_both_signs(wt, x.lo, x.hi, x.n_all)
     u = np.repeat(x.u[:, :1], K, axis=1)
@@ -196,7 +156,7 @@ def test_masking(mesh, order):
     """NaN wherever a call must not write or read -- outside the ranges, on land, on rows >= N*All: the NaN stay
     where they were and nothing inside a range becomes NaN"""
     K, nt = 15, 3
-    x = Host(named_mesh(mesh), K, nt=nt)
+    x = AdvRig(named_mesh(mesh), K, nt=nt, device=False)
 
     def seed(a, m):
         out = np.full(a.shape, np.nan)

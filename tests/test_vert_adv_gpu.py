@@ -8,16 +8,15 @@ import numpy as np
 import pytest
 
 import omega_amd as oa
-from tests import column_reference as CR
 from tests import pressure_grad_reference as PR
 from tests import vert_adv_reference as VR
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
-from tests.vert_adv_fixtures import adv_inputs, assert_both_signs
+from tests.vert_adv_fixtures import AdvRig, adv_inputs, assert_both_signs
 from tests.vert_fixtures import same as _same
 
 pytestmark = pytest.mark.gpu
 
-RHO0 = 1026.0
 EPS = np.finfo(np.float64).eps
 MESHES = ("hex24x20", "fib700_coast_ragged")
 LEVELS = (1, 2, 15, 16, 37, 80)
@@ -30,89 +29,10 @@ def _device():
     oa.device_init(0)
 
 
-class Rig:
-    """One rank's VertCoord, OceanState, Tracers and VertAdv (both flux orders) -- with `config` also AuxiliaryState
-    and Tendencies -- on the global inputs of tests.vert_adv_fixtures.adv_inputs in local order."""
-
-    def __init__(self, g, K, nt, nparts=1, rank=0, weights="Uniform", config=None, G=None):
-        self.K, self.nt = K, nt
-        self.gm = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm, nparts, rank, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K)
-        self.n_own, self.n_all, self.n_size = m.NCellsOwned, m.NCellsAll, m.NCellsSize
-        self.e_own, self.e_all, self.e_size = m.NEdgesOwned, m.NEdgesAll, m.NEdgesSize
-        self.cid, self.eid = self.decomp.get_array("CellID"), self.decomp.get_array("EdgeID")
-        G = self.G = adv_inputs(g, K, nt) if G is None else G
-        crow, erow = self.cid[: self.n_all] - 1, self.eid[: self.e_all] - 1
-
-        def loc(x, rows, n_size):
-            out = np.zeros((n_size,) + x.shape[1:])
-            out[: len(rows)] = x[rows]
-            return out
-
-        self.d, self.ref, self.h = (loc(G[k], crow, self.n_size) for k in ("d", "ref", "h"))
-        self.tr = np.stack([loc(t, crow, self.n_size) for t in G["tr"]])
-        self.u = loc(G["un"], erow, self.e_size)
-        self.w = CR.movement_weights(weights, K)
-        self.vc = oa.VertCoord(m, K, RHO0, weights, G["min_level"], G["max_level"], decomp=self.decomp)
-        self.lo, self.hi = CR.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
-        self.coe = m.get_array("CellsOnEdge")
-        self.mask = np.ascontiguousarray(m.get_array("EdgeMask")[:, 0])
-        self.lo_e, self.hi_e = self.vc.get("MinLayerEdgeBot"), self.vc.get("MaxLayerEdgeTop")
-        self.active = np.zeros((self.n_size, K), bool)
-        self.active[: self.n_all] = VR.active_mask(self.lo, self.hi, self.n_all, K)
-        self.e_active = np.zeros((self.e_size, K), bool)
-        self.e_active[: self.e_all] = PR.range_mask(self.lo_e, self.hi_e, self.e_all, K)
-        self.vc.set("RefLayerThickness", self.seeded(self.ref))  # NaN outside every column's range
-        assert np.array_equal(self.vc.get("VertCoordMovementWeights"), self.w)
-        self.state = oa.OceanState(m, None, K, 2)
-        self.tracers = oa.Tracers(m, None, K, nt, 2)
-        self.state.copy_to_device(self.h, self.u, 0)
-        self.tracers.copy_to_device(self.tr, 0)
-        self.va = {o: oa.VertAdv(m, self.vc, o) for o in (2, 1)}
-        for va in self.va.values():
-            assert np.all(va.get("VerticalTransport") == 0.0)  # zero at construction
-        if config is not None:
-            cfg = oa.default_config(**config)
-            self.aux = oa.AuxiliaryState(m, None, K, nt)
-            self.aux.set_options(cfg.FluxThicknessUpwind, cfg.FluxTracerUpwind, cfg.WindInterpIsotropic)
-            self.tend = oa.Tendencies(m, K, nt, cfg)
-
-    def seeded(self, a, edge=False):
-        """`a` inside the ranges, NaN everywhere else -- other levels, land, rows >= N*All, the sentinel row"""
-        m = self.e_active if edge else self.active
-        out = np.full(a.shape, np.nan)
-        out[..., m] = a[..., m]
-        return out
-
-    def padded(self, a):
-        """the device layout of a level-indexed host array, NaN in the row padding"""
-        pad = np.full(a.shape[:-1] + (oa.level_pitch(self.K),), np.nan)
-        pad[..., : self.K] = a
-        return pad
-
-    def dev(self, a):
-        return oa.DeviceBuffer(self.padded(a))
-
-    def poison_transport(self, order=2):
-        oa.copy_to_device(self.va[order].device_ptr("VerticalTransport"),
-                          np.full((self.n_size, oa.level_pitch(self.K)), np.nan))
-
-    def transport_padded(self, order=2):
-        buf = np.empty((self.n_size, oa.level_pitch(self.K)))
-        oa.lib().omg_copy_to_host(buf.ctypes.data_as(oa.C.c_void_p), oa.C.c_void_p(self.va[order].device_ptr("VerticalTransport")),
-                                  oa.C.c_size_t(buf.nbytes))
-        return buf
-
-    def want_transport(self, d):
-        return VR.vertical_transport(d, self.seeded(self.ref), self.w, self.lo, self.hi, self.n_all,
-                                     np.full((self.n_size, self.K), np.nan))
-
-
 @pytest.mark.parametrize("K", LEVELS)
 @pytest.mark.parametrize("mesh", MESHES)
 def test_bit_exact_on_nan_seeded_arrays(mesh, K):
-    x = Rig(named_mesh(mesh), K, max(TRACERS))
+    x = AdvRig(named_mesh(mesh), K, max(TRACERS))
     d = x.seeded(x.d)
     want_wt = x.want_transport(d)
     cnt = assert_both_signs(want_wt, x.lo, x.hi, x.n_all)
@@ -180,7 +100,7 @@ def test_stream_and_null_stream_forms_agree():
     s = oa.Stream()
     out = []
     for st in (None, s):
-        x = Rig(g, 37, 2)
+        x = AdvRig(g, 37, 2)
         x.poison_transport()
         d, d2 = x.dev(x.seeded(x.d)), x.dev(x.seeded(x.d))
         h, tr, u = x.dev(x.h), x.dev(x.tr), x.dev(x.u)
@@ -230,7 +150,7 @@ def _restated(x, base, order, wt=None):
 @pytest.mark.parametrize("mesh,K,nt,order", [("hex24x20", 16, 2, 2), ("fib700_coast_ragged", 37, 9, 1),
                                              ("fib700_coast_ragged", 15, 1, 2)])
 def test_attached_rhs_is_plain_rhs_then_the_terms(mesh, K, nt, order, fused):
-    x = Rig(named_mesh(mesh), K, nt, config={})
+    x = AdvRig(named_mesh(mesh), K, nt, config={})
     x.vc.set("RefLayerThickness", x.ref)
     x.tend.set_fused(fused)
     oa.device_synchronize()
@@ -276,7 +196,7 @@ def test_attached_rhs_is_plain_rhs_then_the_terms(mesh, K, nt, order, fused):
 def test_nothing_attached_is_the_plain_rhs_with_the_same_counters():
     """two Tendencies on one mesh, one of which had a VertAdv attached and detached: the same bits, the same fused
     kernels recorded by the kernel timer, the same graph statistics, the same resources per evaluation"""
-    x = Rig(named_mesh("hex24x20"), 16, 2, config={})
+    x = AdvRig(named_mesh("hex24x20"), 16, 2, config={})
     cfg = oa.default_config()
     other = oa.Tendencies(x.mesh, x.K, x.nt, cfg)
     x.tend.attach_vert_adv(x.va[2])
@@ -300,7 +220,7 @@ def test_nothing_attached_is_the_plain_rhs_with_the_same_counters():
 def test_attached_with_pressure_grad_vert_adv_comes_first():
     """NormalVelocityTend = (plain - vertical advection) - pressure gradient, in that order"""
     g, K, nt = named_mesh("fib700_coast_ragged"), 16, 2
-    x = Rig(g, K, nt, config=dict(SSHTendencyEnable=0))
+    x = AdvRig(g, K, nt, config=dict(SSHTendencyEnable=0))
     x.vc.set("RefLayerThickness", x.ref)
     rng = np.random.default_rng(11)
     x.vc.set("BottomDepth", np.concatenate([rng.uniform(100.0, 6000.0, x.n_all), np.zeros(x.n_size - x.n_all)]))
@@ -345,7 +265,7 @@ def test_steppers_keep_total_thickness_and_a_constant_tracer(kind):
     G["tr"] = np.full_like(G["tr"], phi0)
     runs = []
     for attach in (True, False):
-        x = Rig(g, K, nt, config=STEP_CONFIG, G=G)
+        x = AdvRig(g, K, nt, config=STEP_CONFIG, G=G)
         x.vc.set("RefLayerThickness", x.ref)
         if attach:
             x.tend.attach_vert_adv(x.va[2])
@@ -382,7 +302,7 @@ def test_two_part_decomposition_matches_one_part(mesh, K):
     g, nt = named_mesh(mesh), 2
 
     def run(nparts, rank):
-        x = Rig(g, K, nt, nparts=nparts, rank=rank)
+        x = AdvRig(g, K, nt, nparts=nparts, rank=rank)
         x.vc.set("RefLayerThickness", x.ref)
         d, tt, ut = x.dev(x.d), x.dev(x.tr * 1.0e-3), x.dev(x.u * 1.0e-2)
         h, tr, u = x.dev(x.h), x.dev(x.tr), x.dev(x.u)
@@ -408,7 +328,7 @@ def test_two_part_decomposition_matches_one_part(mesh, K):
 
 def test_refusals():
     g = named_mesh("hex24x20")
-    x, y = Rig(g, 16, 2, config={}), Rig(g, 15, 2, config={})
+    x, y = AdvRig(g, 16, 2, config={}), AdvRig(g, 15, 2, config={})
     with pytest.raises(oa.OmegaAmdError, match="TracerFluxOrder = 3"):
         oa.VertAdv(x.mesh, x.vc, 3)
     with pytest.raises(oa.OmegaAmdError, match="TracerFluxOrder = 0"):

@@ -10,9 +10,9 @@ import pytest
 import omega_amd as oa
 from tests import vert_adv_reference as VR
 from tests import vert_fixtures as F
+from tests.column_reference import RHO0
 from tests.meshes import named_mesh
-from tests.test_vert_adv_gpu import RHO0, Rig
-from tests.vert_adv_fixtures import assert_both_signs
+from tests.vert_adv_fixtures import AdvRig, assert_both_signs
 from tests.vert_fixtures import same
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +44,7 @@ def test_sweep_covers_every_tile_of_the_column_launch():
 
 @pytest.mark.parametrize("K", K_SWEEP)
 def test_column_launch_bit_exact_at_every_tile(K):
-    x = Rig(named_mesh(MESH), K, 1)
+    x = AdvRig(named_mesh(MESH), K, 1)
     # the fixture still holds every kind of column at this K: full, one layer, KMin > 0, land
     lo, hi = x.lo[: x.n_all], x.hi[: x.n_all]
     ok = (lo >= 0) & (lo <= hi) & (hi < K)

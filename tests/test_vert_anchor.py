@@ -16,9 +16,9 @@ import pytest
 from tests import column_reference as CR
 from tests import tridiag_reference as TR
 from tests import vert_mix_reference as MR
+from tests.column_reference import RHO0
 
 U = 2.0 ** -53
-RHO0 = 1026.0
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE = os.environ.get("OMEGA_REFERENCE_ROOT", os.path.join(os.path.dirname(ROOT), "reference"))
 REFERENCE_EOS = os.path.join(REFERENCE, "components", "omega", "src", "ocn", "Eos.h")

@@ -7,9 +7,9 @@ import pytest
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
 from tests import column_reference as R
+from tests.column_reference import RHO0
 
 G = R.GRAVITY
-RHO0 = 1026.0
 ATOL = 1.0e-10  # VertCoordTest.cpp's tolerance
 
 

@@ -8,8 +8,8 @@ import pytest
 import omega_amd as oa
 from omega_amd.meshgen import planar_hex
 from tests import vert_mix_reference as R
+from tests.column_reference import RHO0
 
-RHO0 = 1026.0
 G = R.GRAVITY
 
 

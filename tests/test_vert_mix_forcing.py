@@ -6,9 +6,9 @@ import pytest
 
 from tests import vert_mix_forcing_reference as F
 from tests import vert_mix_reference as R
+from tests.column_reference import RHO0
 
 EPS = np.finfo(np.float64).eps
-RHO0 = 1026.0
 DT = 1800.0
 
 

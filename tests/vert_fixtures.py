@@ -7,8 +7,9 @@ import numpy as np
 import omega_amd as oa
 from tests import column_reference as CR
 from tests import vert_mix_reference as MR
+from tests.column_reference import RHO0
+from tests.rank_rig import RankRig
 
-RHO0 = 1026.0
 VC_OUT = ("PressureInterface", "PressureMid", "ZInterface", "ZMid", "GeopotentialMid", "LayerThicknessTarget")
 EOS_OUT = ("SpecVol", "SpecVolDisplaced")
 MIX_OUT = ("VertDiff", "VertVisc", "BruntVaisalaFreqSq")
@@ -98,12 +99,18 @@ def pcr_levels(n):
     return lev
 
 
+def systems_launch(K):
+    """what launchMix and launchBolusVelocity share: (columns per workgroup, the lanes they occupy, the lanes of the
+    workgroup) -- as many whole columns as 256 lanes hold, a longer column alone, whole wavefronts"""
+    sys = MIX_LANES // K if K <= MIX_LANES else 1
+    rows = sys * K
+    return sys, rows, (rows + 63) // 64 * 64
+
+
 def mix_launch(K, nrhs):
     """launchMix (MixShape, mixChunk): columns per workgroup, lanes, right-hand sides per pass and its LDS cap, passes,
     dynamic LDS bytes"""
-    sys = MIX_LANES // K if K <= MIX_LANES else 1
-    rows = sys * K
-    threads = (rows + 63) // 64 * 64
+    sys, rows, threads = systems_launch(K)
     cap = (LDS_BYTES // 8 // rows - 4) // 2
     chunk = 1
     for o in MIX_CHUNKS:
@@ -200,30 +207,17 @@ def same(got, want, name):
 # ---------------------------------------------------------------------------------------------------------------------
 # rigs
 # ---------------------------------------------------------------------------------------------------------------------
-class Col:
+class Col(RankRig):
     """One rank's objects (VertCoord, Eos, OceanState, Tracers) with the global inputs in local order."""
 
     def __init__(self, g, K, eos_kind, nparts=1, rank=0, seed=7, weights="Uniform"):
-        self.K, self.eos_kind = K, eos_kind
-        self.gm = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm, nparts, rank, 3)
-        self.mesh = oa.HorzMesh(self.decomp, K)
+        super().__init__(g, K, nparts, rank)
+        self.eos_kind = eos_kind
         m = self.mesh
-        self.n_all, self.n_size = m.NCellsAll, m.NCellsSize
-        self.cid = self.decomp.get_array("CellID")
-        G = col_inputs(g, K, seed)
-        self.G = G
-        rows = self.cid[: self.n_all] - 1
-
-        def loc(x):
-            out = np.zeros((self.n_size,) + x.shape[1:])
-            out[: self.n_all] = x[rows]
-            return out
-
-        self.h = loc(G["h"])
-        self.tr = np.stack([loc(t) for t in G["tr"]])
-        self.ps, self.tidal, self.sal, self.bot, self.ref = (loc(G[k]) for k in ("ps", "tidal", "sal", "bot", "ref"))
-        self.vc = oa.VertCoord(m, K, RHO0, weights, G["min_level"], G["max_level"], decomp=self.decomp)
+        G = self.G = col_inputs(g, K, seed)
+        self.h, self.tr = self.cells(G["h"]), self.cells(G["tr"])
+        self.ps, self.tidal, self.sal, self.bot, self.ref = (self.cells(G[k]) for k in ("ps", "tidal", "sal", "bot", "ref"))
+        self.layers(G["min_level"], G["max_level"], weights=weights)
         self.eos = oa.Eos(m, K, eos_kind)
         self.state = oa.OceanState(m, None, K, 2)
         self.tracers = oa.Tracers(m, None, K, COL_NT, 2)
@@ -231,7 +225,6 @@ class Col:
         self.tracers.copy_to_device(self.tr, 0)
         self.vc.set("BottomDepth", self.bot)
         self.vc.set("RefLayerThickness", self.ref)
-        self.lo, self.hi = CR.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
         self.poison()
 
     def poison(self):
@@ -277,7 +270,7 @@ class Col:
         return st
 
 
-class Mix:
+class Mix(RankRig):
     """One rank's VertCoord, Eos, OceanState, Tracers and VertMix, with the global inputs in local order and the
     column pass (with SpecVolDisplaced at KDisp = 1) already run.  ragged: the layer ranges cycle through
     ragged_depths(K) in local cell order instead of being drawn at random.  column_pass = False skips the column pass
@@ -285,31 +278,16 @@ class Mix:
 
     def __init__(self, g, K, eos_kind="teos10", nparts=1, rank=0, seed=7, full=False, ntracers=MIX_NT, ragged=False,
                  column_pass=True, **cfg):
-        self.K, self.nt = K, ntracers
-        self.gm = oa.GlobalMesh(g)
-        self.decomp = oa.Decomp(self.gm, nparts, rank, 3)
-        self.mesh = m = oa.HorzMesh(self.decomp, K)
-        self.n_own, self.n_all, self.n_size = m.NCellsOwned, m.NCellsAll, m.NCellsSize
-        self.e_own, self.e_all, self.e_size = m.NEdgesOwned, m.NEdgesAll, m.NEdgesSize
-        self.cid = self.decomp.get_array("CellID")
-        self.eid = self.decomp.get_array("EdgeID")
+        super().__init__(g, K, nparts, rank)
+        self.nt = ntracers
+        m = self.mesh
         G = self.G = mix_inputs(g, K, seed, full, ntracers)
-        crow, erow = self.cid[: self.n_all] - 1, self.eid[: self.e_all] - 1
         if ragged:
             mn, mx = ragged_levels_local(np.random.default_rng(seed + 1), self.n_all, K)
-            G["min_level"][crow], G["max_level"][crow] = mn, mx
-
-        def loc(x, rows, n_size, fill=0.0):
-            out = np.full((n_size,) + x.shape[1:], fill)
-            out[: len(rows)] = x[rows]
-            return out
-
-        self.h = loc(G["h"], crow, self.n_size)
-        self.tr = np.stack([loc(t, crow, self.n_size) for t in G["tr"]])
-        self.un = loc(G["un"], erow, self.e_size)
-        self.ut = loc(G["ut"], erow, self.e_size)
-        self.vc = oa.VertCoord(m, K, RHO0, "Uniform", G["min_level"], G["max_level"], decomp=self.decomp)
-        self.lo, self.hi = CR.local_layer_ranges(self.cid, G["min_level"], G["max_level"], self.n_all, self.n_size, K)
+            G["min_level"][self.crow], G["max_level"][self.crow] = mn, mx
+        self.h, self.tr = self.cells(G["h"]), self.cells(G["tr"])
+        self.un, self.ut = self.edges(G["un"]), self.edges(G["ut"])
+        self.layers(G["min_level"], G["max_level"])
         self.eos = oa.Eos(m, K, eos_kind)
         self.state = oa.OceanState(m, None, K, 2)
         self.tracers = oa.Tracers(m, None, K, ntracers, 2)
@@ -356,7 +334,7 @@ class Mix:
 
     def seeded_velocity(self):
         """u at level 0 with NaN outside each owned edge's range and on halo / sentinel rows; level 1 distinct"""
-        lo, hi = self.vc.get("MinLayerEdgeBot"), self.vc.get("MaxLayerEdgeTop")
+        lo, hi = self.lo_e, self.hi_e
         u0 = np.full_like(self.un, np.nan)
         for e in range(self.e_own):
             if 0 <= lo[e] <= hi[e] < self.K:
