@@ -851,6 +851,59 @@ int omg_gm_copy_to_host(const omg_gm *g, const char *name, double *host, size_t 
  * arrays of the two objects equal.  The stepper keeps a pointer to g: detach before destroying it. */
 int omg_stepper_attach_gm(omg_stepper *st, omg_gm *g);
 
+/* ---- Redi: isoneutral diffusion of the tracers, the partner of GentMcWilliams -- the small-slope tensor with the
+ * isopycnal slope relative to the layers on the edge interfaces, its two cross terms explicit on the tracer tendency and
+ * its slope-squared part a vertical diffusivity for the implicit tracer solve of VertMix (the reference has no code for
+ * it).  Numerical contract: omega_amd/csrc/Redi.h.  Arrays are level-indexed device arrays as above.  Every call is
+ * asynchronous on stream and allocates nothing.  The object keeps pointers to v and e: destroy it before them. ---- */
+typedef struct omg_redi omg_redi;
+/* max_tracers: the most tracers omg_redi_add_tracer_tend takes (>= 1); kappa: the diffusivity every entry of "Kappa"
+ * starts with (m^2 s^-1, the class's default is 600, >= 0 and finite); slope_max: the bound of |slope| (default 0.01,
+ * finite and > 0); n2_floor: the least N^2 the slope is divided by (s^-2, default 1e-10, finite and > 0).  Fails also
+ * for a host-only mesh, a VertCoord or Eos of another mesh or layer count and more than 1024 layers */
+int omg_redi_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, int max_tracers, double kappa, double slope_max,
+                    double n2_floor, omg_redi **out);
+int omg_redi_destroy(omg_redi *r);
+/* the fused column pass exactly as omg_gm_update_column runs it, with this object's SurfacePressure / TidalPotential /
+ * SelfAttractionLoading */
+int omg_redi_update_column(omg_redi *r, const double *layer_thickness_dev, const double *tracers_dev, int ntracers,
+                           void *stream);
+/* "SlopeInterface" on every edge's level range (row K: the interface at the top of layer K; 0 at the top of the range),
+ * from the Eos's SpecVol / SpecVolDisplaced and the VertCoord's ZMid as they stand.  layer_thickness_dev is required
+ * and not read (the slope does not depend on it).  One launch */
+int omg_redi_compute_slope(omg_redi *r, const double *layer_thickness_dev, void *stream);
+/* the same from the caller's [NCellsSize][pitch] arrays */
+int omg_redi_compute_slope_arrays(omg_redi *r, const double *layer_thickness_dev, const double *spec_vol_dev,
+                                  const double *spec_vol_displaced_dev, const double *z_mid_dev, void *stream);
+/* tracer_tend_dev [ntracers][NCellsSize][pitch] += the divergence of the horizontal isoneutral flux and of the vertical
+ * cross flux of tracers_dev [ntracers][NCellsSize][pitch], on every cell's layer range, from "SlopeInterface" and "Kappa"
+ * as they stand; z_mid_dev NULL: the VertCoord's ZMid.  Fails for ntracers outside 1 .. max_tracers.  One launch */
+int omg_redi_add_tracer_tend(omg_redi *r, double *tracer_tend_dev, const double *layer_thickness_dev,
+                             const double *tracers_dev, int ntracers, const double *z_mid_dev, void *stream);
+/* "VertDiffusivity" (Kappa times the squared slope, averaged to the cell interfaces); vert_diff_dev [NCellsSize][pitch]
+ * += VertDiffusivity there (NULL: no term).  One launch */
+int omg_redi_compute_vert_diffusivity(omg_redi *r, double *vert_diff_dev, void *stream);
+/* kernel launches the three compute calls have issued on this object so far */
+int omg_redi_launch_count(const omg_redi *r, int64_t *n);
+/* "Kappa" ([NEdgesSize], kappa at creation), "SlopeInterface" ([NEdgesSize][K], zero at creation), "VertDiffusivity"
+ * ([NCellsSize][K], zero at creation), "SurfacePressure", "TidalPotential", "SelfAttractionLoading" ([NCellsSize], zero
+ * at creation) */
+int omg_redi_device_ptr(const omg_redi *r, const char *name, double **dev, size_t *n);
+int omg_redi_copy_to_device(omg_redi *r, const char *name, const double *host, size_t n);
+int omg_redi_copy_to_host(const omg_redi *r, const char *name, double *host, size_t n);
+/* VertMixStep::attachRedi (omega_amd/csrc/VertMixStep.h): omg_vertmix_step_apply adds "VertDiffusivity", from the slopes
+ * r last computed, to the VertMix's VertDiff between the coefficients and the tracer solve (r NULL: detach).  Fails for
+ * an r of another mesh, layer count, VertCoord or Eos.  ms keeps a pointer to r: detach before destroying it. */
+int omg_vertmixstep_attach_redi(omg_vertmix_step *ms, omg_redi *r);
+/* SplitExplicitStepper::attachRedi (omega_amd/csrc/SplitExplicitStepper.h): every step of a "Split-Explicit" stepper
+ * computes the slopes of the current level (after the column pass: the GentMcWilliams's if one is attached, else
+ * omg_redi_update_column) and adds omg_redi_add_tracer_tend to the tracer tendency before the tracer update (r NULL:
+ * detach).  Fails for any other stepper type, an r of another mesh or layer count, max_tracers below the stepper's
+ * tracer count, fewer than 2 tracers, an r on another VertCoord or Eos than an attached GentMcWilliams's or
+ * PressureGrad's, a stepper without omg_stepper_attach_vert_mix and one whose VertMixStep does not have this r attached
+ * (omg_stepper_do_step checks again).  The stepper keeps a pointer to r: detach before destroying it. */
+int omg_stepper_attach_redi(omg_stepper *st, omg_redi *r);
+
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at
  * dev + i * row_pitch (row_pitch 0: nrow).  x holds the right-hand side on entry and the solution on return; only

@@ -2,7 +2,7 @@
 
 Thin ctypes plumbing used by tests/, bench.py and __graft_entry__.py: the product is the
 C++/HIP library under omega_amd/csrc (classes named after Omega's own: Decomp, Halo,
-HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, VertMix, VertMixStep, PressureGrad, VertAdv, GentMcWilliams, Tendencies,
+HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, VertMix, VertMixStep, PressureGrad, VertAdv, GentMcWilliams, Redi, Tendencies,
 TimeStepper).  There is no
 Python or CPU implementation of the hot path here: if the shared library is missing,
 importing the binding raises, and without a HIP device every device call fails.
@@ -1186,6 +1186,12 @@ class VertMixStep(_Handle, _NamedArrays):
         _chk(lib().omg_vertmix_step_set_boundary(self.h, C.c_double(bottom_drag_coeff), C.c_double(rayleigh_drag_coeff),
                                                  int(use_wind_stress)))
 
+    def attach_redi(self, redi: "Redi | None"):
+        """VertMixStep::attachRedi: apply adds `redi`'s VertDiffusivity (from the slopes it last computed) to the
+        VertMix's VertDiff before the tracer solve; None detaches."""
+        _chk(lib().omg_vertmixstep_attach_redi(self.h, redi.h if redi is not None else None))
+        self._redi = redi  # the library keeps a pointer to it
+
     def apply(self, layer_thickness: int, normal_velocity: int, tracers: int, dt: float, stream=None):
         """On device addresses: thickness [NCellsSize][pitch]; velocity [NEdgesSize][pitch] and tracers
         [NT][NCellsSize][pitch] are mixed in place, asynchronously on `stream`."""
@@ -1515,6 +1521,85 @@ class GentMcWilliams(_Handle, _NamedArrays):
         return (self.mesh.NEdgesSize, self.K) if s == "EK" else (self.mesh.NEdgesSize,)
 
 
+REDI_ARRAYS = {"Kappa": "E", "SlopeInterface": "EK", "VertDiffusivity": "CK", "SurfacePressure": "C",
+               "TidalPotential": "C", "SelfAttractionLoading": "C"}
+
+
+class Redi(_Handle, _NamedArrays):
+    """Redi (omega_amd/csrc/Redi.h): isoneutral diffusion of the tracers -- the isopycnal slope relative to the layers on
+    the edge interfaces from the stratification of `vcoord` / `eos` (compute_slope), the explicit cross terms of the
+    small-slope tensor on a tracer tendency (add_tracer_tend) and its slope-squared part as a vertical diffusivity for
+    VertMix's implicit solve (compute_vert_diffusivity).  Level-indexed inputs are numpy arrays [rows][K] or device
+    addresses of [rows][level_pitch(K)] doubles; the results are the object's SlopeInterface and VertDiffusivity
+    (`get`); `tracer_tend` and `vert_diff` are accumulated in place: a device address (asynchronous on `stream`) or a
+    numpy array (staged, computed, returned)."""
+    _destroy, _arrays = "omg_redi_destroy", "omg_redi"
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", max_tracers: int,
+                 kappa: float = 600.0, slope_max: float = 0.01, n2_floor: float = 1.0e-10):
+        self.mesh, self.vcoord, self.eos, self.max_tracers = mesh, vcoord, eos, int(max_tracers)
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self._create("omg_redi_create", mesh.h, vcoord.h if vcoord is not None else None,
+                     eos.h if eos is not None else None, int(max_tracers), C.c_double(kappa), C.c_double(slope_max),
+                     C.c_double(n2_floor))
+
+    def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
+        """The fused column pass with the displaced volume (kdisp = 1) from raw arrays, as
+        GentMcWilliams.update_column, with this object's SurfacePressure / TidalPotential / SelfAttractionLoading."""
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
+        _chk(lib().omg_redi_update_column(self.h, h, t, int(ntracers), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def compute_slope(self, layer_thickness, spec_vol=None, spec_vol_displaced=None, z_mid=None, stream=None):
+        """SlopeInterface from the three given cell arrays (the array form; all three or none), or from the Eos's and
+        the VertCoord's arrays as they stand."""
+        given = [x is not None for x in (spec_vol, spec_vol_displaced, z_mid)]
+        assert all(given) or not any(given), "give SpecVol, SpecVolDisplaced and ZMid, or none of them"
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        if all(given):
+            _chk(lib().omg_redi_compute_slope_arrays(self.h, h, _level_dev(spec_vol, n, self.K, keep),
+                                                     _level_dev(spec_vol_displaced, n, self.K, keep),
+                                                     _level_dev(z_mid, n, self.K, keep), _sh(stream)))
+        else:
+            _chk(lib().omg_redi_compute_slope(self.h, h, _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def add_tracer_tend(self, tracer_tend, layer_thickness, tracers, ntracers: int, z_mid=None, stream=None):
+        """tracer_tend [ntracers][NCellsSize][K] += the isoneutral cross terms of `tracers` on the slopes as they stand;
+        z_mid None: the VertCoord's ZMid."""
+        keep, n, nt = [], self.mesh.NCellsSize, max(int(ntracers), 0)
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        t = _stage_levels(tracers, (nt, n), self.K, keep)[0]
+        z = None if z_mid is None else _level_dev(z_mid, n, self.K, keep)
+        p, buf = _stage_levels(tracer_tend, (nt, n), self.K)
+        _chk(lib().omg_redi_add_tracer_tend(self.h, p, h, t, int(ntracers), z, _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def compute_vert_diffusivity(self, vert_diff=None, stream=None):
+        """VertDiffusivity from the slopes as they stand; vert_diff [NCellsSize][K] += VertDiffusivity if it is given."""
+        p, buf = (None, None) if vert_diff is None else _stage_levels(vert_diff, (self.mesh.NCellsSize,), self.K)
+        _chk(lib().omg_redi_compute_vert_diffusivity(self.h, p, _sh(stream)))
+        return _read_back(buf, self.K, stream)
+
+    def launch_count(self) -> int:
+        """kernel launches the three compute calls have issued on this object so far"""
+        n = C.c_int64(0)
+        _chk(lib().omg_redi_launch_count(self.h, C.byref(n)))
+        return n.value
+
+    def _shape(self, name):
+        s = REDI_ARRAYS.get(name, "C")  # (an unknown name: the library says so)
+        m = self.mesh
+        return {"C": (m.NCellsSize,), "E": (m.NEdgesSize,), "EK": (m.NEdgesSize, self.K), "CK": (m.NCellsSize, self.K)}[s]
+
+
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""
@@ -1703,6 +1788,14 @@ class TimeStepper(_Handle):
         or Eos than its (the caller keeps the forcing arrays of the two equal)."""
         _chk(lib().omg_stepper_attach_gm(self.h, gm.h if gm is not None else None))
         self._gent_mcwilliams = gm  # the library keeps a pointer to it
+
+    def attach_redi(self, redi: "Redi | None"):
+        """SplitExplicitStepper::attachRedi: every step computes the isopycnal slopes of the current level and adds the
+        isoneutral cross terms to the tracer tendency before the tracer update (None detaches); raises on any other
+        kind, for another mesh or layer count, too few tracers, another VertCoord or Eos than an attached
+        GentMcWilliams's or PressureGrad's, and unless a VertMixStep with this same `redi` attached is attached."""
+        _chk(lib().omg_stepper_attach_redi(self.h, redi.h if redi is not None else None))
+        self._redi = redi  # the library keeps a pointer to it
 
     def set_fused_transport(self, on: bool):
         """SplitExplicitStepper::UseFusedTransport (default on): the step's thickness and tracer tendencies through

@@ -47,7 +47,8 @@
 //  - The layer thickness h stands for the metric dz (in the second difference and in u* = -dPsi/dz), as in VertMix.
 //  - The vertical density derivative of the z-correction (RhoZ) is in-situ; only N^2 is locally referenced (the
 //    displaced volume of the layer above).
-//  - Redi (isopycnal) diffusion of the tracers is not part of this.
+//  - Redi (isopycnal) diffusion of the tracers is not part of this class: it is Redi.h, which forms the slope from the
+//    same GradRhoZ and N2E.
 //
 // Algorithmic traffic: 32 B per cell-level (four cell arrays, each row ideally fetched once) + 16 B per edge-level
 // (BolusVelocity and StreamFunction written) + 16 B per edge-level with Transport (read and written): ~ 128 B per

@@ -1,6 +1,7 @@
 // SplitExplicitStepper.cpp -- see SplitExplicitStepper.h.
 #include "SplitExplicitStepper.h"
 #include "PressureGrad.h"
+#include "VertMixStep.h"
 
 namespace OMEGA {
 
@@ -73,12 +74,46 @@ void SplitExplicitStepper::attachGentMcWilliams(GentMcWilliams *G) {
    GM = G;
 }
 
+void SplitExplicitStepper::requireRediFits(const Redi *R, const char *Where) const {
+   const std::string W = std::string(Where) + ": ";
+   OMEGA_REQUIRE(R->Mesh == Mesh && R->NVertLayers == Tend->LayerThicknessTend.Ext[1],
+                 W + "the Redi was built for another mesh or layer count");
+   OMEGA_REQUIRE(Tend->NTracers >= 2, W + "the stepper has " + std::to_string(Tend->NTracers) +
+                                          " tracers: the column pass needs temperature and salinity (tracers 0 and 1)");
+   OMEGA_REQUIRE(R->MaxTracers >= Tend->NTracers, W + "the Redi has MaxTracers = " + std::to_string(R->MaxTracers) +
+                                                      ", below the stepper's " + std::to_string(Tend->NTracers) + " tracers");
+   if (GM) // one column pass, on one set of column fields
+      OMEGA_REQUIRE(R->VCoord == GM->VCoord && R->EqState == GM->EqState,
+                    W + "the Redi and the attached GentMcWilliams are on different VertCoord or Eos objects: the step "
+                        "runs one column pass for both");
+   if (const PressureGrad *P = Tend->pressureGrad())
+      OMEGA_REQUIRE(R->VCoord == P->VCoord && R->EqState == P->EqState,
+                    W + "the Redi and the PressureGrad attached to the Tendencies are on different VertCoord or Eos "
+                        "objects: both run the column pass, on one set of column fields");
+   OMEGA_REQUIRE(VMixStep != nullptr, W + "the stepper has no VertMixStep attached: without the implicit S.S term of the "
+                                          "vertical mixing the explicit part of the isoneutral tensor is indefinite");
+   OMEGA_REQUIRE(VMixStep->redi() == R, W + "the stepper's VertMixStep does not have this Redi attached "
+                                            "(VertMixStep::attachRedi): the implicit S.S term would be missing");
+}
+
+void SplitExplicitStepper::attachRedi(Redi *R) {
+   if (R == nullptr) {
+      RediTerm = nullptr;
+      return;
+   }
+   OMEGA_REQUIRE(Tend && Mesh && Trc, "SplitExplicitStepper::attachRedi: attachData first");
+   requireRediFits(R, "SplitExplicitStepper::attachRedi");
+   RediTerm = R;
+}
+
 void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    OMEGA_REQUIRE(Btr != nullptr, "Split-Explicit doStep: no BarotropicMode is attached: attachBarotropic first");
    if (Mono)
       requireMonotoneAdvFits(Mono, "Split-Explicit doStep");
    if (GM)
       requireGentMcWilliamsFits(GM, "Split-Explicit doStep");
+   if (RediTerm)
+      requireRediFits(RediTerm, "Split-Explicit doStep");
    requireHealthyWire();
    const int CurLevel = 0, NextLevel = 1;
    const StepArrays A = stepArrays("Split-Explicit", State);
@@ -100,12 +135,17 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
       GM->updateColumn(A.CurH, A.CurTr, S);
       GM->computeBolusVelocity(A.CurH, A.NextU, S);
    }
+   if (RediTerm) { // the isopycnal slopes of the same stratification: the column pass is GM's where it has just run
+      if (!GM)
+         RediTerm->updateColumn(A.CurH, A.CurTr, S);
+      RediTerm->computeSlope(A.CurH, S);
+   }
    // (with tracers and their hyperdiffusion term off the tracer update rides in the first transport launch, which loses a
    // wave to it: measured no faster than the three calls, DESIGN.md section 4.9, so those run)
    const bool Fold = UseFusedTransport && FoldUpdates && (Tend->NTracers <= 0 || Tend->Params.TracerHyperDiffTendencyEnable);
-   if (Mono) {
+   if (Mono || RediTerm) {
       // the limiter needs h^{n+1} and the tracer tendency's other terms: both tendencies, the thickness update, the
-      // limited flux divergence onto TracerTend, the tracer update
+      // limited flux divergence onto TracerTend, the tracer update; the isoneutral term joins TracerTend the same way
       if (UseFusedTransport)
          Tend->computeTransportTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
       else {
@@ -113,8 +153,10 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
          Tend->computeTracerTendencies(State, AuxState, A.CurTr, CurLevel, NextLevel, S);
       }
       updateThicknessByTend(State, NextLevel, State, CurLevel, Dt, S);
-      if (Tend->NTracers > 0)
+      if (Mono && Tend->NTracers > 0)
          Mono->addTracerTend(Tend->TracerTend, A.CurH, A.NextH, A.NextU, A.CurTr, Tend->NTracers, Dt, S);
+      if (RediTerm)
+         RediTerm->addTracerTend(Tend->TracerTend, A.CurH, A.CurTr, Tend->NTracers, S);
       updateTracersByTend(A.NextTr, A.CurTr, State, NextLevel, State, CurLevel, Dt, S);
    } else if (Fold) {
       // both tendencies and both updates in the transport kernels; the tendencies are stored as the calls below do

@@ -69,6 +69,24 @@
 // (step 1 of the next step refreshes them before anything reads them).  With nothing attached the step, its launch
 // count and its bits are what they were.
 //
+// With a Redi attached (attachRedi; Redi.h) the tracers are also diffused along the isopycnals of h^{n}, phi^{n}.  After
+// step 5 (and 5b) the step gains
+//   5c. the column pass, then R->computeSlope(h[Cur]): with a GentMcWilliams attached the pass is step 5b's, run once
+//       (the two objects share one VertCoord and one Eos, or the attachment is refused); without one it is
+//       R->updateColumn(h[Cur], CurTracers)
+// and steps 6-7 take the unfolded sequence of the MonotoneAdv, whatever FoldUpdates says:
+//        Tend->computeTransportTendencies(State, AuxState, CurTracers, Cur, Next)
+//            (with UseFusedTransport off: computeThicknessTendencies and computeTracerTendencies with these arguments)
+//        updateThicknessByTend(State, Next, State, Cur, Dt)
+//        M->addTracerTend(...) as above, if a MonotoneAdv is attached
+//        R->addTracerTend(TracerTend, h[Cur], CurTracers, NTracers)
+//        updateTracersByTend(NextTracers, CurTracers, State, Next, State, Cur, Dt)
+// The explicit part of the tensor alone is indefinite: its S.S part is implicit, in the vertical mixing of step 9.  So
+// the stepper must have a VertMixStep attached (attachVertMix) and that VertMixStep this same Redi (VertMixStep::
+// attachRedi): it then adds VertDiffusivity, from the slopes of step 5c, to VertMix's VertDiff before the tracer solve
+// of the new level.  Redi moves tracers only: the velocity and the thickness of the step are those of the unattached
+// step bit for bit.  With nothing attached the step, its launch count and its bits are what they were.
+//
 // What a step carries to the next one besides the state: nothing of the BarotropicMode -- step 2 writes BtrThickEdge and
 // BtrVelocity on every edge and SSH on every column with layers, and steps 3-4 the rest, before anything reads them --
 // with one exception: SSH of a column that is dry by its layer range but still a cell of the mesh.  computeSSH leaves it
@@ -84,6 +102,7 @@
 #include "BarotropicMode.h"
 #include "GentMcWilliams.h"
 #include "MonotoneAdv.h"
+#include "Redi.h"
 #include "TimeStepper.h"
 
 namespace OMEGA {
@@ -128,6 +147,14 @@ class SplitExplicitStepper : public TimeStepper {
    void attachGentMcWilliams(GentMcWilliams *G);
    GentMcWilliams *gentMcWilliams() const { return GM; }
 
+   /// Opt-in (after attachData): step 5c and the Redi term of steps 6-7 above through R; nullptr detaches.  Refuses
+   /// (OmegaError) a Redi of another mesh or layer count, one with MaxTracers below the stepper's tracer count, a stepper
+   /// with fewer than 2 tracers, a Redi on another VertCoord or Eos than an attached GentMcWilliams's or the
+   /// PressureGrad's of the Tendencies, a stepper without a VertMixStep (vertMix() is null) and one whose VertMixStep
+   /// does not have this same Redi attached (all checked again in every step).  The stepper keeps the pointer.
+   void attachRedi(Redi *R);
+   Redi *redi() const { return RediTerm; }
+
    void doStep(OceanState *State, hipStream_t S) override;
    using TimeStepper::doStep;
 
@@ -136,6 +163,9 @@ class SplitExplicitStepper : public TimeStepper {
    int NSub            = 0;
    MonotoneAdv *Mono   = nullptr;
    GentMcWilliams *GM  = nullptr;
+   Redi *RediTerm      = nullptr;
+   /// what attachRedi refuses and doStep checks again (the other attachments may have changed since)
+   void requireRediFits(const Redi *R, const char *Where) const;
    /// what attachGentMcWilliams refuses and doStep checks again (a PressureGrad may have been attached since)
    void requireGentMcWilliamsFits(const GentMcWilliams *G, const char *Where) const;
    /// what attachMonotoneAdv refuses and doStep checks again (the options may have changed since)

@@ -32,6 +32,16 @@ VertMixStep::VertMixStep(const std::string &Name_, const HorzMesh *Mesh_, VertMi
    SelfAttractionLoading = Array1DReal("SelfAttractionLoading", Mesh->NCellsSize);
 }
 
+void VertMixStep::attachRedi(Redi *R) {
+   if (R != nullptr) {
+      OMEGA_REQUIRE(R->Mesh == Mesh && R->NVertLayers == NVertLayers,
+                    "VertMixStep::attachRedi: the Redi was built for another mesh or layer count");
+      OMEGA_REQUIRE(R->VCoord == VCoord && R->EqState == EqState,
+                    "VertMixStep::attachRedi: the Redi is on a different VertCoord or Eos than this VertMixStep");
+   }
+   RediTerm = R;
+}
+
 void VertMixStep::apply(const Array2DReal &H, const Array2DReal &U, const Array3DReal &Tr, Real Dt, hipStream_t S) {
    requireLevelArray("VertMixStep", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
    requireLevelArray("VertMixStep", U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
@@ -43,6 +53,8 @@ void VertMixStep::apply(const Array2DReal &H, const Array2DReal &U, const Array3
    const TangentialReconOnEdge TangentialRecon(Mesh);
    TangentialRecon(TangentialVelocity, U, S);
    VMix->computeVertMix(U, TangentialVelocity, VMix->BruntVaisalaFreqSq, S);
+   if (RediTerm) // the S.S part of the isoneutral tensor joins the implicit tracer solve
+      RediTerm->computeVertDiffusivity(VMix->VertDiff, S);
    VMix->applyTracerVertMix(H, Tr, NTracers, Dt, SurfaceTracerFlux, S);
    VMix->applyVelocityVertMix(H, U, Dt, Boundary, UseWindStress ? NormalStressEdge : Array1DReal(), TangentialVelocity,
                               S);

@@ -9,9 +9,12 @@
 //   2. VMix->computeBruntVaisalaFreqSq(Eos, S)
 //   3. TangentialReconOnEdge: NormalVelocity -> TangentialVelocity (every edge < NEdgesAll)
 //   4. VMix->computeVertMix(NormalVelocity, TangentialVelocity, VMix->BruntVaisalaFreqSq, S)
+//  4b. with a Redi attached (attachRedi; Redi.h): R->computeVertDiffusivity(VMix->VertDiff, S) -- the S.S part of the
+//      isoneutral tensor, from the slopes the Redi last computed (inside a split-explicit step: those of level n, one set
+//      per step as MPAS-Ocean keeps them), added to the diffusivity step 4 has just written
 //   5. VMix->applyTracerVertMix(h, Tracers, NTracers, Dt, SurfaceTracerFlux, S)
 //   6. VMix->applyVelocityVertMix(h, u, Dt, Boundary, NormalStressEdge if UseWindStress, TangentialVelocity, S)
-// The result equals these six public calls made by hand, bit for bit.  Step 6 takes the bottom speed from the velocity
+// The result equals these six (with a Redi: seven) public calls made by hand, bit for bit.  Step 6 takes the bottom speed from the velocity
 // before the solve and the tangential velocity of step 3.
 //
 // One rank only as a stepper hook: the shear of step 4 and the tangential velocity read halo edges, so mixing inside a
@@ -25,6 +28,7 @@
 #include "Eos.h"
 #include "HorzMesh.h"
 #include "OceanState.h"
+#include "Redi.h"
 #include "VertCoord.h"
 #include "VertMix.h"
 
@@ -57,6 +61,11 @@ class VertMixStep : public Registry<VertMixStep> {
    /// thickness and normal velocity of State at time level Level, the tracers of Tracers at TrLevel
    void apply(const OceanState *State, int Level, const TracerStore *Tracers, int TrLevel, Real Dt, hipStream_t S);
 
+   /// Opt-in: step 4b above through R; nullptr detaches.  Refuses (OmegaError) a Redi of another mesh or layer count and
+   /// one on another VertCoord or Eos than this object's.  The object keeps the pointer.
+   void attachRedi(Redi *R);
+   Redi *redi() const { return RediTerm; }
+
    // ---- the reference's style of signature: on this object's `Stream` (default: the null stream)
    hipStream_t Stream = nullptr;
    void apply(const Array2DReal &LayerThickness, const Array2DReal &NormalVelocity, const Array3DReal &Tracers, Real Dt) {
@@ -68,6 +77,9 @@ class VertMixStep : public Registry<VertMixStep> {
    VertCoord *VCoord;
    Eos *EqState;
    std::string Name;
+
+ protected:
+   Redi *RediTerm = nullptr;
 };
 
 } // namespace OMEGA

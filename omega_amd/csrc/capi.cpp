@@ -22,6 +22,7 @@
 #include "TriDiagSolvers.h"
 #include "VertMix.h"
 #include "GentMcWilliams.h"
+#include "Redi.h"
 #include "PressureGrad.h"
 #include "MonotoneAdv.h"
 #include "VertAdv.h"
@@ -97,6 +98,9 @@ struct omg_monoadv {
 };
 struct omg_gm {
    std::unique_ptr<GentMcWilliams> G;
+};
+struct omg_redi {
+   std::unique_ptr<Redi> R;
 };
 
 static thread_local std::string LastError;
@@ -2168,6 +2172,93 @@ int omg_stepper_attach_gm(omg_stepper *st, omg_gm *g) {
    OMG_TRY
    OMG_ARG(st);
    splitExplicit(st, "attachGentMcWilliams")->attachGentMcWilliams(g ? g->G.get() : nullptr);
+   OMG_CATCH
+}
+
+// ---- Redi (Redi.h)
+int omg_redi_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, int max_tracers, double kappa, double slope_max,
+                    double n2_floor, omg_redi **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   newHandle(out, [&](omg_redi &H) {
+      H.R.reset(new Redi("Default", m->M.get(), v ? v->V.get() : nullptr, e ? e->E.get() : nullptr, max_tracers, kappa,
+                         slope_max, n2_floor));
+   });
+   OMG_CATCH
+}
+int omg_redi_destroy(omg_redi *r) {
+   delete r;
+   return 0;
+}
+int omg_redi_update_column(omg_redi *r, const double *layer_thickness, const double *tracers, int ntracers, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness && tracers && ntracers >= 2);
+   const int N = r->R->Mesh->NCellsSize, K = r->R->NVertLayers;
+   r->R->updateColumn(levelView(layer_thickness, N, K), tracerView(tracers, ntracers, N, K), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_redi_compute_slope(omg_redi *r, const double *layer_thickness, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness);
+   r->R->computeSlope(levelView(layer_thickness, r->R->Mesh->NCellsSize, r->R->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_redi_compute_slope_arrays(omg_redi *r, const double *layer_thickness, const double *spec_vol,
+                                  const double *spec_vol_displaced, const double *z_mid, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness && spec_vol && spec_vol_displaced && z_mid);
+   const int N = r->R->Mesh->NCellsSize, K = r->R->NVertLayers;
+   r->R->computeSlope(levelView(layer_thickness, N, K), levelView(spec_vol, N, K), levelView(spec_vol_displaced, N, K),
+                      levelView(z_mid, N, K), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_redi_add_tracer_tend(omg_redi *r, double *tracer_tend, const double *layer_thickness, const double *tracers,
+                             int ntracers, const double *z_mid, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && tracer_tend && layer_thickness && tracers);
+   const int N = r->R->Mesh->NCellsSize, K = r->R->NVertLayers;
+   const int NT = ntracers > 0 ? ntracers : 0; // (the class refuses the count; the views need an extent)
+   if (z_mid)
+      r->R->addTracerTend(tracerView(tracer_tend, NT, N, K), levelView(layer_thickness, N, K), tracerView(tracers, NT, N, K),
+                          ntracers, levelView(z_mid, N, K), (hipStream_t)stream);
+   else
+      r->R->addTracerTend(tracerView(tracer_tend, NT, N, K), levelView(layer_thickness, N, K), tracerView(tracers, NT, N, K),
+                          ntracers, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_redi_compute_vert_diffusivity(omg_redi *r, double *vert_diff, void *stream) {
+   OMG_TRY
+   OMG_ARG(r);
+   r->R->computeVertDiffusivity(vert_diff ? levelView(vert_diff, r->R->Mesh->NCellsSize, r->R->NVertLayers) : Array2DReal(),
+                                (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_redi_launch_count(const omg_redi *r, int64_t *n) {
+   OMG_TRY
+   OMG_ARG(r && n);
+   *n = r->R->LaunchCount;
+   OMG_CATCH
+}
+static ArrRef rediLookup(const Redi &R, const char *Name) {
+   return findNamed<ArrRef>({{"Kappa", arrRef(R.Kappa)},
+                             {"SlopeInterface", arrRef(R.SlopeInterface)},
+                             {"VertDiffusivity", arrRef(R.VertDiffusivity)},
+                             {"SurfacePressure", arrRef(R.SurfacePressure)},
+                             {"TidalPotential", arrRef(R.TidalPotential)},
+                             {"SelfAttractionLoading", arrRef(R.SelfAttractionLoading)}},
+                            Name, "Redi: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_redi_copy_to_host, omg_redi_copy_to_device, omg_redi_device_ptr, omg_redi, r, rediLookup(*r->R, name))
+int omg_stepper_attach_redi(omg_stepper *st, omg_redi *r) {
+   OMG_TRY
+   OMG_ARG(st);
+   splitExplicit(st, "attachRedi")->attachRedi(r ? r->R.get() : nullptr);
+   OMG_CATCH
+}
+int omg_vertmixstep_attach_redi(omg_vertmix_step *ms, omg_redi *r) {
+   OMG_TRY
+   OMG_ARG(ms);
+   ms->M->attachRedi(r ? r->R.get() : nullptr);
    OMG_CATCH
 }
 

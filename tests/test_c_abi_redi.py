@@ -1,0 +1,189 @@
+"""The C entry points of Redi (include/omega_amd.h: omg_redi_*, omg_stepper_attach_redi, omg_vertmixstep_attach_redi)
+called as a C program would: return codes and messages for null handles, bad parameters, a host-only mesh and unknown
+array names without a device; on a device the handle's lifetime, the named-array triple, the calls against the
+restatement and the two attachments."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import omega_amd as oa
+from omega_amd.meshgen import planar_hex
+from tests import redi_reference as RR
+
+SYMBOLS = ("omg_redi_create", "omg_redi_destroy", "omg_redi_update_column", "omg_redi_compute_slope",
+           "omg_redi_compute_slope_arrays", "omg_redi_add_tracer_tend", "omg_redi_compute_vert_diffusivity",
+           "omg_redi_device_ptr", "omg_redi_copy_to_device", "omg_redi_copy_to_host", "omg_redi_launch_count",
+           "omg_stepper_attach_redi", "omg_vertmixstep_attach_redi")
+NAMES = (b"Kappa", b"SlopeInterface", b"VertDiffusivity", b"SurfacePressure", b"TidalPotential", b"SelfAttractionLoading")
+D = C.c_double
+PDBL = C.POINTER(C.c_double)
+
+
+def _err():
+    L = oa.lib()
+    L.omg_last_error.restype = C.c_char_p
+    return L.omg_last_error().decode()
+
+
+def test_symbols_are_exported_and_declared():
+    L = oa.lib()
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "omega_amd.h")).read()
+    for s in SYMBOLS:
+        assert hasattr(L, s), s
+        assert f"int {s}(" in header, s
+
+
+def test_null_handles_bad_parameters_and_a_host_only_mesh_are_errors():
+    L = oa.lib()
+    buf = (C.c_double * 4)()
+    p = PDBL()
+    n = C.c_int64()
+    assert L.omg_redi_update_column(None, buf, buf, 2, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_compute_slope(None, buf, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_compute_slope_arrays(None, buf, buf, buf, buf, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_add_tracer_tend(None, buf, buf, buf, 2, None, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_compute_vert_diffusivity(None, None, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_launch_count(None, C.byref(n)) == 1 and "invalid argument" in _err()
+    for name in NAMES:
+        assert L.omg_redi_device_ptr(None, name, C.byref(p), None) == 1 and "invalid argument" in _err()
+        assert L.omg_redi_copy_to_host(None, name, buf, C.c_size_t(4)) == 1
+        assert L.omg_redi_copy_to_device(None, name, buf, C.c_size_t(4)) == 1
+    assert L.omg_stepper_attach_redi(None, None) == 1 and "invalid argument" in _err()
+    assert L.omg_vertmixstep_attach_redi(None, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_destroy(None) == 0
+    h = C.c_void_p()
+    args = (D(600.0), D(0.01), D(1.0e-10))
+    assert L.omg_redi_create(None, None, None, 2, *args, C.byref(h)) == 1 and "invalid argument" in _err() and not h
+    d = oa.Decomp(oa.GlobalMesh(planar_hex(8, 8, 1.0)), 1, 0, 3)
+    m = oa.HorzMesh(d, 4, host_only=True)
+    assert L.omg_redi_create(m.h, None, None, 2, *args, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_create(m.h, None, None, 2, *args, C.byref(h)) == 1 and "host-only" in _err() and not h
+    for kappa in (-1.0e-300, float("nan"), float("inf")):
+        assert L.omg_redi_create(m.h, None, None, 2, D(kappa), D(0.01), D(1.0e-10), C.byref(h)) == 1
+        assert "RediKappa" in _err() and not h
+    for v in (0.0, -1.0, float("nan"), float("inf")):
+        assert L.omg_redi_create(m.h, None, None, 2, D(600.0), D(v), D(1.0e-10), C.byref(h)) == 1 and "SlopeMax" in _err()
+        assert L.omg_redi_create(m.h, None, None, 2, D(600.0), D(0.01), D(v), C.byref(h)) == 1 and "N2Floor" in _err()
+        assert not h
+    for mt in (0, -3):
+        assert L.omg_redi_create(m.h, None, None, mt, *args, C.byref(h)) == 1 and "MaxTracers" in _err() and not h
+
+
+@pytest.mark.gpu
+def test_calls_on_a_device():
+    oa.device_init(0)
+    L = oa.lib()
+    K, nt, rho0 = 6, 2, 1026.0
+    d = oa.Decomp(oa.GlobalMesh(planar_hex(8, 8, 30.0e3)), 1, 0, 3)
+    m = oa.HorzMesh(d, K)
+    vc = oa.VertCoord(m, K, rho0, "Uniform", decomp=d)
+    eos = oa.Eos(m, K, "linear")
+    nc, ne = m.NCellsSize, m.NEdgesSize
+    h = C.c_void_p()
+    par = (D(250.0), D(0.02), D(1.0e-9))
+    assert L.omg_redi_create(m.h, None, eos.h, 2, *par, C.byref(h)) == 1 and "VertCoord is NULL" in _err() and not h
+    assert L.omg_redi_create(m.h, vc.h, None, 2, *par, C.byref(h)) == 1 and "Eos is NULL" in _err() and not h
+    m2 = oa.HorzMesh(d, K)
+    vc2, eos2 = oa.VertCoord(m2, K, rho0, "Uniform", decomp=d), oa.Eos(m2, K, "linear")
+    assert L.omg_redi_create(m.h, vc2.h, eos.h, 2, *par, C.byref(h)) == 1 and "another mesh" in _err() and not h
+    assert L.omg_redi_create(m.h, vc.h, eos2.h, 2, *par, C.byref(h)) == 1 and "another mesh" in _err() and not h
+    eos3 = oa.Eos(m, K - 1, "linear")
+    assert L.omg_redi_create(m.h, vc.h, eos3.h, 2, *par, C.byref(h)) == 1 and "layer counts" in _err() and not h
+    assert L.omg_redi_create(m.h, vc.h, eos.h, 2, *par, C.byref(h)) == 0 and h
+    # the named-array triple
+    p, cnt = PDBL(), C.c_size_t()
+    sizes = {b"Kappa": ne, b"SlopeInterface": ne * K, b"VertDiffusivity": nc * K, b"SurfacePressure": nc,
+             b"TidalPotential": nc, b"SelfAttractionLoading": nc}
+    for name in NAMES:
+        assert L.omg_redi_device_ptr(h, name, C.byref(p), C.byref(cnt)) == 0 and cnt.value == sizes[name] and p
+        out = np.ones(sizes[name])
+        pd = out.ctypes.data_as(PDBL)
+        assert L.omg_redi_copy_to_host(h, name, pd, C.c_size_t(out.size - 1)) == 1 and "too small" in _err()
+        assert L.omg_redi_copy_to_device(h, name, pd, C.c_size_t(out.size - 1)) == 1 and "size mismatch" in _err()
+        assert L.omg_redi_copy_to_host(h, name, pd, C.c_size_t(out.size)) == 0
+        assert np.all(out == (250.0 if name == b"Kappa" else 0.0))  # the initial values
+    assert L.omg_redi_device_ptr(h, b"NoSuchArray", C.byref(p), None) == 1
+    assert "Redi: no array named NoSuchArray" in _err()
+    assert L.omg_redi_copy_to_host(h, b"NoSuchArray", pd, C.c_size_t(4)) == 1
+    assert L.omg_redi_copy_to_device(h, b"NoSuchArray", pd, C.c_size_t(4)) == 1
+    rng = np.random.default_rng(5)
+    kappa = rng.uniform(100.0, 900.0, ne)
+    assert L.omg_redi_copy_to_device(h, b"Kappa", kappa.ctypes.data_as(PDBL), C.c_size_t(ne)) == 0
+    # the calls against the restatement (K = 6: compact rows, no padding)
+    assert oa.level_pitch(K) == K
+    hh = rng.uniform(5.0, 40.0, (nc, K))
+    tr = np.stack([rng.uniform(2.0, 20.0, (nc, K)), rng.uniform(33.0, 36.0, (nc, K))])
+    tt = rng.uniform(-1.0e-6, 1.0e-6, (nt, nc, K))
+    vd = rng.uniform(1.0e-5, 1.0e-3, (nc, K))
+    bh, btr, bt, bt2, bvd = (oa.DeviceBuffer(a) for a in (hh, tr, tt, tt, vd))
+    vp = C.c_void_p
+    launches = C.c_int64(-1)
+    assert L.omg_redi_launch_count(h, C.byref(launches)) == 0 and launches.value == 0
+    assert L.omg_redi_update_column(h, vp(bh.ptr), vp(btr.ptr), 1, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_update_column(h, None, vp(btr.ptr), nt, None) == 1
+    assert L.omg_redi_update_column(h, vp(bh.ptr), vp(btr.ptr), nt, None) == 0
+    assert L.omg_redi_compute_slope(h, None, None) == 1 and "invalid argument" in _err()
+    assert L.omg_redi_compute_slope(h, vp(bh.ptr), None) == 0
+    oa.device_synchronize()
+    sv, svd, zm = eos.get("SpecVol"), eos.get("SpecVolDisplaced"), vc.get("ZMid")
+    lo_e, hi_e = vc.get("MinLayerEdgeBot"), vc.get("MaxLayerEdgeTop")
+    lo_c, hi_c = vc.get("MinLayerCell"), vc.get("MaxLayerCell")
+    t = RR.tables(m)
+    want_s = RR.slope(hh, sv, svd, zm, t["CellsOnEdge"], t["DcEdge"], lo_e, hi_e, m.NEdgesAll, rho0, np.zeros((ne, K)),
+                      slope_max=0.02, n2_floor=1.0e-9)
+
+    def named(name, shape):
+        out = np.empty(shape)
+        assert L.omg_redi_copy_to_host(h, name, out.ctypes.data_as(PDBL), C.c_size_t(out.size)) == 0
+        return out
+
+    assert np.array_equal(named(b"SlopeInterface", (ne, K)), want_s) and np.abs(want_s).max() > 0.0
+    bsv, bsvd, bzm = (oa.DeviceBuffer(a) for a in (sv, svd, zm))
+    assert L.omg_redi_compute_slope_arrays(h, vp(bh.ptr), vp(bsv.ptr), None, vp(bzm.ptr), None) == 1
+    assert L.omg_redi_compute_slope_arrays(h, vp(bh.ptr), vp(bsv.ptr), vp(bsvd.ptr), vp(bzm.ptr), None) == 0
+    oa.device_synchronize()
+    assert np.array_equal(named(b"SlopeInterface", (ne, K)), want_s)
+    # the tendency: the VertCoord's ZMid (NULL) and the caller's
+    want_t = RR.add_tracer_tend(tt.copy(), hh, tr, nt, zm, want_s, kappa, t, lo_c, hi_c, lo_e, hi_e)
+    assert L.omg_redi_add_tracer_tend(h, None, vp(bh.ptr), vp(btr.ptr), nt, None, None) == 1 and "invalid argument" in _err()
+    for bad in (0, 3):
+        assert L.omg_redi_add_tracer_tend(h, vp(bt.ptr), vp(bh.ptr), vp(btr.ptr), bad, None, None) == 1
+        assert "NTracers" in _err()
+    assert L.omg_redi_add_tracer_tend(h, vp(bt.ptr), vp(bh.ptr), vp(btr.ptr), nt, None, None) == 0
+    assert L.omg_redi_add_tracer_tend(h, vp(bt2.ptr), vp(bh.ptr), vp(btr.ptr), nt, vp(bzm.ptr), None) == 0
+    oa.device_synchronize()
+    assert np.array_equal(bt.to_host(), want_t) and np.array_equal(bt2.to_host(), want_t)
+    assert not np.array_equal(want_t, tt)
+    # the diffusivity, without and with a VertDiff
+    want_d, want_vd = RR.vert_diffusivity(np.zeros((nc, K)), vd.copy(), want_s, kappa, t, lo_c, hi_c, lo_e, hi_e)
+    assert L.omg_redi_compute_vert_diffusivity(h, None, None) == 0
+    oa.device_synchronize()
+    assert np.array_equal(named(b"VertDiffusivity", (nc, K)), want_d) and want_d.max() > 0.0
+    assert L.omg_redi_compute_vert_diffusivity(h, vp(bvd.ptr), None) == 0
+    oa.device_synchronize()
+    assert np.array_equal(bvd.to_host(), want_vd) and not np.array_equal(want_vd, vd)
+    assert L.omg_redi_launch_count(h, C.byref(launches)) == 0 and launches.value == 6
+    # attach / detach
+    aux = oa.AuxiliaryState(m, None, K, nt)
+    tracers = oa.Tracers(m, None, K, nt, 2)
+    tend = oa.Tendencies(m, K, nt)
+    vm = oa.VertMix(m, vc)
+    mix = oa.VertMixStep(m, vm, vc, eos, nt)
+    rk = oa.TimeStepper("RungeKutta4", 60.0, tend, aux, m, None, tracers)
+    assert L.omg_stepper_attach_redi(rk.h, h) == 1 and "Split-Explicit" in _err()
+    se = oa.TimeStepper("Split-Explicit", 60.0, tend, aux, m, None, tracers)
+    assert L.omg_stepper_attach_redi(se.h, h) == 1 and "no VertMixStep attached" in _err()
+    se.attach_vert_mix(mix)
+    assert L.omg_stepper_attach_redi(se.h, h) == 1 and "does not have this Redi attached" in _err()
+    h2 = C.c_void_p()
+    assert L.omg_redi_create(m2.h, vc2.h, eos2.h, 2, *par, C.byref(h2)) == 0
+    assert L.omg_vertmixstep_attach_redi(mix.h, h2) == 1 and "another mesh or layer count" in _err()
+    assert L.omg_vertmixstep_attach_redi(mix.h, h) == 0
+    assert L.omg_stepper_attach_redi(se.h, h2) == 1 and "another mesh or layer count" in _err()
+    assert L.omg_stepper_attach_redi(se.h, h) == 0
+    assert L.omg_stepper_attach_redi(se.h, None) == 0
+    assert L.omg_vertmixstep_attach_redi(mix.h, None) == 0
+    assert L.omg_redi_destroy(h2) == 0
+    assert L.omg_redi_destroy(h) == 0
