@@ -1212,7 +1212,35 @@ class VertMixStep(_Handle, _NamedArrays):
 PGRAD_ARRAYS = ("SurfacePressure", "TidalPotential", "SelfAttractionLoading")
 
 
-class PressureGrad(_Handle, _NamedArrays):
+class _ColumnPass:
+    """What PressureGrad, GentMcWilliams and Redi share (omega_amd/csrc/ColumnPass.h): the mesh, VertCoord and Eos they
+    are built on, the column pass with the object's own forcing, and the staging of a stratification given as arrays.
+    `_arrays` is also the prefix of the class's C symbols."""
+
+    def _create_on(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", *args):
+        self.mesh, self.vcoord, self.eos = mesh, vcoord, eos
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self._create(self._arrays + "_create", mesh.h, vcoord.h if vcoord is not None else None,
+                     eos.h if eos is not None else None, *args)
+
+    def _update_column(self, layer_thickness, tracers, ntracers: int, stream):
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
+        _chk(getattr(lib(), self._arrays + "_update_column")(self.h, h, t, int(ntracers), _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def _stratification(self, spec_vol, spec_vol_displaced, z_mid, keep: list):
+        """the three cell arrays staged on the device (all three or none: then None, the objects' arrays as they stand)"""
+        given = [x is not None for x in (spec_vol, spec_vol_displaced, z_mid)]
+        assert all(given) or not any(given), "give SpecVol, SpecVolDisplaced and ZMid, or none of them"
+        if not all(given):
+            return None
+        return [_level_dev(x, self.mesh.NCellsSize, self.K, keep) for x in (spec_vol, spec_vol_displaced, z_mid)]
+
+
+class PressureGrad(_Handle, _NamedArrays, _ColumnPass):
     """PressureGrad (omega_amd/csrc/PressureGrad.h): the layered-ocean pressure-gradient force on edges,
     Tend -= EdgeMask * (grad GeopotentialMid + 0.5 (SpecVol0 + SpecVol1) grad PressureMid), from the column fields of
     `vcoord` and `eos`.  Level-indexed inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)]
@@ -1221,20 +1249,12 @@ class PressureGrad(_Handle, _NamedArrays):
     _destroy, _arrays = "omg_pgrad_destroy", "omg_pgrad"
 
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None"):
-        self.mesh, self.vcoord, self.eos = mesh, vcoord, eos
-        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        self._create("omg_pgrad_create", mesh.h, vcoord.h if vcoord is not None else None,
-                     eos.h if eos is not None else None)
+        self._create_on(mesh, vcoord, eos)
 
     def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
         """The fused column pass from raw arrays: thickness [NCellsSize][K], tracers [ntracers][NCellsSize][K]
         (temperature 0, salinity 1), with this object's SurfacePressure / TidalPotential / SelfAttractionLoading."""
-        keep, n = [], self.mesh.NCellsSize
-        h = _level_dev(layer_thickness, n, self.K, keep)
-        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
-        _chk(lib().omg_pgrad_update_column(self.h, h, t, int(ntracers), _sh(stream)))
-        if keep:
-            device_synchronize()
+        self._update_column(layer_thickness, tracers, ntracers, stream)
 
     def compute(self, tend, pressure_mid=None, geopotential_mid=None, spec_vol=None, stream=None):
         """tend -= the term: from the three given cell arrays (the array form; all three or none), or from the
@@ -1470,7 +1490,7 @@ GM_ARRAYS = {"Kappa": "E", "BolusVelocity": "EK", "StreamFunction": "EK", "Surfa
              "TidalPotential": "C", "SelfAttractionLoading": "C"}
 
 
-class GentMcWilliams(_Handle, _NamedArrays):
+class GentMcWilliams(_Handle, _NamedArrays, _ColumnPass):
     """GentMcWilliams (omega_amd/csrc/GentMcWilliams.h): the eddy-induced (bolus) velocity of the Gent-McWilliams closure
     on the edges from the stratification of `vcoord` / `eos`, one tridiagonal solve per edge column.  Level-indexed
     inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles; the results are the
@@ -1480,34 +1500,23 @@ class GentMcWilliams(_Handle, _NamedArrays):
 
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", kappa: float = 600.0,
                  grav_wave_speed: float = 0.3):
-        self.mesh, self.vcoord, self.eos = mesh, vcoord, eos
-        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        self._create("omg_gm_create", mesh.h, vcoord.h if vcoord is not None else None,
-                     eos.h if eos is not None else None, C.c_double(kappa), C.c_double(grav_wave_speed))
+        self._create_on(mesh, vcoord, eos, C.c_double(kappa), C.c_double(grav_wave_speed))
 
     def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
         """The fused column pass with the displaced volume (kdisp = 1) from raw arrays: thickness [NCellsSize][K],
         tracers [ntracers][NCellsSize][K] (temperature 0, salinity 1), with this object's SurfacePressure /
         TidalPotential / SelfAttractionLoading."""
-        keep, n = [], self.mesh.NCellsSize
-        h = _level_dev(layer_thickness, n, self.K, keep)
-        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
-        _chk(lib().omg_gm_update_column(self.h, h, t, int(ntracers), _sh(stream)))
-        if keep:
-            device_synchronize()
+        self._update_column(layer_thickness, tracers, ntracers, stream)
 
     def compute(self, layer_thickness, transport=None, spec_vol=None, spec_vol_displaced=None, z_mid=None, stream=None):
         """BolusVelocity and StreamFunction from the three given cell arrays (the array form; all three or none), or from
         the Eos's and the VertCoord's arrays as they stand; transport += BolusVelocity if it is given."""
-        given = [x is not None for x in (spec_vol, spec_vol_displaced, z_mid)]
-        assert all(given) or not any(given), "give SpecVol, SpecVolDisplaced and ZMid, or none of them"
-        keep, n = [], self.mesh.NCellsSize
+        keep = []
+        strat = self._stratification(spec_vol, spec_vol_displaced, z_mid, keep)
         p, buf = (None, None) if transport is None else _stage_levels(transport, (self.mesh.NEdgesSize,), self.K)
-        h = _level_dev(layer_thickness, n, self.K, keep)
-        if all(given):
-            _chk(lib().omg_gm_compute_arrays(self.h, h, _level_dev(spec_vol, n, self.K, keep),
-                                             _level_dev(spec_vol_displaced, n, self.K, keep),
-                                             _level_dev(z_mid, n, self.K, keep), p, _sh(stream)))
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        if strat:
+            _chk(lib().omg_gm_compute_arrays(self.h, h, *strat, p, _sh(stream)))
         else:
             _chk(lib().omg_gm_compute(self.h, h, p, _sh(stream)))
         if keep:
@@ -1525,7 +1534,7 @@ REDI_ARRAYS = {"Kappa": "E", "SlopeInterface": "EK", "VertDiffusivity": "CK", "S
                "TidalPotential": "C", "SelfAttractionLoading": "C"}
 
 
-class Redi(_Handle, _NamedArrays):
+class Redi(_Handle, _NamedArrays, _ColumnPass):
     """Redi (omega_amd/csrc/Redi.h): isoneutral diffusion of the tracers -- the isopycnal slope relative to the layers on
     the edge interfaces from the stratification of `vcoord` / `eos` (compute_slope), the explicit cross terms of the
     small-slope tensor on a tracer tendency (add_tracer_tend) and its slope-squared part as a vertical diffusivity for
@@ -1537,33 +1546,22 @@ class Redi(_Handle, _NamedArrays):
 
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", max_tracers: int,
                  kappa: float = 600.0, slope_max: float = 0.01, n2_floor: float = 1.0e-10):
-        self.mesh, self.vcoord, self.eos, self.max_tracers = mesh, vcoord, eos, int(max_tracers)
-        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        self._create("omg_redi_create", mesh.h, vcoord.h if vcoord is not None else None,
-                     eos.h if eos is not None else None, int(max_tracers), C.c_double(kappa), C.c_double(slope_max),
-                     C.c_double(n2_floor))
+        self.max_tracers = int(max_tracers)
+        self._create_on(mesh, vcoord, eos, int(max_tracers), C.c_double(kappa), C.c_double(slope_max), C.c_double(n2_floor))
 
     def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
         """The fused column pass with the displaced volume (kdisp = 1) from raw arrays, as
         GentMcWilliams.update_column, with this object's SurfacePressure / TidalPotential / SelfAttractionLoading."""
-        keep, n = [], self.mesh.NCellsSize
-        h = _level_dev(layer_thickness, n, self.K, keep)
-        t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
-        _chk(lib().omg_redi_update_column(self.h, h, t, int(ntracers), _sh(stream)))
-        if keep:
-            device_synchronize()
+        self._update_column(layer_thickness, tracers, ntracers, stream)
 
     def compute_slope(self, layer_thickness, spec_vol=None, spec_vol_displaced=None, z_mid=None, stream=None):
         """SlopeInterface from the three given cell arrays (the array form; all three or none), or from the Eos's and
         the VertCoord's arrays as they stand."""
-        given = [x is not None for x in (spec_vol, spec_vol_displaced, z_mid)]
-        assert all(given) or not any(given), "give SpecVol, SpecVolDisplaced and ZMid, or none of them"
-        keep, n = [], self.mesh.NCellsSize
-        h = _level_dev(layer_thickness, n, self.K, keep)
-        if all(given):
-            _chk(lib().omg_redi_compute_slope_arrays(self.h, h, _level_dev(spec_vol, n, self.K, keep),
-                                                     _level_dev(spec_vol_displaced, n, self.K, keep),
-                                                     _level_dev(z_mid, n, self.K, keep), _sh(stream)))
+        keep = []
+        strat = self._stratification(spec_vol, spec_vol_displaced, z_mid, keep)
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        if strat:
+            _chk(lib().omg_redi_compute_slope_arrays(self.h, h, *strat, _sh(stream)))
         else:
             _chk(lib().omg_redi_compute_slope(self.h, h, _sh(stream)))
         if keep:

@@ -9,7 +9,8 @@
 // the same order is bit-identical, tests/gent_mcwilliams_reference.py).  g = VertCoord::Gravity, Rho0 the VertCoord's.
 // For every edge e < NEdgesAll (halo edges are swept like owned ones, as PressureGrad does) with Lo = MinLayerEdgeBot[e],
 // Hi = MaxLayerEdgeTop[e], c0, c1 = CellsOnEdge[e][0], [1]; an edge whose range is not 0 <= Lo <= Hi < NVertLayers is
-// left alone entirely:
+// left alone entirely, and so is one with a cell outside [0, NCellsSize), as in Redi.h and the edge tiles of the other
+// vertical kernels -- no mesh this library builds has one (Decomp maps every missing cell to the sentinel row):
 //      InvDc = 1.0 / DcEdge[e];  C2 = GravWaveSpeed * GravWaveSpeed;  GR = g / Rho0
 //    layers K = Lo .. Hi:
 //      Rho_c[K]   = 1.0 / SpecVol[c][K]                                   (c = c0, c1)
@@ -56,14 +57,11 @@
 #ifndef OMEGA_AMD_GENTMCWILLIAMS_H
 #define OMEGA_AMD_GENTMCWILLIAMS_H
 
-#include "Base.h"
-#include "Eos.h"
-#include "HorzMesh.h"
-#include "VertCoord.h"
+#include "ColumnPass.h"
 
 namespace OMEGA {
 
-class GentMcWilliams : public Registry<GentMcWilliams> {
+class GentMcWilliams : public Registry<GentMcWilliams>, public ColumnPass {
  public:
    /// Refuses (OmegaError) a null or host-only mesh; a VertCoord or Eos that is null, was built for another mesh or has
    /// another layer count; NVertLayers outside 1 .. TriDiagMaxRows; a GMKappa that is negative or not finite; a
@@ -71,19 +69,18 @@ class GentMcWilliams : public Registry<GentMcWilliams> {
    GentMcWilliams(const std::string &Name, const HorzMesh *Mesh, VertCoord *VCoord, Eos *EqState, Real GMKappa = 600.0,
                   Real GravWaveSpeed = 0.3);
 
-   I4 NVertLayers;
    Real GMKappa, GravWaveSpeed;
    /// [NEdgesSize], GMKappa at construction; the caller may overwrite it (e.g. to scale with the resolution)
    Array1DReal Kappa;
    /// [NEdgesSize][levelPitch(K)], zero at construction
    Array2DReal BolusVelocity, StreamFunction;
-   /// The column pass's per-cell forcing, [NCellsSize], zero at construction; the caller may overwrite them
-   Array1DReal SurfacePressure, TidalPotential, SelfAttractionLoading;
 
    /// The fused column pass (VertCoord::computeColumn) from raw arrays: thickness [NCellsSize][levelPitch(K)], tracers
    /// [>= 2][NCellsSize][levelPitch(K)] with TIndex = 0, SIndex = 1, Displaced = true, KDisp = 1, and this object's
-   /// SurfacePressure / TidalPotential / SelfAttractionLoading.
-   void updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const;
+   /// SurfacePressure / TidalPotential / SelfAttractionLoading (ColumnPass.h).
+   void updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const {
+      ColumnPass::updateColumn(LayerThickness, TracerArray, true, S);
+   }
    /// The array form of the contract: the four cell arrays [NCellsSize][levelPitch(K)]; Transport
    /// [NEdgesSize][levelPitch(K)] accumulated in place, or empty (no term).  One launch.
    void computeBolusVelocity(const Array2DReal &LayerThickness, const Array2DReal &SpecVol,
@@ -106,9 +103,6 @@ class GentMcWilliams : public Registry<GentMcWilliams> {
       computeBolusVelocity(LayerThickness, Transport, Stream);
    }
 
-   const HorzMesh *Mesh;
-   VertCoord *VCoord;
-   Eos *EqState;
    std::string Name;
 };
 

@@ -6,20 +6,10 @@
 namespace OMEGA {
 
 PressureGrad::PressureGrad(const std::string &Name_, const HorzMesh *Mesh_, VertCoord *VCoord_, Eos *EqState_)
-    : NVertLayers(0), Mesh(Mesh_), VCoord(VCoord_), EqState(EqState_), Name(Name_) {
+    : ColumnPass(Mesh_, VCoord_, EqState_), Name(Name_) {
    OMEGA_REQUIRE(Mesh != nullptr, "PressureGrad: mesh is NULL");
-   OMEGA_REQUIRE(!Mesh->HostOnly,
-                 "PressureGrad: the mesh was created host-only: no device arrays, compute is unavailable");
-   OMEGA_REQUIRE(VCoord != nullptr, "PressureGrad: VertCoord is NULL");
-   OMEGA_REQUIRE(EqState != nullptr, "PressureGrad: Eos is NULL");
-   OMEGA_REQUIRE(VCoord->Mesh == Mesh, "PressureGrad: the VertCoord was built for another mesh");
-   OMEGA_REQUIRE(EqState->Mesh == Mesh, "PressureGrad: the Eos was built for another mesh");
-   OMEGA_REQUIRE(EqState->NVertLayers == VCoord->NVertLayers,
-                 "PressureGrad: the VertCoord and the Eos have different layer counts");
-   NVertLayers           = VCoord->NVertLayers;
-   SurfacePressure       = Array1DReal("SurfacePressure", Mesh->NCellsSize);
-   TidalPotential        = Array1DReal("TidalPotential", Mesh->NCellsSize);
-   SelfAttractionLoading = Array1DReal("SelfAttractionLoading", Mesh->NCellsSize);
+   requireFits("PressureGrad");
+   allocateForcing();
 }
 
 void PressureGrad::computePressureGrad(const Array2DReal &Tend, const Array2DReal &PMid, const Array2DReal &GeoMid,
@@ -41,11 +31,6 @@ void PressureGrad::computePressureGrad(const Array2DReal &Tend, const Array2DRea
 
 void PressureGrad::computePressureGrad(const Array2DReal &Tend, hipStream_t S) const {
    computePressureGrad(Tend, VCoord->PressureMid, VCoord->GeopotentialMid, EqState->SpecVol, S);
-}
-
-void PressureGrad::updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const {
-   VCoord->computeColumn(LayerThickness, TracerArray, *EqState, SurfacePressure, TidalPotential, SelfAttractionLoading,
-                         false, 0, S, 0, 1);
 }
 
 } // namespace OMEGA

@@ -28,22 +28,15 @@
 #ifndef OMEGA_AMD_PRESSUREGRAD_H
 #define OMEGA_AMD_PRESSUREGRAD_H
 
-#include "Base.h"
-#include "Eos.h"
-#include "HorzMesh.h"
-#include "VertCoord.h"
+#include "ColumnPass.h"
 
 namespace OMEGA {
 
-class PressureGrad : public Registry<PressureGrad> {
+class PressureGrad : public Registry<PressureGrad>, public ColumnPass {
  public:
    /// Refuses (OmegaError) a null or host-only mesh, and a VertCoord or Eos that is null, was built for another mesh or
    /// has another layer count.  Everything is allocated here; no call allocates.
    PressureGrad(const std::string &Name, const HorzMesh *Mesh, VertCoord *VCoord, Eos *EqState);
-
-   I4 NVertLayers;
-   /// The column pass's per-cell forcing, [NCellsSize], zero at construction; the caller may overwrite them
-   Array1DReal SurfacePressure, TidalPotential, SelfAttractionLoading;
 
    /// The array form of the contract: Tend [NEdgesSize][levelPitch(K)] accumulated in place, the three cell arrays
    /// [NCellsSize][levelPitch(K)]
@@ -53,8 +46,10 @@ class PressureGrad : public Registry<PressureGrad> {
    void computePressureGrad(const Array2DReal &Tend, hipStream_t S) const;
    /// The fused column pass (VertCoord::computeColumn) from raw arrays: thickness [NCellsSize][levelPitch(K)], tracers
    /// [>= 2][NCellsSize][levelPitch(K)] with TIndex = 0, SIndex = 1, Displaced = false, and this object's
-   /// SurfacePressure / TidalPotential / SelfAttractionLoading.
-   void updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const;
+   /// SurfacePressure / TidalPotential / SelfAttractionLoading (ColumnPass.h).
+   void updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const {
+      ColumnPass::updateColumn(LayerThickness, TracerArray, false, S);
+   }
 
    // ---- the reference's style of signature: on this object's `Stream` (default: the null stream)
    hipStream_t Stream = nullptr;
@@ -67,9 +62,6 @@ class PressureGrad : public Registry<PressureGrad> {
       updateColumn(LayerThickness, TracerArray, Stream);
    }
 
-   const HorzMesh *Mesh;
-   VertCoord *VCoord;
-   Eos *EqState;
    std::string Name;
 };
 

@@ -2,7 +2,6 @@
 #include "Redi.h"
 #include "Pacer.h"
 #include "kernels/RediKernels.h"
-#include "kernels/TriDiagKernels.h"
 
 #include <cmath>
 #include <vector>
@@ -11,8 +10,8 @@ namespace OMEGA {
 
 Redi::Redi(const std::string &Name_, const HorzMesh *Mesh_, VertCoord *VCoord_, Eos *EqState_, int MaxTracers_,
            Real RediKappa_, Real SlopeMax_, Real N2Floor_)
-    : NVertLayers(0), MaxTracers(MaxTracers_), RediKappa(RediKappa_), SlopeMax(SlopeMax_), N2Floor(N2Floor_), Mesh(Mesh_),
-      VCoord(VCoord_), EqState(EqState_), Name(Name_) {
+    : ColumnPass(Mesh_, VCoord_, EqState_), MaxTracers(MaxTracers_), RediKappa(RediKappa_), SlopeMax(SlopeMax_),
+      N2Floor(N2Floor_), Name(Name_) {
    OMEGA_REQUIRE(Mesh != nullptr, "Redi: mesh is NULL");
    OMEGA_REQUIRE(std::isfinite(RediKappa) && RediKappa >= 0.0,
                  "Redi: RediKappa = " + std::to_string(RediKappa) + " is negative or not finite");
@@ -21,46 +20,22 @@ Redi::Redi(const std::string &Name_, const HorzMesh *Mesh_, VertCoord *VCoord_, 
    OMEGA_REQUIRE(std::isfinite(N2Floor) && N2Floor > 0.0,
                  "Redi: N2Floor = " + std::to_string(N2Floor) + " is not finite or not positive");
    OMEGA_REQUIRE(MaxTracers >= 1, "Redi: MaxTracers = " + std::to_string(MaxTracers) + " is below 1");
-   OMEGA_REQUIRE(!Mesh->HostOnly, "Redi: the mesh was created host-only: no device arrays, compute is unavailable");
-   OMEGA_REQUIRE(VCoord != nullptr, "Redi: VertCoord is NULL");
-   OMEGA_REQUIRE(EqState != nullptr, "Redi: Eos is NULL");
-   OMEGA_REQUIRE(VCoord->Mesh == Mesh, "Redi: the VertCoord was built for another mesh");
-   OMEGA_REQUIRE(EqState->Mesh == Mesh, "Redi: the Eos was built for another mesh");
-   OMEGA_REQUIRE(EqState->NVertLayers == VCoord->NVertLayers, "Redi: the VertCoord and the Eos have different layer counts");
-   OMEGA_REQUIRE(VCoord->NVertLayers >= 1 && VCoord->NVertLayers <= TriDiagMaxRows,
-                 "Redi: NVertLayers = " + std::to_string(VCoord->NVertLayers) +
-                     " is outside the supported 1 <= NVertLayers <= " + std::to_string(TriDiagMaxRows));
-   NVertLayers           = VCoord->NVertLayers;
-   Kappa                 = Array1DReal("Kappa", Mesh->NEdgesSize);
-   SlopeInterface        = Array2DReal::levels("SlopeInterface", Mesh->NEdgesSize, NVertLayers);
-   VertDiffusivity       = Array2DReal::levels("VertDiffusivity", Mesh->NCellsSize, NVertLayers);
-   SurfacePressure       = Array1DReal("SurfacePressure", Mesh->NCellsSize);
-   TidalPotential        = Array1DReal("TidalPotential", Mesh->NCellsSize);
-   SelfAttractionLoading = Array1DReal("SelfAttractionLoading", Mesh->NCellsSize);
+   requireFits("Redi");
+   requirePackedLayers("Redi", NVertLayers);
+   Kappa           = Array1DReal("Kappa", Mesh->NEdgesSize);
+   SlopeInterface  = Array2DReal::levels("SlopeInterface", Mesh->NEdgesSize, NVertLayers);
+   VertDiffusivity = Array2DReal::levels("VertDiffusivity", Mesh->NCellsSize, NVertLayers);
+   allocateForcing();
    const std::vector<Real> Fill((size_t)Mesh->NEdgesSize, RediKappa);
    copyToDevice(Kappa, Fill.data());
 }
 
-void Redi::updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const {
-   VCoord->computeColumn(LayerThickness, TracerArray, *EqState, SurfacePressure, TidalPotential, SelfAttractionLoading,
-                         true, 1, S, 0, 1);
-}
-
 void Redi::computeSlope(const Array2DReal &H, const Array2DReal &SpecVol, const Array2DReal &SpecVolDisp,
                         const Array2DReal &ZMid, hipStream_t S) const {
-   requireLevelArray("Redi", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
-   requireLevelArray("Redi", SpecVol, Mesh->NCellsSize, NVertLayers, "SpecVol");
-   requireLevelArray("Redi", SpecVolDisp, Mesh->NCellsSize, NVertLayers, "SpecVolDisplaced");
-   requireLevelArray("Redi", ZMid, Mesh->NCellsSize, NVertLayers, "ZMid");
-   Pacer::Range Timer("Redi:computeSlope", 1);
    RediSlopeArgs A;
-   A.NEdgesAll = Mesh->NEdgesAll, A.NCellsSize = Mesh->NCellsSize, A.K = NVertLayers;
-   A.CellsOnEdge     = Mesh->CellsOnEdge.Ptr;
-   A.MinLayerEdgeBot = VCoord->MinLayerEdgeBot.Ptr, A.MaxLayerEdgeTop = VCoord->MaxLayerEdgeTop.Ptr;
-   A.DcEdge    = Mesh->DcEdge.Ptr;
-   A.GOverRho0 = VertCoord::Gravity / VCoord->Rho0;
+   stratificationArgs("Redi", A, H, SpecVol, SpecVolDisp, ZMid);
+   Pacer::Range Timer("Redi:computeSlope", 1);
    A.SlopeMax = SlopeMax, A.N2Floor = N2Floor;
-   A.SpecVol = SpecVol.Ptr, A.SpecVolDisplaced = SpecVolDisp.Ptr, A.ZMid = ZMid.Ptr;
    A.SlopeInterface = SlopeInterface.Ptr;
    launchRediSlope(A, S);
    ++LaunchCount;

@@ -84,14 +84,11 @@
 #ifndef OMEGA_AMD_REDI_H
 #define OMEGA_AMD_REDI_H
 
-#include "Base.h"
-#include "Eos.h"
-#include "HorzMesh.h"
-#include "VertCoord.h"
+#include "ColumnPass.h"
 
 namespace OMEGA {
 
-class Redi : public Registry<Redi> {
+class Redi : public Registry<Redi>, public ColumnPass {
  public:
    /// Refuses (OmegaError) a null or host-only mesh; a VertCoord or Eos that is null, was built for another mesh or has
    /// another layer count; NVertLayers outside 1 .. TriDiagMaxRows; a RediKappa that is negative or not finite; a
@@ -99,7 +96,6 @@ class Redi : public Registry<Redi> {
    Redi(const std::string &Name, const HorzMesh *Mesh, VertCoord *VCoord, Eos *EqState, int MaxTracers,
         Real RediKappa = 600.0, Real SlopeMax = 0.01, Real N2Floor = 1.0e-10);
 
-   I4 NVertLayers;
    I4 MaxTracers;
    Real RediKappa, SlopeMax, N2Floor;
    /// [NEdgesSize], RediKappa at construction; the caller may overwrite it
@@ -108,13 +104,13 @@ class Redi : public Registry<Redi> {
    Array2DReal SlopeInterface;
    /// [NCellsSize][levelPitch(K)], zero at construction; the same row convention
    Array2DReal VertDiffusivity;
-   /// The column pass's per-cell forcing, [NCellsSize], zero at construction; the caller may overwrite them
-   Array1DReal SurfacePressure, TidalPotential, SelfAttractionLoading;
    mutable I8 LaunchCount = 0; ///< kernel launches issued by the three compute calls so far
 
    /// GentMcWilliams::updateColumn's pass (Displaced = true, KDisp = 1, temperature 0, salinity 1) with this object's
-   /// forcing
-   void updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const;
+   /// forcing (ColumnPass.h)
+   void updateColumn(const Array2DReal &LayerThickness, const Array3DReal &TracerArray, hipStream_t S) const {
+      ColumnPass::updateColumn(LayerThickness, TracerArray, true, S);
+   }
    /// 1. of the contract, the array form: the cell arrays [NCellsSize][levelPitch(K)]
    void computeSlope(const Array2DReal &LayerThickness, const Array2DReal &SpecVol, const Array2DReal &SpecVolDisplaced,
                      const Array2DReal &ZMid, hipStream_t S) const;
@@ -150,9 +146,6 @@ class Redi : public Registry<Redi> {
    }
    void computeVertDiffusivity(const Array2DReal &VertDiff) const { computeVertDiffusivity(VertDiff, Stream); }
 
-   const HorzMesh *Mesh;
-   VertCoord *VCoord;
-   Eos *EqState;
    std::string Name;
 };
 

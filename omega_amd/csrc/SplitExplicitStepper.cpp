@@ -51,17 +51,26 @@ void SplitExplicitStepper::attachMonotoneAdv(MonotoneAdv *M) {
    Mono = M;
 }
 
-void SplitExplicitStepper::requireGentMcWilliamsFits(const GentMcWilliams *G, const char *Where) const {
-   const std::string W = std::string(Where) + ": ";
-   OMEGA_REQUIRE(G->Mesh == Mesh && G->NVertLayers == Tend->LayerThicknessTend.Ext[1],
-                 W + "the GentMcWilliams was built for another mesh or layer count");
+void SplitExplicitStepper::requireColumnPassFits(const ColumnPass &C, const std::string &Class,
+                                                 const std::string &W) const {
+   OMEGA_REQUIRE(C.Mesh == Mesh && C.NVertLayers == Tend->LayerThicknessTend.Ext[1],
+                 W + "the " + Class + " was built for another mesh or layer count");
    OMEGA_REQUIRE(Tend->NTracers >= 2, W + "the stepper has " + std::to_string(Tend->NTracers) +
                                           " tracers: the column pass needs temperature and salinity (tracers 0 and 1)");
+}
+
+void SplitExplicitStepper::requirePressureGradShares(const ColumnPass &C, const std::string &Class, const std::string &W,
+                                                     const char *Tail) const {
    if (const PressureGrad *P = Tend->pressureGrad()) // two column passes on two sets of column fields: refused
-      OMEGA_REQUIRE(G->VCoord == P->VCoord && G->EqState == P->EqState,
-                    W + "the GentMcWilliams and the PressureGrad attached to the Tendencies are on different VertCoord "
-                        "or Eos objects: both run the column pass, on one set of column fields, and keeping their "
-                        "forcing arrays equal is the caller's responsibility");
+      OMEGA_REQUIRE(C.VCoord == P->VCoord && C.EqState == P->EqState,
+                    W + "the " + Class + " and the PressureGrad attached to the Tendencies are on different VertCoord " +
+                        "or Eos objects: both run the column pass, on one set of column fields" + Tail);
+}
+
+void SplitExplicitStepper::requireGentMcWilliamsFits(const GentMcWilliams *G, const char *Where) const {
+   const std::string W = std::string(Where) + ": ";
+   requireColumnPassFits(*G, "GentMcWilliams", W);
+   requirePressureGradShares(*G, "GentMcWilliams", W, ", and keeping their forcing arrays equal is the caller's responsibility");
 }
 
 void SplitExplicitStepper::attachGentMcWilliams(GentMcWilliams *G) {
@@ -76,20 +85,14 @@ void SplitExplicitStepper::attachGentMcWilliams(GentMcWilliams *G) {
 
 void SplitExplicitStepper::requireRediFits(const Redi *R, const char *Where) const {
    const std::string W = std::string(Where) + ": ";
-   OMEGA_REQUIRE(R->Mesh == Mesh && R->NVertLayers == Tend->LayerThicknessTend.Ext[1],
-                 W + "the Redi was built for another mesh or layer count");
-   OMEGA_REQUIRE(Tend->NTracers >= 2, W + "the stepper has " + std::to_string(Tend->NTracers) +
-                                          " tracers: the column pass needs temperature and salinity (tracers 0 and 1)");
+   requireColumnPassFits(*R, "Redi", W);
    OMEGA_REQUIRE(R->MaxTracers >= Tend->NTracers, W + "the Redi has MaxTracers = " + std::to_string(R->MaxTracers) +
                                                       ", below the stepper's " + std::to_string(Tend->NTracers) + " tracers");
    if (GM) // one column pass, on one set of column fields
       OMEGA_REQUIRE(R->VCoord == GM->VCoord && R->EqState == GM->EqState,
                     W + "the Redi and the attached GentMcWilliams are on different VertCoord or Eos objects: the step "
                         "runs one column pass for both");
-   if (const PressureGrad *P = Tend->pressureGrad())
-      OMEGA_REQUIRE(R->VCoord == P->VCoord && R->EqState == P->EqState,
-                    W + "the Redi and the PressureGrad attached to the Tendencies are on different VertCoord or Eos "
-                        "objects: both run the column pass, on one set of column fields");
+   requirePressureGradShares(*R, "Redi", W, "");
    OMEGA_REQUIRE(VMixStep != nullptr, W + "the stepper has no VertMixStep attached: without the implicit S.S term of the "
                                           "vertical mixing the explicit part of the isoneutral tensor is indefinite");
    OMEGA_REQUIRE(VMixStep->redi() == R, W + "the stepper's VertMixStep does not have this Redi attached "

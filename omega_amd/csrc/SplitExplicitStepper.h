@@ -164,6 +164,11 @@ class SplitExplicitStepper : public TimeStepper {
    MonotoneAdv *Mono   = nullptr;
    GentMcWilliams *GM  = nullptr;
    Redi *RediTerm      = nullptr;
+   /// what both have in common: the mesh, the layer count and the two tracers of the column pass (ColumnPass.h), and
+   /// one set of column fields with a PressureGrad attached to the Tendencies (Tail: the end of that message)
+   void requireColumnPassFits(const ColumnPass &C, const std::string &Class, const std::string &W) const;
+   void requirePressureGradShares(const ColumnPass &C, const std::string &Class, const std::string &W,
+                                  const char *Tail) const;
    /// what attachRedi refuses and doStep checks again (the other attachments may have changed since)
    void requireRediFits(const Redi *R, const char *Where) const;
    /// what attachGentMcWilliams refuses and doStep checks again (a PressureGrad may have been attached since)

@@ -28,8 +28,8 @@
 //    OmegaError naming the limit.
 //  - The Kokkos-only members -- makeTeamPolicy and the TriDiagScratch / TriDiagDiffScratch structs -- are not
 //    reproduced.  A kernel that solves columns it has assembled itself calls the device bodies of
-//    kernels/TriDiagKernels.h (pcrSolveRow, pcrDiffSolveRow, thomasSolveColumn, thomasDiffSolveColumn), the counterpart
-//    of the reference's team-level solve(Member, Scratch).
+//    kernels/TriDiagKernels.h (pcrSolveRow, pcrDiffSolveRowRagged, thomasSolveColumn, thomasDiffSolveColumn), the
+//    counterpart of the reference's team-level solve(Member, Scratch).
 #ifndef OMEGA_AMD_TRIDIAGSOLVERS_H
 #define OMEGA_AMD_TRIDIAGSOLVERS_H
 

@@ -7,7 +7,7 @@ namespace OMEGA {
 
 VertMixStep::VertMixStep(const std::string &Name_, const HorzMesh *Mesh_, VertMix *VMix_, VertCoord *VCoord_,
                          Eos *EqState_, int NTracers_)
-    : NVertLayers(0), NTracers(NTracers_), Mesh(Mesh_), VMix(VMix_), VCoord(VCoord_), EqState(EqState_), Name(Name_) {
+    : ColumnPass(Mesh_, VCoord_, EqState_), NTracers(NTracers_), VMix(VMix_), Name(Name_) {
    OMEGA_REQUIRE(Mesh != nullptr, "VertMixStep: mesh is NULL");
    OMEGA_REQUIRE(NTracers >= 2, "VertMixStep: NTracers = " + std::to_string(NTracers) +
                                     " is below 2: the column pass needs temperature (0) and salinity (1)");
@@ -24,12 +24,10 @@ VertMixStep::VertMixStep(const std::string &Name_, const HorzMesh *Mesh_, VertMi
    OMEGA_REQUIRE(NVertLayers <= MaxLayers, "VertMixStep: NVertLayers = " + std::to_string(NVertLayers) +
                                                " is above the fused column pass's limit of " +
                                                std::to_string(MaxLayers));
-   TangentialVelocity    = Array2DReal::levels("TangentialVelocity", Mesh->NEdgesSize, NVertLayers);
-   NormalStressEdge      = Array1DReal("NormalStressEdge", Mesh->NEdgesSize);
-   SurfaceTracerFlux     = Array2DReal("SurfaceTracerFlux", NTracers, Mesh->NCellsSize);
-   SurfacePressure       = Array1DReal("SurfacePressure", Mesh->NCellsSize);
-   TidalPotential        = Array1DReal("TidalPotential", Mesh->NCellsSize);
-   SelfAttractionLoading = Array1DReal("SelfAttractionLoading", Mesh->NCellsSize);
+   TangentialVelocity = Array2DReal::levels("TangentialVelocity", Mesh->NEdgesSize, NVertLayers);
+   NormalStressEdge   = Array1DReal("NormalStressEdge", Mesh->NEdgesSize);
+   SurfaceTracerFlux  = Array2DReal("SurfaceTracerFlux", NTracers, Mesh->NCellsSize);
+   allocateForcing();
 }
 
 void VertMixStep::attachRedi(Redi *R) {
@@ -48,7 +46,7 @@ void VertMixStep::apply(const Array2DReal &H, const Array2DReal &U, const Array3
    requireLevelArray("VertMixStep", Tr, NTracers, Mesh->NCellsSize, NVertLayers, "Tracers", "NCellsSize");
    VertMix::requireBoundary(Boundary);
    Pacer::Range Timer("VertMixStep:apply", 1);
-   VCoord->computeColumn(H, Tr, *EqState, SurfacePressure, TidalPotential, SelfAttractionLoading, true, 1, S);
+   updateColumn(H, Tr, true, S);
    VMix->computeBruntVaisalaFreqSq(*EqState, S);
    const TangentialReconOnEdge TangentialRecon(Mesh);
    TangentialRecon(TangentialVelocity, U, S);

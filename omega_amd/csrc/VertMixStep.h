@@ -24,17 +24,14 @@
 #ifndef OMEGA_AMD_VERTMIXSTEP_H
 #define OMEGA_AMD_VERTMIXSTEP_H
 
-#include "Base.h"
-#include "Eos.h"
-#include "HorzMesh.h"
+#include "ColumnPass.h"
 #include "OceanState.h"
 #include "Redi.h"
-#include "VertCoord.h"
 #include "VertMix.h"
 
 namespace OMEGA {
 
-class VertMixStep : public Registry<VertMixStep> {
+class VertMixStep : public Registry<VertMixStep>, public ColumnPass {
  public:
    /// The largest layer count of the fused column pass with the displaced volume (the LDS tile)
    static constexpr int MaxLayers = 1008;
@@ -45,13 +42,11 @@ class VertMixStep : public Registry<VertMixStep> {
    VertMixStep(const std::string &Name, const HorzMesh *Mesh, VertMix *VMix, VertCoord *VCoord, Eos *EqState,
                int NTracers);
 
-   I4 NVertLayers;
    I4 NTracers;
-   /// Zero at construction; the caller's to overwrite
-   Array2DReal TangentialVelocity;                                      ///< [NEdgesSize][levelPitch]: rewritten by apply
-   Array1DReal NormalStressEdge;                                        ///< [NEdgesSize], Pa
-   Array2DReal SurfaceTracerFlux;                                       ///< [NTracers][NCellsSize]
-   Array1DReal SurfacePressure, TidalPotential, SelfAttractionLoading; ///< [NCellsSize]: the column pass's forcing
+   /// Zero at construction; the caller's to overwrite (as the column pass's forcing, ColumnPass.h)
+   Array2DReal TangentialVelocity; ///< [NEdgesSize][levelPitch]: rewritten by apply
+   Array1DReal NormalStressEdge;   ///< [NEdgesSize], Pa
+   Array2DReal SurfaceTracerFlux;  ///< [NTracers][NCellsSize]
 
    VertMixBoundary Boundary;
    bool UseWindStress = false; ///< pass NormalStressEdge to the velocity solve
@@ -72,10 +67,7 @@ class VertMixStep : public Registry<VertMixStep> {
       apply(LayerThickness, NormalVelocity, Tracers, Dt, Stream);
    }
 
-   const HorzMesh *Mesh;
    VertMix *VMix;
-   VertCoord *VCoord;
-   Eos *EqState;
    std::string Name;
 
  protected:

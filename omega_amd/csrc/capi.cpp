@@ -1773,6 +1773,12 @@ int omg_stepper_attach_vert_mix(omg_stepper *st, omg_vertmix_step *ms) {
 }
 
 // ---- PressureGrad (PressureGrad.h)
+/// the column pass of a PressureGrad (Displaced = false), GentMcWilliams or Redi (true) on the caller's raw arrays
+static void updateColumnOf(const ColumnPass &C, bool Displaced, const double *LayerThickness, const double *Tracers,
+                           int NTracers, void *Stream) {
+   const int N = C.Mesh->NCellsSize, K = C.NVertLayers;
+   C.updateColumn(levelView(LayerThickness, N, K), tracerView(Tracers, NTracers, N, K), Displaced, (hipStream_t)Stream);
+}
 int omg_pgrad_create(const omg_mesh *m, omg_vcoord *v, omg_eos *e, omg_pgrad **out) {
    OMG_TRY
    OMG_ARG(m && out);
@@ -1789,10 +1795,7 @@ int omg_pgrad_update_column(omg_pgrad *p, const double *layer_thickness, const d
                             void *stream) {
    OMG_TRY
    OMG_ARG(p && layer_thickness && tracers && ntracers >= 2);
-   const HorzMesh *M = p->P->Mesh;
-   const int K       = p->P->NVertLayers;
-   p->P->updateColumn(levelView(layer_thickness, M->NCellsSize, K), tracerView(tracers, ntracers, M->NCellsSize, K),
-                      (hipStream_t)stream);
+   updateColumnOf(*p->P, false, layer_thickness, tracers, ntracers, stream);
    OMG_CATCH
 }
 int omg_pgrad_compute(omg_pgrad *p, double *tend, void *stream) {
@@ -2131,10 +2134,7 @@ int omg_gm_destroy(omg_gm *g) {
 int omg_gm_update_column(omg_gm *g, const double *layer_thickness, const double *tracers, int ntracers, void *stream) {
    OMG_TRY
    OMG_ARG(g && layer_thickness && tracers && ntracers >= 2);
-   const HorzMesh *M = g->G->Mesh;
-   const int K       = g->G->NVertLayers;
-   g->G->updateColumn(levelView(layer_thickness, M->NCellsSize, K), tracerView(tracers, ntracers, M->NCellsSize, K),
-                      (hipStream_t)stream);
+   updateColumnOf(*g->G, true, layer_thickness, tracers, ntracers, stream);
    OMG_CATCH
 }
 /// the optional transport of the two compute calls: NULL is the empty array (no term)
@@ -2193,8 +2193,7 @@ int omg_redi_destroy(omg_redi *r) {
 int omg_redi_update_column(omg_redi *r, const double *layer_thickness, const double *tracers, int ntracers, void *stream) {
    OMG_TRY
    OMG_ARG(r && layer_thickness && tracers && ntracers >= 2);
-   const int N = r->R->Mesh->NCellsSize, K = r->R->NVertLayers;
-   r->R->updateColumn(levelView(layer_thickness, N, K), tracerView(tracers, ntracers, N, K), (hipStream_t)stream);
+   updateColumnOf(*r->R, true, layer_thickness, tracers, ntracers, stream);
    OMG_CATCH
 }
 int omg_redi_compute_slope(omg_redi *r, const double *layer_thickness, void *stream) {

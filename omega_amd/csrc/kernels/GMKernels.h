@@ -4,18 +4,15 @@
 #ifndef OMEGA_AMD_GMKERNELS_H
 #define OMEGA_AMD_GMKERNELS_H
 
-#include "../Base.h"
+#include "PackedColumns.h"
 
 namespace OMEGA {
 
-/// Everything one bolus-velocity launch reads and writes (GentMcWilliams::computeBolusVelocity).
-struct GMArgs {
-   int NEdgesAll = 0, K = 0;
-   const I4 *CellsOnEdge = nullptr;                                 ///< [edge][2]
-   const I4 *MinLayerEdgeBot = nullptr, *MaxLayerEdgeTop = nullptr; ///< [edge] level range of the edge column
-   const Real *DcEdge = nullptr, *Kappa = nullptr;                  ///< [edge]
-   Real C2 = 0, GOverRho0 = 0; ///< GravWaveSpeed * GravWaveSpeed and g / Rho0, evaluated by the caller
-   const Real *LayerThickness = nullptr, *SpecVol = nullptr, *SpecVolDisplaced = nullptr, *ZMid = nullptr; ///< [cell][Pitch]
+/// Everything one bolus-velocity launch reads and writes (GentMcWilliams::computeBolusVelocity)
+struct GMArgs : EdgeColumnArgs {
+   const Real *Kappa = nullptr;          ///< [edge]
+   Real C2 = 0;                          ///< GravWaveSpeed * GravWaveSpeed, evaluated by the caller
+   const Real *LayerThickness = nullptr; ///< [cell][Pitch]
    Real *BolusVelocity = nullptr, *StreamFunction = nullptr; ///< [edge][Pitch]
    Real *Transport = nullptr;                                ///< [edge][Pitch], accumulated; null: no term
 };

@@ -4,19 +4,14 @@
 #ifndef OMEGA_AMD_REDIKERNELS_H
 #define OMEGA_AMD_REDIKERNELS_H
 
-#include "../Base.h"
+#include "PackedColumns.h"
 
 namespace OMEGA {
 
-/// Everything one slope launch reads and writes (Redi::computeSlope).
-struct RediSlopeArgs {
-   int NEdgesAll = 0, NCellsSize = 0, K = 0;
-   const I4 *CellsOnEdge = nullptr;                                 ///< [edge][2]
-   const I4 *MinLayerEdgeBot = nullptr, *MaxLayerEdgeTop = nullptr; ///< [edge] level range of the edge column
-   const Real *DcEdge = nullptr;                                    ///< [edge]
-   Real GOverRho0 = 0, SlopeMax = 0, N2Floor = 0;                   ///< g / Rho0 evaluated by the caller
-   const Real *SpecVol = nullptr, *SpecVolDisplaced = nullptr, *ZMid = nullptr; ///< [cell][Pitch]
-   Real *SlopeInterface = nullptr;                                              ///< [edge][Pitch]
+/// Everything one slope launch reads and writes (Redi::computeSlope)
+struct RediSlopeArgs : EdgeColumnArgs {
+   Real SlopeMax = 0, N2Floor = 0;
+   Real *SlopeInterface = nullptr; ///< [edge][Pitch]
 };
 void launchRediSlope(const RediSlopeArgs &A, hipStream_t S);
 

@@ -1,11 +1,12 @@
 // RediKernels.hip -- the three kernels behind Redi (Redi.h) on gfx950.
 //
 // Launch 1, the slope: the edge-column geometry of the bolus-velocity kernel (kernels/GMKernels.hip) without its solve
-// -- lanes along the layers of an edge column (layer Lo + I on lane I), floor(256 / K) columns per workgroup (one for
-// K > 256, up to 1024 lanes).  A lane reads its layer of the two cells once (SpecVol, SpecVolDisplaced, ZMid: coalesced
-// along the levels) and hands the six values the interface below it needs -- the two densities, the two heights, the
-// two displaced densities -- to the next lane through LDS; lane I >= 1 then forms the slope of the interface at the top
-// of its layer in registers and stores it.  One barrier, no solve, one array written.
+// -- lanes along the layers of an edge column (layer Lo + I on lane I) in the packed-column shape, and the edge layer
+// and edge interface of kernels/PackedColumns.h, which both kernels use.  A lane reads its layer of the two cells once
+// (SpecVol, SpecVolDisplaced, ZMid: coalesced along the levels) and hands the six values the interface below it needs
+// -- the two densities, the two heights, the two displaced densities -- to the next lane through LDS; lane I >= 1 then
+// forms the slope of the interface at the top of its layer in registers and stores it.  One barrier, no solve, one
+// array written.
 //
 // Launches 2 and 3, the tracer tendency and the S.S diffusivity: gather stencils over cells with the levels innermost.
 // A workgroup owns a tile of cells; its lanes run along the levels of a cell (LanesK = the power of two that holds
@@ -20,51 +21,27 @@
 // no grid-wide synchronisation.
 #include "RediKernels.h"
 #include "KernelCommon.h"
-#include "TriDiagKernels.h"
 
 namespace OMEGA {
 
 namespace {
 
-constexpr int RediLanes     = 256; // lanes a workgroup of short columns fills (launch 1)
-constexpr int RediArrays    = 6;   // LDS doubles per lane of launch 1
 constexpr int RediTileCells = 32;  // most cells per workgroup of the cell launches
 constexpr int RediMaxLanesK = 16;  // most lanes along one cell's levels: one 128-byte line of a row
 
-__global__ void __launch_bounds__(TriDiagMaxRows) rediSlopeKernel(RediSlopeArgs A, int Pitch, int SysPerBlock, int Rows) {
+__global__ void __launch_bounds__(TriDiagMaxRows) rediSlopeKernel(RediSlopeArgs A, int Pitch, PackedShape P) {
    extern __shared__ Real Lds[];
-   const int T      = threadIdx.x;
-   const int S      = T / A.K;
-   const int I      = T - S * A.K; // layer of the column: level Lo + I
-   const long Col   = (long)blockIdx.x * SysPerBlock + S;
-   const bool InSys = T < Rows && Col < A.NEdgesAll;
-   int Lo = 0, N = 0, C0 = 0, C1 = 0;
-   if (InSys) {
-      Lo           = A.MinLayerEdgeBot[Col];
-      const int Hi = A.MaxLayerEdgeTop[Col];
-      C0 = A.CellsOnEdge[2 * Col], C1 = A.CellsOnEdge[2 * Col + 1];
-      if (Lo >= 0 && Lo <= Hi && Hi < A.K && C0 >= 0 && C0 < A.NCellsSize && C1 >= 0 && C1 < A.NCellsSize)
-         N = Hi - Lo + 1;
-   }
-   const bool Act = InSys && I < N;
-   const int Lev  = Lo + I;
+   const int T        = threadIdx.x;
+   const PackedLane L = packedLane(P, A.K, A.NEdgesAll);
+   const EdgeColumn E = edgeColumn(A, L);
+   const bool Act     = L.InSys && L.I < E.N;
+   const int Lev      = E.Lo + L.I;
 
    // ---- this lane's layer of the two cells, and what the interface below it needs of it
-   Real Rho0 = 0, Rho1 = 0, Z0 = 0, Z1 = 0, InvDc = 0;
+   EdgeLayer V;
    if (Act) {
-      const size_t P0 = (size_t)C0 * Pitch + Lev, P1 = (size_t)C1 * Pitch + Lev;
-      Rho0  = 1.0 / A.SpecVol[P0];
-      Rho1  = 1.0 / A.SpecVol[P1];
-      Z0    = A.ZMid[P0];
-      Z1    = A.ZMid[P1];
-      InvDc = 1.0 / A.DcEdge[Col];
-      Real Rd0 = 0, Rd1 = 0;
-      if (I < N - 1) { // the bottom layer's displaced volume is not part of the contract (it may be unset)
-         Rd0 = 1.0 / A.SpecVolDisplaced[P0];
-         Rd1 = 1.0 / A.SpecVolDisplaced[P1];
-      }
-      Lds[0 * Rows + T] = Rho0, Lds[1 * Rows + T] = Rho1, Lds[2 * Rows + T] = Z0, Lds[3 * Rows + T] = Z1;
-      Lds[4 * Rows + T] = Rd0, Lds[5 * Rows + T] = Rd1;
+      V = loadEdgeLayer(A, L.Col, (size_t)E.C0 * Pitch + Lev, (size_t)E.C1 * Pitch + Lev, L.I == E.N - 1);
+      storeEdgeLayer(V, Lds, P.Rows, T);
    }
    __syncthreads();
    if (!Act)
@@ -72,28 +49,17 @@ __global__ void __launch_bounds__(TriDiagMaxRows) rediSlopeKernel(RediSlopeArgs 
 
    // ---- the interface between layer Lev - 1 (the lane above) and layer Lev
    Real Slope = 0.0; // the surface of the column
-   if (I >= 1) {
-      const int U      = T - 1;
-      const Real Rho0u = Lds[0 * Rows + U], Rho1u = Lds[1 * Rows + U], Z0u = Lds[2 * Rows + U], Z1u = Lds[3 * Rows + U];
-      const Real Rd0u = Lds[4 * Rows + U], Rd1u = Lds[5 * Rows + U];
-      const Real GR      = A.GOverRho0;
-      const Real GradRho = (Rho1 - Rho0) * InvDc, GradRhoU = (Rho1u - Rho0u) * InvDc;
-      const Real GradZ = (Z1 - Z0) * InvDc, GradZU = (Z1u - Z0u) * InvDc;
-      const Real Dz0 = Z0u - Z0, Dz1 = Z1u - Z1;
-      const Real RhoZ0 = (Rho0u - Rho0) / Dz0, RhoZ1 = (Rho1u - Rho1) / Dz1;
-      const Real N20 = (GR * (Rho0 - Rd0u)) / Dz0, N21 = (GR * (Rho1 - Rd1u)) / Dz1;
-      const Real RhoZE = 0.5 * (RhoZ0 + RhoZ1);
-      Real N2E         = 0.5 * (N20 + N21);
-      N2E              = N2E < 0.0 ? 0.0 : N2E;
-      const Real GradRhoZ = 0.5 * (GradRhoU + GradRho) - RhoZE * (0.5 * (GradZU + GradZ));
-      const Real Den      = N2E < A.N2Floor ? A.N2Floor : N2E;
-      const Real SIso     = (GR * GradRhoZ) / Den;
-      Real SRel           = SIso - 0.5 * (GradZU + GradZ);
-      SRel                = SRel > A.SlopeMax ? A.SlopeMax : SRel;
-      SRel                = SRel < -A.SlopeMax ? -A.SlopeMax : SRel;
-      Slope               = SRel;
+   if (L.I >= 1) {
+      const Real GR         = A.GOverRho0;
+      const EdgeInterface F = edgeInterface(V, Lds, P.Rows, T - 1, GR);
+      const Real Den        = F.N2E < A.N2Floor ? A.N2Floor : F.N2E;
+      const Real SIso       = (GR * F.GradRhoZ) / Den;
+      Real SRel             = SIso - F.GradZE;
+      SRel                  = SRel > A.SlopeMax ? A.SlopeMax : SRel;
+      SRel                  = SRel < -A.SlopeMax ? -A.SlopeMax : SRel;
+      Slope                 = SRel;
    }
-   A.SlopeInterface[(size_t)Col * Pitch + Lev] = Slope;
+   A.SlopeInterface[(size_t)L.Col * Pitch + Lev] = Slope;
 }
 
 /// What the cell launches keep in LDS per (cell of the tile, slot): carved from the dynamic LDS, doubles first
@@ -298,11 +264,7 @@ inline RediCellShape rediCellShape(int NCellsAll, int K) {
    return G;
 }
 
-void requireRediLayers(int K) {
-   OMEGA_REQUIRE(K >= 1 && K <= TriDiagMaxRows, "Redi: NVertLayers = " + std::to_string(K) +
-                                                    " is outside the supported 1 <= NVertLayers <= " +
-                                                    std::to_string(TriDiagMaxRows));
-}
+void requireRediLayers(int K) { requirePackedLayers("Redi", K); }
 
 } // namespace
 
@@ -310,13 +272,9 @@ void launchRediSlope(const RediSlopeArgs &A, hipStream_t S) {
    requireRediLayers(A.K);
    if (A.NEdgesAll <= 0)
       return;
-   // columns per workgroup and the lanes they occupy (as the bolus-velocity launch and the mixing solves)
-   const int Sys     = A.K <= RediLanes ? RediLanes / A.K : 1;
-   const int Rows    = Sys * A.K;
-   const int Threads = (Rows + 63) / 64 * 64;
-   const dim3 Grid((A.NEdgesAll + Sys - 1) / Sys);
-   const size_t Bytes = (size_t)RediArrays * Rows * sizeof(Real);
-   hipLaunchKernelGGL(rediSlopeKernel, Grid, dim3(Threads), Bytes, S, A, levelPitch(A.K), Sys, Rows);
+   const PackedShape P(A.K);
+   const size_t Bytes = (size_t)EdgeLayerArrays * P.Rows * sizeof(Real);
+   hipLaunchKernelGGL(rediSlopeKernel, P.grid(A.NEdgesAll), dim3(P.Threads), Bytes, S, A, levelPitch(A.K), P);
    HIP_CHECK(hipGetLastError());
 }
 

@@ -93,52 +93,61 @@ __device__ inline Real pcrSolveRow(bool Active, int K, int NRow, Real DL, Real D
    return X / D; // 1x1 system
 }
 
-/// PCRDiffusionSolver::solve(Member, Scratch) (TriDiagSolvers.h:377-454) for row K, as pcrSolveRow; the workspace
-/// holds 2 x 3 arrays (G, H, X) of `Span` doubles: array A of buffer B at Sys[(B * 3 + A) * Span + row].
-__device__ inline Real pcrDiffSolveRow(bool Active, int K, int NRow, Real G, Real H, Real X, Real *Sys, int Span) {
-   if (NRow == 1) // the reference's 1 << -1; defined as the 1x1 solve (TriDiagSolvers.h)
-      return X / (H + G);
-   const int NLevels = pcrLevels(NRow);
-   int B             = 0;
-   for (int Lev = 1; Lev < NLevels; ++Lev) {
-      Real *W = Sys + B * 3 * Span;
-      if (Active) {
-         W[0 * Span + K] = G, W[1 * Span + K] = H, W[2 * Span + K] = X;
-      }
-      __syncthreads();
-      if (Active) {
-         const int Stride     = 1 << Lev;
-         const int HalfStride = 1 << (Lev - 1);
+/// One level of PCRDiffusionSolver::solve(Member, Scratch) (TriDiagSolvers.h:377-454) on (G, H) of row K: W holds the
+/// level's G of every row of the system at W[row] and its H at W[Span + row].  G and H become the next level's; what
+/// is returned takes a right-hand side through the same level: X = X + Alpha * X[Kmh] + Beta * X[Kph].
+struct PcrDiffLevel {
+   Real Alpha, Beta;
+   int Kmh, Kph;
+};
+__device__ inline PcrDiffLevel pcrDiffLevel(int Lev, int K, int NRow, Real &G, Real &H, const Real *W, int Span) {
+   const int Stride     = 1 << Lev;
+   const int HalfStride = 1 << (Lev - 1);
+   PcrDiffLevel L;
 
-         int Kmh         = K - HalfStride;
-         const Real Gkmh = Kmh < 0 ? 0 : W[0 * Span + Kmh];
-         Kmh             = Kmh < 0 ? 0 : Kmh;
+   int Kmh         = K - HalfStride;
+   const Real Gkmh = Kmh < 0 ? 0 : W[0 * Span + Kmh];
+   L.Kmh           = Kmh < 0 ? 0 : Kmh;
 
-         const int Kms   = K - Stride;
-         const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
+   const int Kms   = K - Stride;
+   const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
 
-         int Kph = K + HalfStride;
-         Kph     = Kph >= NRow ? NRow - 1 : Kph;
+   const int Kph = K + HalfStride;
+   L.Kph         = Kph >= NRow ? NRow - 1 : Kph;
 
-         const Real Alpha = Gkmh / (W[1 * Span + Kmh] + Gkms + Gkmh);
-         const Real Beta  = G / (W[1 * Span + Kph] + G + W[0 * Span + Kph]);
+   L.Alpha = Gkmh / (W[1 * Span + L.Kmh] + Gkms + Gkmh);
+   L.Beta  = G / (W[1 * Span + L.Kph] + G + W[0 * Span + L.Kph]);
 
-         const Real NewG = W[0 * Span + Kph] * Beta;
-         const Real NewX = X + Alpha * W[2 * Span + Kmh] + Beta * W[2 * Span + Kph];
-         const Real NewH = H + Alpha * W[1 * Span + Kmh] + Beta * W[1 * Span + Kph];
-         G = NewG, H = NewH, X = NewX;
-      }
-      B ^= 1;
+   const Real NewG = W[0 * Span + L.Kph] * L.Beta;
+   const Real NewH = H + L.Alpha * W[1 * Span + L.Kmh] + L.Beta * W[1 * Span + L.Kph];
+   G = NewG, H = NewH;
+   return L;
+}
+
+/// The final 2x2 / 1x1 systems of the diffusion-form PCR for row K, from the reduced G, H of the last level (W as in
+/// pcrDiffLevel; NLev = pcrLevels(NRow)): the reference's thread K (K < NRow / 2) writes both rows of a 2x2 system,
+/// here each row's thread computes its own row with the same expressions, value() below.
+struct PcrDiffFinal {
+   int Partner = -1; ///< the other row of the 2x2 system; -1: a 1x1 system
+   bool Upper  = false; ///< this row is the first of the two
+   Real Ca = 1, Cb = 0, Det = 1;
+   /// X of this row and Xw[row] of the others
+   __device__ Real value(Real X, const Real *Xw) const {
+      if (Partner < 0)
+         return X / Det;
+      if (Upper)
+         return (Ca * X - Cb * Xw[Partner]) / Det;
+      return (Ca * Xw[Partner] + Cb * X) / Det; // the reference's order: its row K's term first
    }
-   Real *W = Sys + B * 3 * Span;
-   if (Active) {
-      W[0 * Span + K] = G, W[1 * Span + K] = H, W[2 * Span + K] = X;
+};
+__device__ inline PcrDiffFinal pcrDiffFinal(int K, int NRow, int NLev, Real G, Real H, const Real *W, int Span) {
+   PcrDiffFinal F;
+   if (NRow == 1) { // the reference's 1 << -1; defined as the 1x1 solve (TriDiagSolvers.h)
+      F.Det = H + G;
+      return F;
    }
-   __syncthreads();
-   if (!Active)
-      return X;
-   const int Stride = 1 << (NLevels - 1);
-   if (K + Stride < NRow) { // 2x2 system (K, K + Stride), row K
+   const int Stride = 1 << (NLev - 1);
+   if (K + Stride < NRow) { // 2x2 system (K, K + Stride), row K: (Dkps * Xk - DUk * Xkps) / Det
       const int P      = K + Stride;
       const int Kms    = K - Stride;
       const Real Gkms  = Kms < 0 ? 0 : W[0 * Span + Kms];
@@ -146,12 +155,9 @@ __device__ inline Real pcrDiffSolveRow(bool Active, int K, int NRow, Real G, Rea
       const Real Dkps  = W[1 * Span + P] + G + W[0 * Span + P];
       const Real DUk   = -G;
       const Real DLkps = -G;
-      const Real Det   = Dk * Dkps - DLkps * DUk;
-      const Real Xk    = X;
-      const Real Xkps  = W[2 * Span + P];
-      return (Dkps * Xk - DUk * Xkps) / Det;
-   }
-   if (K - Stride >= 0) { // 2x2 system (K - Stride, K), row K
+      F.Det            = Dk * Dkps - DLkps * DUk;
+      F.Partner = P, F.Upper = true, F.Ca = Dkps, F.Cb = DUk;
+   } else if (K - Stride >= 0) { // 2x2 system (K - Stride, K), row K: (-DLkps * Xk + Dk * Xkps) / Det
       const int P      = K - Stride;
       const int Kms    = P - Stride;
       const Real Gp    = W[0 * Span + P];
@@ -160,22 +166,51 @@ __device__ inline Real pcrDiffSolveRow(bool Active, int K, int NRow, Real G, Rea
       const Real Dkps  = H + Gp + G;
       const Real DUk   = -Gp;
       const Real DLkps = -Gp;
-      const Real Det   = Dk * Dkps - DLkps * DUk;
-      const Real Xk    = W[2 * Span + P];
-      const Real Xkps  = X;
-      return (-DLkps * Xk + Dk * Xkps) / Det;
+      F.Det            = Dk * Dkps - DLkps * DUk;
+      F.Partner = P, F.Ca = -DLkps, F.Cb = Dk;
+   } else { // 1x1 system
+      const int Kms   = K - Stride;
+      const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
+      F.Det           = H + Gkms + G;
    }
-   const int Kms   = K - Stride; // 1x1 system
-   const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
-   return X / (H + Gkms + G);
+   return F;
+}
+
+/// PCRDiffusionSolver::solve(Member, Scratch) (TriDiagSolvers.h:377-454) for row K, as pcrSolveRow, for the systems of
+/// one workgroup, which may differ in NRow: NLevWg is the workgroup-uniform number of barrier steps, at least
+/// pcrLevels(NRow) of every system in it (pcrLevels(NRow) itself when they are all alike).  A system that has finished
+/// its own levels keeps joining the barriers without touching the workspace, and reads its last level after them: the
+/// systems own disjoint rows.  One right-hand side, so G, H and X go through the levels together (one barrier per
+/// level, no Alpha / Beta kept).  `Sys` points to row 0 of the thread's system in a workspace of 2 x 3 arrays (G, H, X)
+/// of `Span` doubles (array A of buffer B at Sys[(B * 3 + A) * Span + row]); a caller that reuses it barriers first.
+__device__ inline Real pcrDiffSolveRowRagged(bool Active, int K, int NRow, int NLevWg, Real G, Real H, Real X,
+                                             Real *Sys, int Span) {
+   const int NLev = Active ? pcrLevels(NRow) : 0;
+   int B          = 0;
+   for (int Lev = 1; Lev <= NLevWg; ++Lev) { // workgroup-uniform
+      Real *W = Sys + B * 3 * Span;
+      if (Lev <= NLev) {
+         W[0 * Span + K] = G, W[1 * Span + K] = H, W[2 * Span + K] = X;
+      }
+      __syncthreads();
+      if (Lev < NLev) {
+         const PcrDiffLevel L = pcrDiffLevel(Lev, K, NRow, G, H, W, Span);
+         X                    = X + L.Alpha * W[2 * Span + L.Kmh] + L.Beta * W[2 * Span + L.Kph];
+         B ^= 1; // the next level writes the other buffer; the last level's buffer stays to be read below
+      }
+   }
+   if (!Active)
+      return X;
+   const Real *W = Sys + B * 3 * Span;
+   return pcrDiffFinal(K, NRow, NLev, G, H, W, Span).value(X, W + 2 * Span);
 }
 
 /// Largest PCR level count (pcrLevels(TriDiagMaxRows)): the multi-right-hand-side body keeps one Alpha / Beta per level
 /// in registers, so its level loops have this compile-time bound
 constexpr int TriDiagMaxLevels = 10;
 
-/// pcrDiffSolveRow for NRhs right-hand sides that share G and H (e.g. every tracer of a column): the result for each
-/// right-hand side is bit for bit that of pcrDiffSolveRow on (G, H, X_t).  Everything that depends only on G and H --
+/// pcrDiffSolveRowRagged for NRhs right-hand sides that share G and H (e.g. every tracer of a column): the result for
+/// each right-hand side is bit for bit that of pcrDiffSolveRowRagged on (G, H, X_t).  Everything that depends only on G and H --
 /// Alpha, Beta, NewG, NewH of every level and the final Dk / Dkps / Det -- is computed once; each X_t then goes
 /// through the same levels with the stored Alpha / Beta, Chunk right-hand sides at a time.  LoadX(T) returns X of
 /// right-hand side T of this row and StoreX(T, V) takes its solution (called only when Active).
@@ -190,7 +225,7 @@ __device__ inline void pcrDiffSolveRowMulti(bool Active, int K, int NRow, int NL
    const int NLev = Active ? pcrLevels(NRow) : 0;
    Real Alpha[TriDiagMaxLevels], Beta[TriDiagMaxLevels];
    Real *GH = Sys, *XW = Sys + 4 * Span;
-   // ---- G and H: the levels of pcrDiffSolveRow, keeping Alpha and Beta; the last step writes the reduced G, H
+   // ---- G and H: the levels of pcrDiffSolveRowRagged, keeping Alpha and Beta; the last step writes the reduced G, H
    int B = 0;
 #pragma unroll
    for (int Lev = 1; Lev <= TriDiagMaxLevels; ++Lev) {
@@ -202,67 +237,13 @@ __device__ inline void pcrDiffSolveRowMulti(bool Active, int K, int NRow, int NL
       }
       __syncthreads();
       if (Lev < NLev) {
-         const int Stride     = 1 << Lev;
-         const int HalfStride = 1 << (Lev - 1);
-
-         int Kmh         = K - HalfStride;
-         const Real Gkmh = Kmh < 0 ? 0 : W[0 * Span + Kmh];
-         Kmh             = Kmh < 0 ? 0 : Kmh;
-
-         const int Kms   = K - Stride;
-         const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
-
-         int Kph = K + HalfStride;
-         Kph     = Kph >= NRow ? NRow - 1 : Kph;
-
-         const Real A  = Gkmh / (W[1 * Span + Kmh] + Gkms + Gkmh);
-         const Real Bt = G / (W[1 * Span + Kph] + G + W[0 * Span + Kph]);
-
-         const Real NewG = W[0 * Span + Kph] * Bt;
-         const Real NewH = H + A * W[1 * Span + Kmh] + Bt * W[1 * Span + Kph];
-         G = NewG, H = NewH;
-         Alpha[Lev - 1] = A, Beta[Lev - 1] = Bt;
+         const PcrDiffLevel L = pcrDiffLevel(Lev, K, NRow, G, H, W, Span);
+         Alpha[Lev - 1] = L.Alpha, Beta[Lev - 1] = L.Beta;
          B ^= 1;
       }
    }
-   // ---- the final 2x2 / 1x1 systems: X = (Ca * X - Cb * Xpartner) / Det, or X / Det without a partner (Cb unused)
-   int Partner = -1;
-   Real Ca = 1, Cb = 0, Det = 1;
-   if (Active) {
-      const Real *W = GH + B * 2 * Span;
-      if (NRow == 1) { // the reference's 1 << -1; defined as the 1x1 solve (TriDiagSolvers.h)
-         Det = H + G;
-      } else {
-         const int Stride = 1 << (NLev - 1);
-         if (K + Stride < NRow) { // 2x2 system (K, K + Stride), row K: (Dkps * Xk - DUk * Xkps) / Det
-            const int P      = K + Stride;
-            const int Kms    = K - Stride;
-            const Real Gkms  = Kms < 0 ? 0 : W[0 * Span + Kms];
-            const Real Dk    = H + Gkms + G;
-            const Real Dkps  = W[1 * Span + P] + G + W[0 * Span + P];
-            const Real DUk   = -G;
-            const Real DLkps = -G;
-            Det              = Dk * Dkps - DLkps * DUk;
-            Partner = P, Ca = Dkps, Cb = DUk;
-         } else if (K - Stride >= 0) { // 2x2 system (K - Stride, K), row K: (-DLkps * Xk + Dk * Xkps) / Det
-            const int P      = K - Stride;
-            const int Kms    = P - Stride;
-            const Real Gp    = W[0 * Span + P];
-            const Real Gkms  = Kms < 0 ? 0 : W[0 * Span + Kms];
-            const Real Dk    = W[1 * Span + P] + Gkms + Gp;
-            const Real Dkps  = H + Gp + G;
-            const Real DUk   = -Gp;
-            const Real DLkps = -Gp;
-            Det              = Dk * Dkps - DLkps * DUk;
-            Partner = P, Ca = -DLkps, Cb = Dk; // kept in the reference's order below: Ca * Xpartner + Cb * X
-         } else { // 1x1 system
-            const int Kms   = K - Stride;
-            const Real Gkms = Kms < 0 ? 0 : W[0 * Span + Kms];
-            Det             = H + Gkms + G;
-         }
-      }
-   }
-   const bool Upper = Partner > K; // which of the two 2x2 expressions this row evaluates
+   // ---- the final 2x2 / 1x1 systems, once for every right-hand side
+   const PcrDiffFinal F = Active ? pcrDiffFinal(K, NRow, NLev, G, H, GH + B * 2 * Span, Span) : PcrDiffFinal();
    // ---- every right-hand side through the stored levels
    for (int T0 = 0; T0 < NRhs; T0 += Chunk) {
       if (T0 > 0)
@@ -302,14 +283,7 @@ __device__ inline void pcrDiffSolveRowMulti(bool Active, int K, int NRow, int NL
          for (int J = 0; J < Chunk; ++J) {
             if (T0 + J >= NRhs)
                break;
-            Real V;
-            if (Partner < 0)
-               V = X[J] / Det;
-            else if (Upper)
-               V = (Ca * X[J] - Cb * W[J * Span + Partner]) / Det;
-            else
-               V = (Ca * W[J * Span + Partner] + Cb * X[J]) / Det;
-            Store(T0 + J, V);
+            Store(T0 + J, F.value(X[J], W + J * Span));
          }
       }
    }

@@ -4,23 +4,22 @@
 // neighbours in one row and a wave reads whole runs of each edge's row.  The shear gather loops over the cell's edges
 // in ascending slot order.
 //
-// The implicit solves: lanes along the rows of a column (level KMin + i on lane i), floor(256 / K) columns per workgroup
-// (one for K > 256, up to 1024 lanes), as the PCR array launcher does (kernels/TriDiagKernels.hip).  A lane assembles
-// its row of G and H once and solves every right-hand side of the column with pcrDiffSolveRowMulti
+// The implicit solves: lanes along the rows of a column (level KMin + i on lane i) in the packed-column shape
+// (kernels/PackedColumns.h), as the PCR array launcher (kernels/TriDiagKernels.hip).  A lane assembles its row of G and H
+// once and solves every right-hand side of the column with pcrDiffSolveRowMulti
 // (kernels/TriDiagKernels.h): the G / H recursion, and with it every division except the last, is done once per
 // column instead of once per tracer.  Columns of one workgroup have different depths: the workgroup loops to the
-// largest level count among them and each lane stops updating after its own.
+// largest level count among them (packedLevels) and each lane stops updating after its own.
 //
 // The forced solves (VertMix.h) are further instantiations of the same kernel: the boundary terms change one diagonal
 // entry and one right-hand-side entry per column, read by the lane of row 0 or row N-1; nothing is added per level.
-#include "TriDiagKernels.h"
+#include "PackedColumns.h"
 #include "VertMixKernels.h"
 
 namespace OMEGA {
 
 namespace {
 
-constexpr int MixLanes    = 256;   // lanes a workgroup of short columns fills
 constexpr int MixLdsBytes = 65536; // workspace limit of one solve workgroup
 constexpr int PointBlock  = 256;
 
@@ -119,29 +118,18 @@ struct MixArgs {
 /// the wind stress on X; row N-1: the bottom drag on the diagonal) and the Rayleigh drag on every row's diagonal.
 /// The diagonal goes to the solver where H stood; X = Hr * value keeps the thickness.
 template <int Chunk, bool OnEdge, bool Forced>
-__global__ void __launch_bounds__(TriDiagMaxRows) implicitMixKernel(MixArgs A, int SysPerBlock, int Rows) {
+__global__ void __launch_bounds__(TriDiagMaxRows) implicitMixKernel(MixArgs A, PackedShape P) {
    extern __shared__ Real Lds[];
-   __shared__ int NLevShared;
-   const int T      = threadIdx.x;
-   const int S      = T / A.K;
-   const int I      = T - S * A.K; // row of the column: level Lo + I
-   const long Col   = (long)blockIdx.x * SysPerBlock + S;
-   const bool InSys = T < Rows && Col < A.NCols;
+   const PackedLane L = packedLane(P, A.K, A.NCols);
+   const int S = L.S, I = L.I, Rows = P.Rows; // row I of the column: level Lo + I
+   const long Col = L.Col;
    int Lo = 0, N = 0;
-   if (InSys) {
-      Lo           = A.Lo[Col];
-      const int Hi = A.Hi[Col];
-      if (Lo >= 0 && Lo <= Hi && Hi < A.K)
-         N = Hi - Lo + 1;
+   if (L.InSys) {
+      Lo = A.Lo[Col];
+      N  = packedRows(Lo, A.Hi[Col], A.K);
    }
-   if (T == 0)
-      NLevShared = 0;
-   __syncthreads();
-   if (InSys && I == 0 && N > 0)
-      atomicMax(&NLevShared, pcrLevels(N));
-   __syncthreads();
-   const int NLevWg = NLevShared;
-   const bool Act   = InSys && I < N;
+   const int NLevWg = packedLevels(L.InSys && I == 0, N);
+   const bool Act   = L.InSys && I < N;
 
    Real G = 0, Hr = 0;
    const int Lev = Lo + I;
@@ -210,16 +198,6 @@ __global__ void __launch_bounds__(TriDiagMaxRows) implicitMixKernel(MixArgs A, i
    }
 }
 
-/// Columns per workgroup and the lanes they occupy (as the PCR array launcher)
-struct MixShape {
-   int Sys, Rows, Threads;
-   explicit MixShape(int K) {
-      Sys     = K <= MixLanes ? MixLanes / K : 1;
-      Rows    = Sys * K;
-      Threads = (Rows + 63) / 64 * 64;
-   }
-};
-
 /// Right-hand sides per pass: the fewest of 1, 2, 4, 6, 8 that hold NRhs, within the LDS limit
 int mixChunk(int NRhs, int Rows) {
    const int Cap      = (MixLdsBytes / (int)sizeof(Real) / Rows - 4) / 2;
@@ -232,21 +210,19 @@ int mixChunk(int NRhs, int Rows) {
 }
 
 template <bool OnEdge, bool Forced> void launchMix(const MixArgs &A, hipStream_t Str) {
-   OMEGA_REQUIRE(A.K >= 1 && A.K <= TriDiagMaxRows, "VertMix: NVertLayers = " + std::to_string(A.K) +
-                                                        " is outside the supported 1 <= NVertLayers <= " +
-                                                        std::to_string(TriDiagMaxRows));
+   requirePackedLayers("VertMix", A.K);
    if (A.NCols <= 0 || A.NRhs <= 0)
       return;
-   const MixShape P(A.K);
+   const PackedShape P(A.K);
    const int Chunk = mixChunk(A.NRhs, P.Rows);
-   const dim3 Grid((A.NCols + P.Sys - 1) / P.Sys);
+   const dim3 Grid = P.grid(A.NCols);
    const size_t Bytes = (size_t)(4 + 2 * Chunk) * P.Rows * sizeof(Real);
    switch (Chunk) {
-   case 1: hipLaunchKernelGGL((implicitMixKernel<1, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   case 2: hipLaunchKernelGGL((implicitMixKernel<2, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   case 4: hipLaunchKernelGGL((implicitMixKernel<4, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   case 6: hipLaunchKernelGGL((implicitMixKernel<6, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows); break;
-   default: hipLaunchKernelGGL((implicitMixKernel<8, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P.Sys, P.Rows);
+   case 1: hipLaunchKernelGGL((implicitMixKernel<1, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P); break;
+   case 2: hipLaunchKernelGGL((implicitMixKernel<2, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P); break;
+   case 4: hipLaunchKernelGGL((implicitMixKernel<4, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P); break;
+   case 6: hipLaunchKernelGGL((implicitMixKernel<6, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P); break;
+   default: hipLaunchKernelGGL((implicitMixKernel<8, OnEdge, Forced>), Grid, dim3(P.Threads), Bytes, Str, A, P);
    }
    HIP_CHECK(hipGetLastError());
 }

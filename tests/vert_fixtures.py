@@ -108,7 +108,7 @@ def systems_launch(K):
 
 
 def mix_launch(K, nrhs):
-    """launchMix (MixShape, mixChunk): columns per workgroup, lanes, right-hand sides per pass and its LDS cap, passes,
+    """launchMix (PackedShape of kernels/PackedColumns.h, mixChunk): columns per workgroup, lanes, right-hand sides per pass and its LDS cap, passes,
     dynamic LDS bytes"""
     sys, rows, threads = systems_launch(K)
     cap = (LDS_BYTES // 8 // rows - 4) // 2
