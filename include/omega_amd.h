@@ -904,6 +904,46 @@ int omg_vertmixstep_attach_redi(omg_vertmix_step *ms, omg_redi *r);
  * (omg_stepper_do_step checks again).  The stepper keeps a pointer to r: detach before destroying it. */
 int omg_stepper_attach_redi(omg_stepper *st, omg_redi *r);
 
+/* ---- VertRemap (omega_amd/csrc/VertRemap.h; O/doc/design/VertCoord.md sections 2.6, 2.7, design only): vertical
+ * Lagrangian remapping -- the target thickness of the VertCoord from the column totals of a thickness, and the
+ * conservative PCM / PLM / PPM remap of tracers and velocity from that thickness onto the target.  Level-indexed device
+ * arrays are [rows][pitch] with pitch = omg_level_pitch(NVertLayers).  Every call is asynchronous on stream, allocates
+ * nothing and writes nothing outside the layer ranges.  The object keeps a pointer to v: destroy it before v. ---- */
+typedef struct omg_vremap omg_vremap;
+/* order: 1 PCM, 2 PLM, 3 PPM; max_tracers: the most tracers a call takes (>= 0).  Fails for another order, a negative
+ * max_tracers, a host-only mesh, a VertCoord that is NULL or of another mesh or layer count, and more layers than
+ * omg_vremap_max_layers */
+int omg_vremap_create(const omg_mesh *m, const omg_vcoord *v, int order, int max_tracers, omg_vremap **out);
+int omg_vremap_destroy(omg_vremap *r);
+int omg_vremap_max_layers(int *n);
+/* "LayerThicknessTarget" from layer_thickness_dev [NCellsSize][pitch] and the VertCoord's RefLayerThickness and
+ * VertCoordMovementWeights.  One launch */
+int omg_vremap_compute_target(omg_vremap *r, const double *layer_thickness_dev, void *stream);
+/* tracers_dev [ntracers][NCellsSize][pitch] in place, from layer_thickness_dev onto "LayerThicknessTarget" as it stands.
+ * Fails for ntracers outside 0 .. max_tracers.  One launch whatever ntracers (none for 0) */
+int omg_vremap_remap_tracers(omg_vremap *r, const double *layer_thickness_dev, double *tracers_dev, int ntracers,
+                             void *stream);
+/* normal_velocity_dev [NEdgesSize][pitch] in place, between the means of the two cells' thicknesses and targets on every
+ * edge's level range.  One launch */
+int omg_vremap_remap_velocity(omg_vremap *r, const double *layer_thickness_dev, double *normal_velocity_dev, void *stream);
+/* layer_thickness_dev = "LayerThicknessTarget" on the cells' ranges.  One launch */
+int omg_vremap_adopt_target(omg_vremap *r, double *layer_thickness_dev, void *stream);
+/* the four calls above in that order, in three launches, with the same bits */
+int omg_vremap_remap(omg_vremap *r, double *layer_thickness_dev, double *normal_velocity_dev, double *tracers_dev,
+                     int ntracers, void *stream);
+/* kernel launches the five calls have issued on this object so far */
+int omg_vremap_launch_count(const omg_vremap *r, int64_t *n);
+/* "LayerThicknessTarget" ([NCellsSize][NVertLayers], zero at creation) */
+int omg_vremap_device_ptr(const omg_vremap *r, const char *name, double **dev, size_t *n);
+int omg_vremap_copy_to_device(omg_vremap *r, const char *name, const double *host, size_t n);
+int omg_vremap_copy_to_host(const omg_vremap *r, const char *name, double *host, size_t n);
+/* SplitExplicitStepper::attachVertRemap (omega_amd/csrc/SplitExplicitStepper.h): every step of a "Split-Explicit"
+ * stepper runs omg_vremap_remap on the new time level between the velocity update and the vertical mixing (r NULL:
+ * detach).  Fails for any other stepper type, an r of another mesh or layer count, max_tracers below the stepper's
+ * tracer count, and while a VertAdv is attached to the Tendencies (omg_stepper_do_step checks again).  The stepper keeps
+ * a pointer to r: detach before destroying it. */
+int omg_stepper_attach_vert_remap(omg_stepper *st, omg_vremap *r);
+
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at
  * dev + i * row_pitch (row_pitch 0: nrow).  x holds the right-hand side on entry and the solution on return; only

@@ -1598,6 +1598,76 @@ class Redi(_Handle, _NamedArrays, _ColumnPass):
         return {"C": (m.NCellsSize,), "E": (m.NEdgesSize,), "EK": (m.NEdgesSize, self.K), "CK": (m.NCellsSize, self.K)}[s]
 
 
+class VertRemap(_Handle, _NamedArrays):
+    """VertRemap (omega_amd/csrc/VertRemap.h): vertical Lagrangian remapping -- the target thickness of the VertCoord
+    from the column totals of a thickness ("LayerThicknessTarget", [NCellsSize][K]) and the conservative remap of tracers
+    and velocity from that thickness onto it, `order` 1 PCM, 2 PLM, 3 PPM.  Level-indexed arguments are numpy arrays
+    [rows][K] or device addresses of [rows][level_pitch(K)] doubles; what a call changes in place is a device address
+    (asynchronous on `stream`, nothing returned) or a numpy array (staged, computed, returned)."""
+    _destroy, _arrays = "omg_vremap_destroy", "omg_vremap"
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", max_tracers: int, order: int = 3):
+        self.mesh, self.vcoord, self.order, self.max_tracers = mesh, vcoord, int(order), int(max_tracers)
+        self.K = vcoord.K if vcoord is not None else (mesh.NVertLayers if mesh is not None else 0)
+        self._create("omg_vremap_create", mesh.h if mesh is not None else None, vcoord.h if vcoord is not None else None,
+                     int(order), int(max_tracers))
+
+    @staticmethod
+    def max_layers() -> int:
+        n = C.c_int()
+        _chk(lib().omg_vremap_max_layers(C.byref(n)))
+        return n.value
+
+    def compute_target(self, layer_thickness, stream=None):
+        keep = []
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        _chk(lib().omg_vremap_compute_target(self.h, h, _sh(stream)))
+        if keep:
+            device_synchronize()
+
+    def remap_tracers(self, layer_thickness, tracers, ntracers: int, stream=None):
+        keep, n, nt = [], self.mesh.NCellsSize, max(int(ntracers), 0)
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        p, buf = _stage_levels(tracers, (nt, n), self.K)
+        _chk(lib().omg_vremap_remap_tracers(self.h, h, p, int(ntracers), _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def remap_velocity(self, layer_thickness, normal_velocity, stream=None):
+        keep = []
+        h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
+        p, buf = _stage_levels(normal_velocity, (self.mesh.NEdgesSize,), self.K)
+        _chk(lib().omg_vremap_remap_velocity(self.h, h, p, _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def adopt_target(self, layer_thickness, stream=None):
+        p, buf = _stage_levels(layer_thickness, (self.mesh.NCellsSize,), self.K)
+        _chk(lib().omg_vremap_adopt_target(self.h, p, _sh(stream)))
+        return _read_back(buf, self.K, stream)
+
+    def remap(self, layer_thickness, normal_velocity, tracers, ntracers: int, stream=None):
+        """compute_target, remap_tracers, remap_velocity, adopt_target in three launches; numpy arguments come back as
+        (layer_thickness, normal_velocity, tracers), None in the place of a device address"""
+        n, nt = self.mesh.NCellsSize, max(int(ntracers), 0)
+        ph, bh = _stage_levels(layer_thickness, (n,), self.K)
+        pu, bu = _stage_levels(normal_velocity, (self.mesh.NEdgesSize,), self.K)
+        pt, bt = (None, None) if tracers is None else _stage_levels(tracers, (nt, n), self.K)
+        _chk(lib().omg_vremap_remap(self.h, ph, pu, pt, int(ntracers), _sh(stream)))
+        return tuple(_read_back(b, self.K, stream) for b in (bh, bu, bt))
+
+    def launch_count(self) -> int:
+        """kernel launches the five calls have issued on this object so far"""
+        n = C.c_int64(0)
+        _chk(lib().omg_vremap_launch_count(self.h, C.byref(n)))
+        return n.value
+
+    def _shape(self, name):
+        return (self.mesh.NCellsSize, self.K)
+
+
 def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edges: int, nvertlayers: int):
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""
@@ -1794,6 +1864,13 @@ class TimeStepper(_Handle):
         GentMcWilliams's or PressureGrad's, and unless a VertMixStep with this same `redi` attached is attached."""
         _chk(lib().omg_stepper_attach_redi(self.h, redi.h if redi is not None else None))
         self._redi = redi  # the library keeps a pointer to it
+
+    def attach_vert_remap(self, vert_remap: "VertRemap | None"):
+        """SplitExplicitStepper::attachVertRemap: every step remaps the new time level back onto the VertCoord's target
+        grid (VertRemap.remap) between the velocity update and the vertical mixing (None detaches); raises on any other
+        kind, for another mesh or layer count, too few tracers, and while a VertAdv is attached to the Tendencies."""
+        _chk(lib().omg_stepper_attach_vert_remap(self.h, vert_remap.h if vert_remap is not None else None))
+        self._vert_remap = vert_remap  # the library keeps a pointer to it
 
     def set_fused_transport(self, on: bool):
         """SplitExplicitStepper::UseFusedTransport (default on): the step's thickness and tracer tendencies through

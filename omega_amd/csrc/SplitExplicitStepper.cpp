@@ -109,6 +109,27 @@ void SplitExplicitStepper::attachRedi(Redi *R) {
    RediTerm = R;
 }
 
+void SplitExplicitStepper::requireVertRemapFits(const VertRemap *R, const char *Where) const {
+   const std::string W = std::string(Where) + ": ";
+   OMEGA_REQUIRE(R->Mesh == Mesh && R->NVertLayers == Tend->LayerThicknessTend.Ext[1],
+                 W + "the VertRemap was built for another mesh or layer count");
+   OMEGA_REQUIRE(R->MaxTracers >= Tend->NTracers, W + "the VertRemap has MaxTracers = " + std::to_string(R->MaxTracers) +
+                                                      ", below the stepper's " + std::to_string(Tend->NTracers) + " tracers");
+   OMEGA_REQUIRE(Tend->vertAdv() == nullptr,
+                 W + "a VertAdv is attached to the Tendencies: its vertical transport and the VertRemap would both hold "
+                     "the layers to the coordinate; detach one of them");
+}
+
+void SplitExplicitStepper::attachVertRemap(VertRemap *R) {
+   if (R == nullptr) {
+      Remap = nullptr;
+      return;
+   }
+   OMEGA_REQUIRE(Tend && Mesh && Trc, "SplitExplicitStepper::attachVertRemap: attachData first");
+   requireVertRemapFits(R, "SplitExplicitStepper::attachVertRemap");
+   Remap = R;
+}
+
 void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    OMEGA_REQUIRE(Btr != nullptr, "Split-Explicit doStep: no BarotropicMode is attached: attachBarotropic first");
    if (Mono)
@@ -117,6 +138,8 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
       requireGentMcWilliamsFits(GM, "Split-Explicit doStep");
    if (RediTerm)
       requireRediFits(RediTerm, "Split-Explicit doStep");
+   if (Remap)
+      requireVertRemapFits(Remap, "Split-Explicit doStep");
    requireHealthyWire();
    const int CurLevel = 0, NextLevel = 1;
    const StepArrays A = stepArrays("Split-Explicit", State);
@@ -178,6 +201,8 @@ void SplitExplicitStepper::doStep(OceanState *State, hipStream_t S) {
    }
    // u^{n+1} = (baroclinic u^{n} + Dt*(R_u^{n} - its mean)) + the barotropic velocity the sub-cycle ended with
    Btr->advanceVelocity(A.CurU, Tend->NormalVelocityTend, Dt, A.NextU, S);
+   if (Remap) // the Lagrangian column back onto the coordinate's target grid, before the mixing sees it
+      Remap->remap(A.NextH, A.NextU, A.NextTr, Tend->NTracers, S);
    mixNewLevel(State, S);
    updateTimeLevels(State, S);
    ++NStepsDone;

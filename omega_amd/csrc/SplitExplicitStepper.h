@@ -87,6 +87,18 @@
 // of the new level.  Redi moves tracers only: the velocity and the thickness of the step are those of the unattached
 // step bit for bit.  With nothing attached the step, its launch count and its bits are what they were.
 //
+// With a VertRemap attached (attachVertRemap; VertRemap.h) the step is a vertical Lagrangian one followed by a remap:
+// without a VertAdv the thickness of steps 6-7 moves with the horizontal divergence alone, and between steps 8 and 9 the
+// step gains
+//   8b. R->remap(h[Next], u[Next], NextTracers, NTracers)
+// -- the target thickness of the VertRemap's VertCoord from the column totals of h[Next], the tracers and the velocity of
+// the new level remapped onto it conservatively, and h[Next] set to it: three launches on the step's arrays, nothing
+// copied or allocated.  The implicit mixing of step 9 and the next step then see the regridded column.  A VertAdv on the
+// Tendencies is the other way of holding the layers to the coordinate: the two together are refused, at the attachment
+// and again in every step, and with them a MonotoneAdv that owns that VertAdv (its 3-D form needs it on the Tendencies).
+// The remap comes after everything else of the step that moves the state explicitly, so steps 1-8 are those of the
+// unattached step bit for bit.  With nothing attached the step, its launch count and its bits are what they were.
+//
 // What a step carries to the next one besides the state: nothing of the BarotropicMode -- step 2 writes BtrThickEdge and
 // BtrVelocity on every edge and SSH on every column with layers, and steps 3-4 the rest, before anything reads them --
 // with one exception: SSH of a column that is dry by its layer range but still a cell of the mesh.  computeSSH leaves it
@@ -104,6 +116,7 @@
 #include "MonotoneAdv.h"
 #include "Redi.h"
 #include "TimeStepper.h"
+#include "VertRemap.h"
 
 namespace OMEGA {
 
@@ -155,6 +168,12 @@ class SplitExplicitStepper : public TimeStepper {
    void attachRedi(Redi *R);
    Redi *redi() const { return RediTerm; }
 
+   /// Opt-in (after attachData): step 8b above through R; nullptr detaches.  Refuses (OmegaError) a VertRemap of another
+   /// mesh or layer count, one with MaxTracers below the stepper's tracer count, and a Tendencies with a VertAdv
+   /// attached (all checked again in every step).  The stepper keeps the pointer.
+   void attachVertRemap(VertRemap *R);
+   VertRemap *vertRemap() const { return Remap; }
+
    void doStep(OceanState *State, hipStream_t S) override;
    using TimeStepper::doStep;
 
@@ -164,6 +183,7 @@ class SplitExplicitStepper : public TimeStepper {
    MonotoneAdv *Mono   = nullptr;
    GentMcWilliams *GM  = nullptr;
    Redi *RediTerm      = nullptr;
+   VertRemap *Remap    = nullptr;
    /// what both have in common: the mesh, the layer count and the two tracers of the column pass (ColumnPass.h), and
    /// one set of column fields with a PressureGrad attached to the Tendencies (Tail: the end of that message)
    void requireColumnPassFits(const ColumnPass &C, const std::string &Class, const std::string &W) const;
@@ -171,6 +191,8 @@ class SplitExplicitStepper : public TimeStepper {
                                   const char *Tail) const;
    /// what attachRedi refuses and doStep checks again (the other attachments may have changed since)
    void requireRediFits(const Redi *R, const char *Where) const;
+   /// what attachVertRemap refuses and doStep checks again (a VertAdv may have been attached since)
+   void requireVertRemapFits(const VertRemap *R, const char *Where) const;
    /// what attachGentMcWilliams refuses and doStep checks again (a PressureGrad may have been attached since)
    void requireGentMcWilliamsFits(const GentMcWilliams *G, const char *Where) const;
    /// what attachMonotoneAdv refuses and doStep checks again (the options may have changed since)

@@ -26,6 +26,7 @@
 #include "PressureGrad.h"
 #include "MonotoneAdv.h"
 #include "VertAdv.h"
+#include "VertRemap.h"
 #include "VertMixStep.h"
 #include "BarotropicMode.h"
 #include "SplitExplicitStepper.h"
@@ -101,6 +102,9 @@ struct omg_gm {
 };
 struct omg_redi {
    std::unique_ptr<Redi> R;
+};
+struct omg_vremap {
+   std::unique_ptr<VertRemap> R;
 };
 
 static thread_local std::string LastError;
@@ -2258,6 +2262,85 @@ int omg_vertmixstep_attach_redi(omg_vertmix_step *ms, omg_redi *r) {
    OMG_TRY
    OMG_ARG(ms);
    ms->M->attachRedi(r ? r->R.get() : nullptr);
+   OMG_CATCH
+}
+
+// ---- VertRemap (VertRemap.h)
+int omg_vremap_create(const omg_mesh *m, const omg_vcoord *v, int order, int max_tracers, omg_vremap **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   VertRemapConfig Cfg;
+   Cfg.Order = order;
+   newHandle(out, [&](omg_vremap &H) {
+      H.R.reset(new VertRemap("Default", m->M.get(), v ? v->V.get() : nullptr, max_tracers, Cfg));
+   });
+   OMG_CATCH
+}
+int omg_vremap_destroy(omg_vremap *r) {
+   delete r;
+   return 0;
+}
+int omg_vremap_max_layers(int *n) {
+   OMG_TRY
+   OMG_ARG(n);
+   *n = VertRemap::maxLayers();
+   OMG_CATCH
+}
+int omg_vremap_compute_target(omg_vremap *r, const double *layer_thickness, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness);
+   r->R->computeTarget(levelView(layer_thickness, r->R->Mesh->NCellsSize, r->R->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vremap_remap_tracers(omg_vremap *r, const double *layer_thickness, double *tracers, int ntracers, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness && (tracers || ntracers <= 0));
+   const int N = r->R->Mesh->NCellsSize, K = r->R->NVertLayers;
+   const int NT = ntracers > 0 ? ntracers : 0; // (the class refuses the count; the view needs an extent)
+   r->R->remapTracers(levelView(layer_thickness, N, K), tracerView(tracers, NT, N, K), ntracers, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vremap_remap_velocity(omg_vremap *r, const double *layer_thickness, double *normal_velocity, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness && normal_velocity);
+   const HorzMesh *M = r->R->Mesh;
+   const int K       = r->R->NVertLayers;
+   r->R->remapVelocity(levelView(layer_thickness, M->NCellsSize, K), levelView(normal_velocity, M->NEdgesSize, K),
+                       (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vremap_adopt_target(omg_vremap *r, double *layer_thickness, void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness);
+   r->R->adoptTarget(levelView(layer_thickness, r->R->Mesh->NCellsSize, r->R->NVertLayers), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vremap_remap(omg_vremap *r, double *layer_thickness, double *normal_velocity, double *tracers, int ntracers,
+                     void *stream) {
+   OMG_TRY
+   OMG_ARG(r && layer_thickness && normal_velocity && (tracers || ntracers <= 0));
+   const HorzMesh *M = r->R->Mesh;
+   const int K       = r->R->NVertLayers;
+   const int NT      = ntracers > 0 ? ntracers : 0;
+   r->R->remap(levelView(layer_thickness, M->NCellsSize, K), levelView(normal_velocity, M->NEdgesSize, K),
+               tracerView(tracers, NT, M->NCellsSize, K), ntracers, (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_vremap_launch_count(const omg_vremap *r, int64_t *n) {
+   OMG_TRY
+   OMG_ARG(r && n);
+   *n = r->R->LaunchCount;
+   OMG_CATCH
+}
+static ArrRef vremapLookup(const VertRemap &R, const char *Name) {
+   return findNamed<ArrRef>({{"LayerThicknessTarget", arrRef(R.LayerThicknessTarget)}}, Name, "VertRemap: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_vremap_copy_to_host, omg_vremap_copy_to_device, omg_vremap_device_ptr, omg_vremap, r,
+                 vremapLookup(*r->R, name))
+int omg_stepper_attach_vert_remap(omg_stepper *st, omg_vremap *r) {
+   OMG_TRY
+   OMG_ARG(st);
+   splitExplicit(st, "attachVertRemap")->attachVertRemap(r ? r->R.get() : nullptr);
    OMG_CATCH
 }
 
