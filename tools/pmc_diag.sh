@@ -8,24 +8,16 @@
 #   ta-tcp  texture-addresser / L1 path (four passes of two counters of one block)
 #   usage (through gpurun): bash tools/pmc_diag.sh <tag> <sq|ta-tcp|all> [bench.py args]      (one script for the former
 #   pmc_diag.sh + pmc_diag2.sh; a variant build is selected with OMEGA_AMD_LIB=.../libomega_amd_x.so in the environment)
-set -o pipefail
-TAG=${1:?tag}; MODE=${2:?sq|ta-tcp|all}; shift 2
-cd "$(dirname "$0")/.."
-export TMPDIR=/tmp
+NAME=diag
 OUT=gpurun_out
-mkdir -p $OUT
+OUT_DIR=$OUT
+. "$(dirname "$0")/profile_lib.sh"
+MODE=${1:?sq|ta-tcp|all}; shift
 ARGS="--full --steps 4 --warmup 1 --rk4-steps 0 --no-cpu-baseline --no-live-traffic --realistic none $*"
 PASSES=""
 pass() { # name counters...
-   n=$1; shift
-   timeout -k 10 150 rocprofv3 --pmc "$@" --output-format csv -d $OUT/${TAG}_$n -o p -- python3 bench.py $ARGS > $OUT/${TAG}_$n.log 2>&1
-   rc=$?
-   echo "[diag] pass $n rc=$rc"
-   if [ $rc -ne 0 ]; then
-      echo "[diag] pass $n FAILED (rc $rc; 124 = timeout): last lines of its log" >&2
-      tail -20 $OUT/${TAG}_$n.log >&2
-      exit $rc
-   fi
+   local n=$1; shift
+   step $n 150 rocprofv3 --pmc "$@" --output-format csv -d $OUT/${TAG}_$n -o p -- python3 bench.py $ARGS
    PASSES="$PASSES $n"
 }
 if [ "$MODE" = sq ] || [ "$MODE" = all ]; then
@@ -37,17 +29,4 @@ if [ "$MODE" = ta-tcp ] || [ "$MODE" = all ]; then
    pass tcp1 TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum GRBM_GUI_ACTIVE
    pass tcp2 TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum GRBM_GUI_ACTIVE
 fi
-DIAG_OUT=$OUT DIAG_TAG=$TAG DIAG_PASSES="$PASSES" python3 - <<'PY'
-import collections, csv, glob, os, sys
-sys.path.insert(0, ".")
-from tools.summarise_profile import short
-out, tag = os.environ["DIAG_OUT"], os.environ["DIAG_TAG"]
-for sub in os.environ["DIAG_PASSES"].split():
-    rows = collections.defaultdict(lambda: collections.defaultdict(list))
-    for f in glob.glob(f"{out}/{tag}_{sub}/**/*counter_collection.csv", recursive=True):
-        for r in csv.DictReader(open(f)):
-            rows[short(r["Kernel_Name"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
-    for k, v in sorted(rows.items()):
-        if "Body" in k:
-            print(sub, k[:70], {c: round(sum(x) / len(x), 1) for c, x in v.items()})
-PY
+python3 tools/summarise_profile.py passes --out-dir $OUT --tag $TAG $PASSES

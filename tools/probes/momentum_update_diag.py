@@ -28,84 +28,28 @@ Bytes model per cell-level of a hexagon mesh (3 edge rows per cell), 8 B values,
           [--warmup 10] [--local-order kd] [--hyperdiff 1] [--out FILE]
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-import omega_amd as oa  # noqa: E402
-from omega_amd.meshgen import planar_hex  # noqa: E402
-
-PEAK_TBS = 8.0
+from probe_rig import PEAK_TBS, Qu30Rig, add_common_args, emit, oa, summarise, with_rate
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--nx", type=int, default=680)
-    ap.add_argument("--levels", type=int, default=80)
-    ap.add_argument("--tracers", type=int, default=6)
-    ap.add_argument("--nsub", type=int, default=30)
-    ap.add_argument("--dt", type=float, default=600.0)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--local-order", default="kd")
+    add_common_args(ap, nx=680, levels=80, tracers=6, nsub=30, dt=600.0, iters=50, warmup=10, local_order="kd")
     ap.add_argument("--hyperdiff", type=int, default=1, help="TracerHyperDiffTendencyEnable: 0 puts the tracer update in launch 1")
-    ap.add_argument("--out", default="")
-    a = ap.parse_args()
-    K, NT = a.levels, a.tracers
-    oa.device_init(0)
-    layer = 50.0
-    g = planar_hex(a.nx, a.nx, 30.0e3, bottom_depth=layer * K)
-    n = int(g["nCells"])
-    rng = np.random.default_rng(2026)
-    min_level = np.ones(n, np.int32)
-    max_level = np.where(rng.random(n) < 0.6, K, rng.integers(5, K + 1, n)).astype(np.int32)
-    decomp = oa.Decomp(oa.GlobalMesh(g), 1, 0, 3, local_order=a.local_order)
-    mesh = oa.HorzMesh(decomp, K)
-    ns, nes = mesh.NCellsSize, mesh.NEdgesSize
-    state = oa.OceanState(mesh, None, K, 2)
-    tracers = oa.Tracers(mesh, None, K, NT, 2)
-    h0, u0 = layer + rng.uniform(-1.0e-3, 1.0e-3, (ns, K)), rng.uniform(-1.0e-3, 1.0e-3, (nes, K))
-    tr0 = rng.uniform(-1.0, 1.0, (NT, ns, K))
-
-    def reset():
-        for lvl in (0, 1):
-            state.copy_to_device(h0, u0, lvl)
-            tracers.copy_to_device(tr0, lvl)
-
-    reset()
-    vc = oa.VertCoord(mesh, K, 1026.0, "Uniform", min_level, max_level, decomp=decomp)
+    a = ap.parse_args(argv)
+    w = Qu30Rig(a, bottom="layers")
+    K, NT, mesh, ns, state, tracers, vc, reset = w.K, w.NT, w.mesh, w.ns, w.state, w.tracers, w.vc, w.reset
     bm = oa.BarotropicMode(mesh, vc)
     cfg = oa.default_config(TracerHyperDiffTendencyEnable=a.hyperdiff)
-    aux = oa.AuxiliaryState(mesh, None, K, NT)
-    aux.set_options(cfg.FluxThicknessUpwind, cfg.FluxTracerUpwind, cfg.WindInterpIsotropic)
-    tend = oa.Tendencies(mesh, K, NT, cfg)
-    stream = oa.Stream()
-    nc, ne, pitch = mesh.NCellsAll, mesh.NEdgesAll, oa.level_pitch(K)
+    aux, tend = w.tendencies(cfg)
+    stream = w.stream
+    nc, ne, pitch = w.nc, w.ne, w.P
     coeff = oa.coeff_seconds(1.0, a.dt)
     h_cur, h_next = state.device_ptr(0, 0), state.device_ptr(0, 1)
     tr_cur, tr_next = tracers.device_ptr(0), tracers.device_ptr(1)
     h_tend, tr_tend = tend.device_ptr(0)[0], tend.device_ptr(2)[0]
     sh = stream.h.value  # (the raw-pointer update calls take the stream as an address)
-
-    def timed(fn, before=None, every=0):
-        for _ in range(a.warmup):
-            fn()
-        stream.synchronize()
-        evs = [[oa.Event() for _ in range(2)] for _ in range(a.iters)]
-        for i, (e0, e1) in enumerate(evs):
-            if before and (i == 0 or (every and i % every == 0)):
-                stream.synchronize()
-                before()
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-        stream.synchronize()
-        per = np.array([e0.elapsed_ms(e1) for e0, e1 in evs])
-        return {"ms_median": float(np.median(per)), "ms_min": float(per.min()), "ms_max": float(per.max())}
 
     def rhs():
         tend.compute_all_tendencies(state, aux, tracers, stream=stream)
@@ -134,18 +78,16 @@ def main():
            "dt": a.dt, "coeff": coeff, "local_order": a.local_order, "iters": a.iters, "warmup": a.warmup,
            "peak_TBs": PEAK_TBS, "tracer_hyperdiffusion": hyper, "calls": {}}
     c = res["calls"]
-    c["rhs_fused"] = timed(rhs)
-    c["momentum_rhs"] = timed(momentum)
-    c["sequence_1"] = timed(sequence)
-    c["transport_alone"] = timed(transport)
-    c["folded_keep"] = timed(lambda: folded(True))
-    c["folded_drop"] = timed(lambda: folded(False))
-    c["sequence_2"] = timed(sequence)
+    c["rhs_fused"] = w.time([rhs])[0]
+    c["momentum_rhs"] = w.time([momentum])[0]
+    c["sequence_1"] = w.time([sequence])[0]
+    c["transport_alone"] = w.time([transport])[0]
+    c["folded_keep"] = w.time([lambda: folded(True)])[0]
+    c["folded_drop"] = w.time([lambda: folded(False)])[0]
+    c["sequence_2"] = w.time([sequence])[0]
     for name, key in (("sequence_1", "sequence"), ("sequence_2", "sequence"), ("transport_alone", "transport"),
                       ("folded_keep", "folded_keep"), ("folded_drop", "folded_drop")):
-        c[name]["algorithmic_GB"] = nbytes[key] / 1.0e9
-        c[name]["TBs"] = c[name]["algorithmic_GB"] / c[name]["ms_median"]
-        c[name]["share_of_8TBs"] = c[name]["TBs"] / PEAK_TBS
+        with_rate(c[name], nbytes[key])
 
     # ---- the same bits on the timed workload
     def same(x, y):
@@ -164,8 +106,8 @@ def main():
     want = (state.copy_to_host(1)[0][:nc].copy(), tracers.copy_to_host(1)[:, :nc].copy(), tend.get(0)[:nc].copy(),
             tend.get(2)[:, :nc].copy())
     for keep in (True, False):
-        state.copy_to_device(h0, u0, 1)
-        tracers.copy_to_device(tr0, 1)
+        state.copy_to_device(w.h0, w.u0, 1)
+        tracers.copy_to_device(w.tr0, 1)
         folded(keep)
         stream.synchronize()
         tag = "keep" if keep else "drop"
@@ -185,7 +127,7 @@ def main():
     for name, mom, fold in combos:
         se.set_momentum_rhs(mom)
         se.set_folded_updates(fold)
-        c[name] = timed(lambda: se.do_step(state, stream=stream), before=reset, every=5)
+        c[name] = w.time([lambda: se.do_step(state, stream=stream)], before=reset, every=5)[0]
         reset()
         for _ in range(3):
             se.do_step(state, stream=stream)
@@ -197,8 +139,7 @@ def main():
     r = c["rhs_fused"]["ms_median"]
     for t in c.values():
         t["fraction_of_rhs"] = t["ms_median"] / r
-    seq = 0.5 * (c["sequence_1"]["ms_median"] + c["sequence_2"]["ms_median"])
-    seq_spread = abs(c["sequence_1"]["ms_median"] - c["sequence_2"]["ms_median"])
+    seq, seq_spread = summarise(c, ["sequence"]).values()
     step = 0.5 * (c["step_off_off"]["ms_median"] + c["step_off_off_again"]["ms_median"])
     step_spread = abs(c["step_off_off"]["ms_median"] - c["step_off_off_again"]["ms_median"])
     s = res["summary"] = {"rhs_ms": r, "momentum_ms": c["momentum_rhs"]["ms_median"],
@@ -213,12 +154,7 @@ def main():
         s[name + "_saving_ms"] = step - c[name]["ms_median"]
         s[name + "_faster_by_more_than_the_spread"] = bool(step - c[name]["ms_median"] > step_spread)
     s["all_bitwise_equal"] = bool(all(v if isinstance(v, bool) else all(v.values()) for v in eq.values()))
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f_:
-            f_.write(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -43,59 +43,20 @@ Bytes model per cell-level of a hexagon mesh (3 edge rows per cell), 8 B values,
           [--dt 600] [--iters 50] [--warmup 10] [--local-order kd] [--only-kernels] [--no-steps] [--out FILE]
 """
 import argparse
-import json
-import os
-import sys
 from types import SimpleNamespace
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-import omega_amd as oa  # noqa: E402
-from omega_amd.meshgen import planar_hex  # noqa: E402
-
-PEAK_TBS = 8.0
+from probe_rig import PEAK_TBS, Qu30Rig, add_common_args, emit, oa, summarise, with_rate
 
 
 def workload(a, ragged, ref_thickness, **config):
-    """the mesh, state and Tendencies (of default_config(**config)) every form times on"""
-    w = SimpleNamespace(a=a, K=a.levels, NT=a.tracers)
-    K, NT = w.K, w.NT
-    oa.device_init(0)
-    layer = 50.0
-    w.g = g = planar_hex(a.nx, a.nx, 30.0e3, bottom_depth=layer * K)
-    rng = np.random.default_rng(2026)
-    ranges = ()
-    if ragged:
-        n = int(g["nCells"])
-        ranges = (np.ones(n, np.int32), np.where(rng.random(n) < 0.6, K, rng.integers(5, K + 1, n)).astype(np.int32))
-    decomp = oa.Decomp(oa.GlobalMesh(g), 1, 0, 3, local_order=a.local_order)
-    w.mesh = mesh = oa.HorzMesh(decomp, K)
-    w.ns, nes = mesh.NCellsSize, mesh.NEdgesSize
-    w.state = oa.OceanState(mesh, None, K, 2)
-    w.tracers = oa.Tracers(mesh, None, K, NT, 2)
-    h0, u0 = layer + rng.uniform(-1.0e-3, 1.0e-3, (w.ns, K)), rng.uniform(-1.0e-3, 1.0e-3, (nes, K))
-    tr0 = rng.uniform(-1.0, 1.0, (NT, w.ns, K))
-
-    def reset():
-        for lvl in (0, 1):
-            w.state.copy_to_device(h0, u0, lvl)
-            w.tracers.copy_to_device(tr0, lvl)
-
-    w.reset = reset
-    reset()
-    w.vc = oa.VertCoord(mesh, K, 1026.0, "Uniform", *ranges, decomp=decomp)
-    if ref_thickness:
-        w.vc.set("RefLayerThickness", np.full((w.ns, K), layer))
-    w.bm = oa.BarotropicMode(mesh, w.vc)
-    w.cfg = cfg = oa.default_config(**config)
-    w.aux = oa.AuxiliaryState(mesh, None, K, NT)
-    w.aux.set_options(cfg.FluxThicknessUpwind, cfg.FluxTracerUpwind, cfg.WindInterpIsotropic)
-    w.tend = oa.Tendencies(mesh, K, NT, cfg)
-    w.hyper = bool(cfg.TracerHyperDiffTendencyEnable)
-    w.stream = oa.Stream()
-    w.nc = mesh.NCellsAll
+    """the rig and the Tendencies (of default_config(**config)) every form times on"""
+    w = Qu30Rig(a, bottom="layers", ragged=ragged, ref_thickness=ref_thickness)
+    w.bm = oa.BarotropicMode(w.mesh, w.vc)
+    w.cfg = oa.default_config(**config)
+    w.aux, w.tend = w.tendencies(w.cfg)
+    w.hyper = bool(w.cfg.TracerHyperDiffTendencyEnable)
+    w.stream  # (made here, after the Tendencies)
     w.h_old, w.h_new, w.u_new = w.state.device_ptr(0, 0), w.state.device_ptr(0, 1), w.state.device_ptr(1, 1)
     w.tr_ptr, w.tend_ptr = w.tracers.device_ptr(0), w.tend.device_ptr(2)[0]
     return w
@@ -278,42 +239,17 @@ def form_ho(a):
 FORMS = {"2d": form_2d, "3d": form_3d, "ho": form_ho}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--form", choices=tuple(FORMS), default="2d")
-    ap.add_argument("--nx", type=int, default=680)
-    ap.add_argument("--levels", type=int, default=80)
-    ap.add_argument("--tracers", type=int, default=6)
-    ap.add_argument("--nsub", type=int, default=30)
-    ap.add_argument("--dt", type=float, default=600.0)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--local-order", default="kd")
-    ap.add_argument("--only-kernels", action="store_true")
+    add_common_args(ap, only_kernels=True, nx=680, levels=80, tracers=6, nsub=30, dt=600.0, iters=50, warmup=10, local_order="kd")
     ap.add_argument("--no-steps", action="store_true", help="the calls alone: no Split-Explicit step is timed")
-    ap.add_argument("--out", default="")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if (a.only_kernels and a.form == "2d") or (a.no_steps and a.form != "ho"):
         ap.error(f"--form {a.form} has no such mode")
     form = FORMS[a.form](a)
     w = form.w
     stream, nc, K = w.stream, w.nc, w.K
-
-    def timed(fn, before=None, every=0):
-        for _ in range(a.warmup):
-            fn()
-        stream.synchronize()
-        evs = [[oa.Event() for _ in range(2)] for _ in range(a.iters)]
-        for i, (e0, e1) in enumerate(evs):
-            if before and (i == 0 or (every and i % every == 0)):
-                stream.synchronize()
-                before()
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-        stream.synchronize()
-        per = np.array([e0.elapsed_ms(e1) for e0, e1 in evs])
-        return {"ms_median": float(np.median(per)), "ms_min": float(per.min()), "ms_max": float(per.max())}
 
     res = {"probe": form.probe, "ncells": nc, "nedges": w.mesh.NEdgesAll, "levels": K, "tracers": w.NT, "nsub": a.nsub,
            "dt": a.dt, "local_order": a.local_order, "iters": a.iters, "warmup": a.warmup, "peak_TBs": PEAK_TBS,
@@ -334,33 +270,23 @@ def main():
                 if finish:
                     finish(t)
                 if nbytes:
-                    t["algorithmic_GB"] = nc * K * nbytes / 1.0e9
-                    t["TBs"] = t["algorithmic_GB"] / t["ms_median"]
-                    t["share_of_8TBs"] = t["TBs"] / PEAK_TBS
+                    with_rate(t, nc * K * nbytes)
         return [name for name, *_ in cases]
 
-    keys = rounds(form.calls, timed)
+    keys = rounds(form.calls, lambda fn: w.time([fn])[0])
     if not a.no_steps:
         # whole steps (the calm start again every 5 steps, as in transport_diag.py)
         keys += rounds([(name, st, 0, setup) for name, st, setup in form.steps()],
-                       lambda st: timed(lambda: st.do_step(w.state, stream=stream), before=w.reset, every=5))
+                       lambda st: w.time([lambda: st.do_step(w.state, stream=stream)], before=w.reset, every=5)[0])
         stream.synchronize()
     si = form.mono.get("ScaleIn")[:, :nc]
     res["scale_in_finite"] = bool(np.isfinite(si).all())
     res["scale_in_limited_fraction"] = float((si < 1.0).mean())
     if hasattr(form, "extras"):
         form.extras(res)
-    s = res["summary"] = {}
-    for k in keys:
-        s[k + "_ms"] = 0.5 * (c[k + "_1"]["ms_median"] + c[k + "_2"]["ms_median"])
-        s[k + "_spread_ms"] = abs(c[k + "_1"]["ms_median"] - c[k + "_2"]["ms_median"])
+    s = res["summary"] = summarise(c, keys)
     form.derive(s)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f_:
-            f_.write(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -6,30 +6,21 @@ Algorithmic bytes per row: 40 for the general form (DL, D, DU, X read, X written
    python tools/probes/tridiag_diag.py [--iters 50] [--warmup 10] [--sizes qu30_k80,...] [--out FILE]
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
+from probe_rig import PEAK_TBS, add_common_args, emit, oa, timed, with_rate
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-import omega_amd as oa  # noqa: E402
-
-PEAK_TBS = 8.0
 BYTES = {"general": 40, "diffusion": 32}
 SOLVERS = [("general", "pcr"), ("diffusion", "pcr"), ("general", "thomas"), ("diffusion", "thomas")]
 SIZES = [("qu30_k80", 462400, 80, 80), ("qu30_k60_p64", 462400, 60, 64)] + \
         [(f"ref_{nb}x64", nb, 64, 64) for nb in (500, 1000, 5000, 10000)]
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
+    add_common_args(ap, iters=50, warmup=10)
     ap.add_argument("--sizes", default="", help="comma-separated case names (default: all)")
-    ap.add_argument("--out", default="")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     only = set(filter(None, a.sizes.split(",")))
     oa.device_init(0)
     rng = np.random.default_rng(2026)
@@ -60,28 +51,10 @@ def main():
                 def fn():
                     oa.tridiag_diff_solve(p["g"], p["h"], p["x"], algorithm=algo, stream=stream, nbatch=nb, nrow=n,
                                           row_pitch=pitch)
-            for _ in range(a.warmup):
-                fn()
-            stream.synchronize()
-            evs = [oa.Event() for _ in range(a.iters + 1)]
-            evs[0].record(stream)
-            for i in range(a.iters):
-                fn()
-                evs[i + 1].record(stream)
-            stream.synchronize()
-            per = np.array([evs[i].elapsed_ms(evs[i + 1]) for i in range(a.iters)])
-            med = float(np.median(per))
-            gb = nb * n * BYTES[form] / 1.0e9
-            case[f"{algo}_{form}"] = {"ms_median": med, "ms_min": float(per.min()), "ms_max": float(per.max()),
-                                      "algorithmic_GB": gb, "TBs": gb / med, "share_of_8TBs": gb / med / PEAK_TBS}
+            case[f"{algo}_{form}"] = with_rate(timed(stream, [fn], a.iters, a.warmup, successive=True)[0], nb * n * BYTES[form])
         res["cases"][name] = case
         del bufs
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

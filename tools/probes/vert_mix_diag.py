@@ -15,57 +15,25 @@ Algorithmic bytes (each array touched once):
    python tools/probes/vert_mix_diag.py [--nx 680] [--levels 80] [--tracers 6] [--iters 50] [--warmup 10] [--out FILE]
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-import omega_amd as oa  # noqa: E402
-from omega_amd.meshgen import planar_hex  # noqa: E402
-
-PEAK_TBS = 8.0
+from probe_rig import PEAK_TBS, Qu30Rig, active_levels, add_common_args, emit, oa, with_rate
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--nx", type=int, default=680)
-    ap.add_argument("--levels", type=int, default=80)
-    ap.add_argument("--tracers", type=int, default=6)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--out", default="")
-    a = ap.parse_args()
-    K, NT = a.levels, a.tracers
-    P = oa.level_pitch(K)
-    oa.device_init(0)
-    g = planar_hex(a.nx, a.nx, 30.0e3)
-    n = int(g["nCells"])
-    rng = np.random.default_rng(2026)
-    min_level = np.ones(n, np.int32)
-    max_level = np.where(rng.random(n) < 0.6, K, rng.integers(5, K + 1, n)).astype(np.int32)
-    gm = oa.GlobalMesh(g)
-    decomp = oa.Decomp(gm, 1, 0, 3)
-    mesh = oa.HorzMesh(decomp, K)
-    ns, nes, nown, eown = mesh.NCellsSize, mesh.NEdgesSize, mesh.NCellsOwned, mesh.NEdgesOwned
-    state = oa.OceanState(mesh, None, K, 2)
-    tracers = oa.Tracers(mesh, None, K, NT, 2)
-    h = rng.uniform(1.0, 50.0, (ns, K))
-    state.copy_to_device(h, rng.uniform(-0.05, 0.05, (nes, K)), 0)
-    tr = np.concatenate([rng.uniform(-2.0, 30.0, (1, ns, K)), rng.uniform(30.0, 38.0, (1, ns, K)),
-                         rng.uniform(-1.0, 1.0, (NT - 2, ns, K))])
-    tracers.copy_to_device(tr, 0)
-    del tr
-    vc = oa.VertCoord(mesh, K, 1026.0, "Uniform", min_level, max_level, decomp=decomp)
+    add_common_args(ap, nx=680, levels=80, tracers=6, iters=50, warmup=10)
+    a = ap.parse_args(argv)
+    w = Qu30Rig(a, fields="rough", tracers=((-2.0, 30.0), (30.0, 38.0)))
+    K, NT, P, mesh, nes, state, tracers, vc, rng = w.K, w.NT, w.P, w.mesh, w.nes, w.state, w.tracers, w.vc, w.rng
+    nown, eown, h = mesh.NCellsOwned, mesh.NEdgesOwned, w.h0
     vc_full = oa.VertCoord(mesh, K, 1026.0, "Uniform")
     eos = oa.Eos(mesh, K, "teos10")
     vc.compute_column(state, tracers, eos, kdisp=1)
     vm = oa.VertMix(mesh, vc)
     vm_full = oa.VertMix(mesh, vc_full)
     ut = oa.DeviceBuffer(np.pad(rng.uniform(-0.05, 0.05, (nes, K)), ((0, 0), (0, P - K))))
-    stream = oa.Stream()
+    stream = w.stream
     hp, up, trp = state.device_ptr(0, 0), state.device_ptr(1, 0), tracers.device_ptr(0)
     vm.compute_bvf(eos, stream=stream)
     vm.compute(up, ut.ptr, stream=stream)
@@ -94,31 +62,9 @@ def main():
         "separate_pcr_x%d" % NT: separate,
     }
 
-    def timed(fns):
-        """median / min / max ms of each fn, the fns alternating in one loop"""
-        for _ in range(a.warmup):
-            for fn in fns:
-                fn()
-        stream.synchronize()
-        evs = [[oa.Event() for _ in range(2)] for _ in range(a.iters * len(fns))]
-        i = 0
-        for _ in range(a.iters):
-            for fn in fns:
-                evs[i][0].record(stream)
-                fn()
-                evs[i][1].record(stream)
-                i += 1
-        stream.synchronize()
-        out = []
-        for j in range(len(fns)):
-            per = np.array([evs[r * len(fns) + j][0].elapsed_ms(evs[r * len(fns) + j][1]) for r in range(a.iters)])
-            out.append({"ms_median": float(np.median(per)), "ms_min": float(per.min()), "ms_max": float(per.max())})
-        return out
-
-    lo, hi = vc.get("MinLayerCell")[:nown], vc.get("MaxLayerCell")[:nown]
-    active = int(np.sum(hi - lo + 1))
-    elo, ehi = vc.get("MinLayerEdgeBot")[:eown], vc.get("MaxLayerEdgeTop")[:eown]
-    eactive = int(np.sum(np.where((elo >= 0) & (elo <= ehi), ehi - elo + 1, 0)))
+    # (the owned elements: the rows of the separate launches)
+    active = active_levels(vc.get("MinLayerCell")[:nown], vc.get("MaxLayerCell")[:nown])
+    eactive = active_levels(vc.get("MinLayerEdgeBot")[:eown], vc.get("MaxLayerEdgeTop")[:eown])
     cl, el = mesh.NCellsAll * K, mesh.NEdgesAll * K
     gb = {"bvf": 32 * cl, "coefficients": 32 * cl + 16 * el, "tracer_pass": (16 + 16 * NT) * active,
           "tracer_pass_full_columns": (16 + 16 * NT) * nown * K, "velocity_pass": 16 * eactive + 16 * cl,
@@ -130,22 +76,14 @@ def main():
     groups = [["bvf"], ["coefficients"], ["velocity_pass"],
               ["tracer_pass", "tracer_pass_full_columns", "separate_pcr_x%d" % NT]]
     for grp in groups:
-        for name, t in zip(grp, timed([calls[x] for x in grp])):
-            t["algorithmic_GB"] = gb[name] / 1.0e9
-            t["TBs"] = t["algorithmic_GB"] / t["ms_median"]
-            t["share_of_8TBs"] = t["TBs"] / PEAK_TBS
-            res["calls"][name] = t
+        for name, t in zip(grp, w.time([calls[x] for x in grp])):
+            res["calls"][name] = with_rate(t, gb[name])
     assert set(res["calls"]) == set(names)
     sepn = "separate_pcr_x%d" % NT
     res["full_columns_over_separate"] = res["calls"]["tracer_pass_full_columns"]["ms_median"] / \
         res["calls"][sepn]["ms_median"]
     res["tracer_pass_over_separate"] = res["calls"]["tracer_pass"]["ms_median"] / res["calls"][sepn]["ms_median"]
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

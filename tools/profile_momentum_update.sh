@@ -7,19 +7,7 @@
 # after it.
 #   usage: [OUT_DIR=dir] bash tools/profile_momentum_update.sh <tag> [momentum_update_diag.py args]
 #   -> $OUT_DIR/<tag>_*   (OUT_DIR defaults to build/profile_out, which git ignores)
-set -o pipefail
-TAG=${1:?tag}; shift
-cd "$(dirname "$0")/.."
-export TMPDIR=/tmp
-OUT=${OUT_DIR:-build/profile_out}
-mkdir -p $OUT
-timeout -k 10 540 python3 tools/probes/momentum_update_diag.py "$@" --out $OUT/${TAG}_momentum_update_diag_qu30.json > $OUT/${TAG}_momentum_update_diag.log 2>&1
-rc=$?
-echo "[momentum_update] diag rc=$rc"
-if [ $rc -ne 0 ]; then
-   echo "[momentum_update] diag FAILED (rc $rc; 124 = timeout): last lines of its log" >&2
-   tail -20 $OUT/${TAG}_momentum_update_diag.log >&2
-   exit $rc
-fi
+NAME=momentum_update LOG=momentum_update_
+. "$(dirname "$0")/profile_lib.sh"
+step diag 540 python3 tools/probes/momentum_update_diag.py "$@" --out $OUT/${TAG}_momentum_update_diag_qu30.json
 cat $OUT/${TAG}_momentum_update_diag_qu30.json
-exit 0

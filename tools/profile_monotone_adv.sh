@@ -7,15 +7,9 @@
 # after it.
 #   usage: [OUT_DIR=dir] bash tools/profile_monotone_adv.sh <tag> [--form 2d|3d|ho] [monotone_adv_diag.py args]
 #   -> $OUT_DIR/<tag>_*   (OUT_DIR defaults to build/profile_out, which git ignores)
-set -o pipefail
-TAG=${1:?tag}; shift
-cd "$(dirname "$0")/.."
-export TMPDIR=/tmp
-OUT=${OUT_DIR:-build/profile_out}
-mkdir -p $OUT
 FORM=2d
 prev=
-for arg in "$@"; do
+for arg in "${@:2}"; do
    [ "$prev" = --form ] && FORM=$arg
    case $arg in --form=*) FORM=${arg#--form=};; esac
    prev=$arg
@@ -26,34 +20,23 @@ case $FORM in
    ho) NAME=monotone_adv_ho;;
    *) echo "unknown form '$FORM'" >&2; exit 2;;
 esac
-
-step() {  # <label> <seconds> <log> <command...>: the command under its own time limit; the script ends if it fails
-   local label=$1 limit=$2 log=$3; shift 3
-   timeout -k 10 $limit "$@" > $log 2>&1
-   local rc=$?
-   echo "[$NAME] $label rc=$rc"
-   if [ $rc -ne 0 ]; then
-      echo "[$NAME] $label FAILED (rc $rc; 124 = timeout): last lines of its log" >&2
-      tail -20 $log >&2
-      exit $rc
-   fi
-}
-
+LOG=${NAME}_
+. "$(dirname "$0")/profile_lib.sh"
 JSON=$OUT/${TAG}_${NAME}_diag_qu30.json
-step diag 540 $OUT/${TAG}_${NAME}_diag.log python3 tools/probes/monotone_adv_diag.py "$@" --out $JSON
+step diag 540 python3 tools/probes/monotone_adv_diag.py "$@" --out $JSON
 cat $JSON
 [ $FORM = 2d ] && exit 0
-step trace 300 $OUT/${TAG}_${NAME}_trace.log rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_${NAME}_trace -o t -- \
-   python3 tools/probes/monotone_adv_diag.py "$@" --only-kernels --iters 20
+trace python3 tools/probes/monotone_adv_diag.py "$@" --only-kernels --iters 20
 # the tile kernels' mean durations go into the record as "kernel_trace_ms"
 python3 - $OUT/${TAG}_${NAME}_trace $JSON <<'PY'
-import csv, glob, json, re, sys
+import json, re, sys
+sys.path.insert(0, ".")
+from tools.summarise_profile import kernel_stats
 rows = {}
-for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):
-    for r in csv.DictReader(open(f)):
-        m = re.search(r"(Mono\w+Body\w*(?:<[\w, ]+>)?)", r["Name"])
-        if m:
-            rows[m.group(1)] = {"calls": int(r["Calls"]), "mean_ms": float(r["AverageNs"]) / 1.0e6}
+for r in kernel_stats(sys.argv[1]):
+    m = re.search(r"(Mono\w+Body\w*(?:<[\w, ]+>)?)", r["Name"])
+    if m:
+        rows[m.group(1)] = {"calls": int(r["Calls"]), "mean_ms": float(r["AverageNs"]) / 1.0e6}
 rec = json.load(open(sys.argv[2]))
 rec["kernel_trace_ms"] = rows
 open(sys.argv[2], "w").write(json.dumps(rec) + "\n")

@@ -5,25 +5,10 @@
 # A run that fails or times out ends the script with its log tail and a non-zero exit: no further GPU step after it.
 #   usage: [OUT_DIR=dir] bash tools/profile_vert_adv.sh <tag> [vert_adv_diag.py args]   -> $OUT_DIR/<tag>_*
 #   (OUT_DIR defaults to build/profile_out, which git ignores)
-set -o pipefail
-TAG=${1:?tag}; shift
-cd "$(dirname "$0")/.."
-export TMPDIR=/tmp
-OUT=${OUT_DIR:-build/profile_out}
-mkdir -p $OUT
+NAME=vertadv
+. "$(dirname "$0")/profile_lib.sh"
 PROBE="python3 tools/probes/vert_adv_diag.py $*"
-step() { # name seconds command...
-   n=$1; t=$2; shift 2
-   timeout -k 10 $t "$@" > $OUT/${TAG}_$n.log 2>&1
-   rc=$?
-   echo "[vertadv] $n rc=$rc"
-   if [ $rc -ne 0 ]; then
-      echo "[vertadv] $n FAILED (rc $rc; 124 = timeout): last lines of its log" >&2
-      tail -20 $OUT/${TAG}_$n.log >&2
-      exit $rc
-   fi
-}
 step diag 500 $PROBE --out $OUT/${TAG}_diag_qu30.json
-step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -o t -- $PROBE --only-kernels --iters 20
-find $OUT/${TAG}_trace -name '*kernel_stats.csv' -exec grep -h -E '^"?Name|vertAdv' {} \; > $OUT/${TAG}_kernel_stats_qu30.csv
+trace $PROBE --only-kernels --iters 20
+kernel_stats vertAdv
 cat $OUT/${TAG}_diag_qu30.json
