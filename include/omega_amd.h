@@ -944,6 +944,57 @@ int omg_vremap_copy_to_host(const omg_vremap *r, const char *name, double *host,
  * a pointer to r: detach before destroying it. */
 int omg_stepper_attach_vert_remap(omg_stepper *st, omg_vremap *r);
 
+/* ---- Kpp (omega_amd/csrc/Kpp.h; O/doc/design/OmegaV1GoverningEqns.md section 1 and VerticalMixingCoeff.md, design
+ * only): K-profile boundary-layer mixing on top of a VertMix -- the boundary-layer depth from a bulk Richardson number,
+ * the K-profile viscosity and diffusivity inside the layer over what omg_vertmix_compute wrote, and the non-local
+ * redistribution of the surface tracer flux.  Level-indexed device arrays are [rows][pitch] with pitch =
+ * omg_level_pitch(NVertLayers); z_interface_dev is [NCellsSize][omg_level_pitch(NVertLayers + 1)].  Every call is
+ * asynchronous on stream and allocates nothing.  The object keeps pointers to v and x: destroy it before them. ---- */
+typedef struct omg_kpp omg_kpp;
+typedef struct omg_kpp_config {
+   double VonKarman;            /* 0.4 */
+   double CritBulkRichardson;   /* 0.3 */
+   double SurfaceLayerFraction; /* 0.1 */
+   double Cv;                   /* 1.7 */
+   double EntrainmentRatio;     /* 0.2 */
+   double CStar;                /* 10 */
+} omg_kpp_config;
+int omg_kpp_config_default(omg_kpp_config *c);
+/* c NULL: the defaults.  Fails for a VonKarman or CritBulkRichardson that is not positive, a SurfaceLayerFraction
+ * outside (0, 1), a negative Cv, EntrainmentRatio or CStar, a host-only mesh, a VertCoord or VertMix that is NULL or of
+ * another mesh or layer count, and NVertLayers outside 1 .. 1024 */
+int omg_kpp_create(const omg_mesh *m, const omg_vcoord *v, omg_vertmix *x, const omg_kpp_config *c, omg_kpp **out);
+int omg_kpp_destroy(omg_kpp *k);
+/* "BoundaryLayerDepth", "BoundaryLayerIndex", "BulkRichardson", "NonLocalShape" and, inside the boundary layer, the
+ * VertMix's "VertDiff" / "VertVisc", from the edge velocities [NEdgesSize][pitch], the VertMix's "BruntVaisalaFreqSq",
+ * the VertCoord's "ZMid" / "ZInterface" and this object's "FrictionVelocity" / "SurfaceBuoyancyFlux".  One launch */
+int omg_kpp_compute(omg_kpp *k, const double *normal_velocity_dev, const double *tangential_velocity_dev, void *stream);
+/* the same on the caller's cell arrays; vert_diff_dev and vert_visc_dev are rewritten inside the boundary layer only */
+int omg_kpp_compute_arrays(omg_kpp *k, const double *normal_velocity_dev, const double *tangential_velocity_dev,
+                           const double *bvf_dev, const double *z_mid_dev, const double *z_interface_dev,
+                           double *vert_diff_dev, double *vert_visc_dev, void *stream);
+/* tracers_dev [ntracers][NCellsSize][pitch] in place on owned cells: the counter-gradient part of surface_flux_dev
+ * [ntracers][NCellsSize] (positive into the ocean; NULL: nothing is done) on "NonLocalShape" as it stands.  One launch */
+int omg_kpp_apply_non_local(omg_kpp *k, const double *layer_thickness_dev, double *tracers_dev, int ntracers, double dt,
+                            const double *surface_flux_dev, void *stream);
+/* the two constants formed at creation (Kpp.h): VtCoef and NonLocalCoeff */
+int omg_kpp_constants(const omg_kpp *k, double *vt_coef, double *non_local_coeff);
+/* kernel launches the three calls have issued on this object so far */
+int omg_kpp_launch_count(const omg_kpp *k, int64_t *n);
+/* "FrictionVelocity", "SurfaceBuoyancyFlux", "BoundaryLayerDepth" ([NCellsSize]), "BulkRichardson", "NonLocalShape"
+ * ([NCellsSize][NVertLayers]); all zero at creation */
+int omg_kpp_device_ptr(const omg_kpp *k, const char *name, double **dev, size_t *n);
+int omg_kpp_copy_to_device(omg_kpp *k, const char *name, const double *host, size_t n);
+int omg_kpp_copy_to_host(const omg_kpp *k, const char *name, double *host, size_t n);
+/* "BoundaryLayerIndex" ([NCellsSize] int32, zero at creation; -1 on land after a compute) */
+int omg_kpp_copy_to_host_i4(const omg_kpp *k, const char *name, int32_t *host, size_t n);
+int omg_kpp_copy_to_device_i4(omg_kpp *k, const char *name, const int32_t *host, size_t n);
+/* VertMixStep::attachKpp (omega_amd/csrc/VertMixStep.h): omg_vertmix_step_apply runs omg_kpp_compute_arrays after the
+ * coefficients and omg_kpp_apply_non_local with the step's "SurfaceTracerFlux" before the tracer solve (k NULL:
+ * detach).  Fails for a k of another mesh or layer count or on another VertCoord or VertMix.  The VertMixStep keeps a
+ * pointer to k: detach before destroying it. */
+int omg_vmix_step_attach_kpp(omg_vertmix_step *ms, omg_kpp *k);
+
 /* ---- Batched tridiagonal solvers (O/src/base/TriDiagSolvers.h).  Numerical contract: omega_amd/csrc/TriDiagSolvers.h.
  * nbatch systems of nrow rows (1 <= nrow <= 1024; anything else fails naming the limit), row i of every array at
  * dev + i * row_pitch (row_pitch 0: nrow).  x holds the right-hand side on entry and the solution on return; only

@@ -1192,6 +1192,12 @@ class VertMixStep(_Handle, _NamedArrays):
         _chk(lib().omg_vertmixstep_attach_redi(self.h, redi.h if redi is not None else None))
         self._redi = redi  # the library keeps a pointer to it
 
+    def attach_kpp(self, kpp: "Kpp | None"):
+        """VertMixStep::attachKpp: apply runs `kpp`'s compute after the coefficients and its non-local redistribution
+        of SurfaceTracerFlux before the tracer solve; None detaches."""
+        _chk(lib().omg_vmix_step_attach_kpp(self.h, kpp.h if kpp is not None else None))
+        self._kpp = kpp  # the library keeps a pointer to it
+
     def apply(self, layer_thickness: int, normal_velocity: int, tracers: int, dt: float, stream=None):
         """On device addresses: thickness [NCellsSize][pitch]; velocity [NEdgesSize][pitch] and tracers
         [NT][NCellsSize][pitch] are mixed in place, asynchronously on `stream`."""
@@ -1207,6 +1213,99 @@ class VertMixStep(_Handle, _NamedArrays):
         m = self.mesh
         return {"TangentialVelocity": (m.NEdgesSize, self.K), "NormalStressEdge": (m.NEdgesSize,),
                 "SurfaceTracerFlux": (self.NT, m.NCellsSize)}.get(name, (m.NCellsSize,))
+
+
+class KppConfig(C.Structure):
+    """omg_kpp_config (omega_amd/csrc/Kpp.h)"""
+    _fields_ = [("VonKarman", C.c_double), ("CritBulkRichardson", C.c_double), ("SurfaceLayerFraction", C.c_double),
+                ("Cv", C.c_double), ("EntrainmentRatio", C.c_double), ("CStar", C.c_double)]
+
+
+def kpp_config(**over) -> KppConfig:
+    """The defaults (omg_kpp_config_default) with the given fields replaced; an unknown field raises KeyError."""
+    c = KppConfig()
+    _chk(lib().omg_kpp_config_default(C.byref(c)))
+    names = {f[0] for f in KppConfig._fields_}
+    for k, v in over.items():
+        if k not in names:
+            raise KeyError(k)
+        setattr(c, k, v)
+    return c
+
+
+class Kpp(_Handle, _NamedArrays):
+    """Kpp (omega_amd/csrc/Kpp.h): K-profile boundary-layer mixing on top of `vert_mix` -- the boundary-layer depth from
+    a bulk Richardson number, the K-profile viscosity and diffusivity inside the layer (compute) and the non-local
+    redistribution of a surface tracer flux (apply_non_local).  `config` fields as in KppConfig (e.g. Cv=1.5).  The
+    caller sets "FrictionVelocity" and "SurfaceBuoyancyFlux" ([NCellsSize]) with `set`; the results are
+    "BoundaryLayerDepth", "BoundaryLayerIndex" (int32), "BulkRichardson" and "NonLocalShape" (`get`).  Level-indexed
+    inputs are numpy arrays [rows][K] or device addresses of [rows][level_pitch(K)] doubles."""
+    _destroy, _arrays, _i4 = "omg_kpp_destroy", "omg_kpp", ("BoundaryLayerIndex",)
+
+    def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", vert_mix: "VertMix | None", **config):
+        self.mesh, self.vcoord, self.vert_mix = mesh, vcoord, vert_mix
+        self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
+        self.config = kpp_config(**config)
+        self._create("omg_kpp_create", mesh.h, vcoord.h if vcoord is not None else None,
+                     vert_mix.h if vert_mix is not None else None, C.byref(self.config))
+
+    def constants(self) -> tuple:
+        """(VtCoef, NonLocalCoeff) as formed at creation"""
+        a, b = C.c_double(), C.c_double()
+        _chk(lib().omg_kpp_constants(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def compute(self, normal_velocity, tangential_velocity, bvf=None, z_mid=None, z_interface=None, vert_diff=None,
+                vert_visc=None, stream=None):
+        """The boundary layer from the edge velocities: on the five given cell arrays (the array form; all five or
+        none; z_interface is [NCellsSize][K + 1]), or on the VertMix's and the VertCoord's arrays as they stand.
+        vert_diff and vert_visc are rewritten inside the layer: device addresses, or numpy arrays (staged, computed and
+        returned as a pair)."""
+        keep, ne, nc = [], self.mesh.NEdgesSize, self.mesh.NCellsSize
+        un = _level_dev(normal_velocity, ne, self.K, keep)
+        ut = _level_dev(tangential_velocity, ne, self.K, keep)
+        given = [a is not None for a in (bvf, z_mid, z_interface, vert_diff, vert_visc)]
+        if not any(given):
+            _chk(lib().omg_kpp_compute(self.h, un, ut, _sh(stream)))
+            if keep:
+                device_synchronize()
+            return None
+        if not all(given):
+            raise OmegaAmdError("Kpp.compute: the array form takes bvf, z_mid, z_interface, vert_diff and vert_visc together")
+        n2 = _level_dev(bvf, nc, self.K, keep)
+        zm = _level_dev(z_mid, nc, self.K, keep)
+        zi = _level_dev(z_interface, nc, self.K + 1, keep)
+        pd, bd = _stage_levels(vert_diff, (nc,), self.K)
+        pv, bv = _stage_levels(vert_visc, (nc,), self.K)
+        _chk(lib().omg_kpp_compute_arrays(self.h, un, ut, n2, zm, zi, pd, pv, _sh(stream)))
+        if keep or bd is not None or bv is not None:
+            if stream is not None:
+                stream.synchronize()
+            device_synchronize()
+        return _read_back(bd, self.K, stream), _read_back(bv, self.K, stream)
+
+    def apply_non_local(self, layer_thickness, tracers, ntracers: int, dt: float, surface_flux=None, stream=None):
+        """tracers [ntracers][NCellsSize][K] take the counter-gradient part of surface_flux ([ntracers][NCellsSize], a
+        numpy array or a device address; None: nothing is done) on NonLocalShape as it stands; in place on a device
+        address, or a numpy array (staged, computed, returned)."""
+        keep, n = [], self.mesh.NCellsSize
+        h = _level_dev(layer_thickness, n, self.K, keep)
+        p, buf = _stage_levels(tracers, (int(ntracers), n), self.K)
+        f = None if surface_flux is None else _flat_dev(surface_flux, (int(ntracers), n), keep)
+        _chk(lib().omg_kpp_apply_non_local(self.h, h, p, int(ntracers), C.c_double(dt), f, _sh(stream)))
+        if keep:
+            device_synchronize()
+        return _read_back(buf, self.K, stream)
+
+    def launch_count(self) -> int:
+        """kernel launches compute and apply_non_local have issued on this object so far"""
+        n = C.c_int64(0)
+        _chk(lib().omg_kpp_launch_count(self.h, C.byref(n)))
+        return n.value
+
+    def _shape(self, name):
+        m = self.mesh
+        return (m.NCellsSize, self.K) if name in ("BulkRichardson", "NonLocalShape") else (m.NCellsSize,)
 
 
 PGRAD_ARRAYS = ("SurfacePressure", "TidalPotential", "SelfAttractionLoading")

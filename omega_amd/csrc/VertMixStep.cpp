@@ -40,6 +40,16 @@ void VertMixStep::attachRedi(Redi *R) {
    RediTerm = R;
 }
 
+void VertMixStep::attachKpp(Kpp *P) {
+   if (P != nullptr) {
+      OMEGA_REQUIRE(P->Mesh == Mesh && P->NVertLayers == NVertLayers,
+                    "VertMixStep::attachKpp: the Kpp was built for another mesh or layer count");
+      OMEGA_REQUIRE(P->VCoord == VCoord && P->VMix == VMix,
+                    "VertMixStep::attachKpp: the Kpp is on a different VertCoord or VertMix than this VertMixStep");
+   }
+   KppTerm = P;
+}
+
 void VertMixStep::apply(const Array2DReal &H, const Array2DReal &U, const Array3DReal &Tr, Real Dt, hipStream_t S) {
    requireLevelArray("VertMixStep", H, Mesh->NCellsSize, NVertLayers, "LayerThickness");
    requireLevelArray("VertMixStep", U, Mesh->NEdgesSize, NVertLayers, "NormalVelocity");
@@ -51,8 +61,13 @@ void VertMixStep::apply(const Array2DReal &H, const Array2DReal &U, const Array3
    const TangentialReconOnEdge TangentialRecon(Mesh);
    TangentialRecon(TangentialVelocity, U, S);
    VMix->computeVertMix(U, TangentialVelocity, VMix->BruntVaisalaFreqSq, S);
+   if (KppTerm) // the boundary layer: its depth, and the K-profile coefficients inside it
+      KppTerm->compute(U, TangentialVelocity, VMix->BruntVaisalaFreqSq, VCoord->ZMid, VCoord->ZInterface, VMix->VertDiff,
+                       VMix->VertVisc, S);
    if (RediTerm) // the S.S part of the isoneutral tensor joins the implicit tracer solve
       RediTerm->computeVertDiffusivity(VMix->VertDiff, S);
+   if (KppTerm) // the counter-gradient part of the surface flux, before the solve applies the flux itself
+      KppTerm->applyNonLocalTracerFlux(H, Tr, NTracers, Dt, SurfaceTracerFlux, S);
    VMix->applyTracerVertMix(H, Tr, NTracers, Dt, SurfaceTracerFlux, S);
    VMix->applyVelocityVertMix(H, U, Dt, Boundary, UseWindStress ? NormalStressEdge : Array1DReal(), TangentialVelocity,
                               S);

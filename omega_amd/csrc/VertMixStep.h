@@ -9,12 +9,17 @@
 //   2. VMix->computeBruntVaisalaFreqSq(Eos, S)
 //   3. TangentialReconOnEdge: NormalVelocity -> TangentialVelocity (every edge < NEdgesAll)
 //   4. VMix->computeVertMix(NormalVelocity, TangentialVelocity, VMix->BruntVaisalaFreqSq, S)
+//  4a. with a Kpp attached (attachKpp; Kpp.h): P->compute(NormalVelocity, TangentialVelocity, VMix->BruntVaisalaFreqSq,
+//      VCoord->ZMid, VCoord->ZInterface, VMix->VertDiff, VMix->VertVisc, S) -- the boundary-layer depth, and the
+//      K-profile coefficients over what step 4 wrote inside it
 //  4b. with a Redi attached (attachRedi; Redi.h): R->computeVertDiffusivity(VMix->VertDiff, S) -- the S.S part of the
 //      isoneutral tensor, from the slopes the Redi last computed (inside a split-explicit step: those of level n, one set
-//      per step as MPAS-Ocean keeps them), added to the diffusivity step 4 has just written
+//      per step as MPAS-Ocean keeps them), added to the diffusivity steps 4 and 4a have just written
+//  4c. with a Kpp attached: P->applyNonLocalTracerFlux(h, Tracers, NTracers, Dt, SurfaceTracerFlux, S) -- the
+//      counter-gradient redistribution of the surface flux, before the solve that applies the flux itself
 //   5. VMix->applyTracerVertMix(h, Tracers, NTracers, Dt, SurfaceTracerFlux, S)
 //   6. VMix->applyVelocityVertMix(h, u, Dt, Boundary, NormalStressEdge if UseWindStress, TangentialVelocity, S)
-// The result equals these six (with a Redi: seven) public calls made by hand, bit for bit.  Step 6 takes the bottom speed from the velocity
+// The result equals these six (with a Redi: seven; with a Kpp: two more) public calls made by hand, bit for bit.  Step 6 takes the bottom speed from the velocity
 // before the solve and the tangential velocity of step 3.
 //
 // One rank only as a stepper hook: the shear of step 4 and the tangential velocity read halo edges, so mixing inside a
@@ -25,6 +30,7 @@
 #define OMEGA_AMD_VERTMIXSTEP_H
 
 #include "ColumnPass.h"
+#include "Kpp.h"
 #include "OceanState.h"
 #include "Redi.h"
 #include "VertMix.h"
@@ -60,6 +66,10 @@ class VertMixStep : public Registry<VertMixStep>, public ColumnPass {
    /// one on another VertCoord or Eos than this object's.  The object keeps the pointer.
    void attachRedi(Redi *R);
    Redi *redi() const { return RediTerm; }
+   /// Opt-in: steps 4a and 4c above through P; nullptr detaches.  Refuses (OmegaError) a Kpp of another mesh or layer
+   /// count and one on another VertCoord or VertMix than this object's.  The object keeps the pointer.
+   void attachKpp(Kpp *P);
+   Kpp *kpp() const { return KppTerm; }
 
    // ---- the reference's style of signature: on this object's `Stream` (default: the null stream)
    hipStream_t Stream = nullptr;
@@ -72,6 +82,7 @@ class VertMixStep : public Registry<VertMixStep>, public ColumnPass {
 
  protected:
    Redi *RediTerm = nullptr;
+   Kpp *KppTerm   = nullptr;
 };
 
 } // namespace OMEGA

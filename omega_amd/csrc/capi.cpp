@@ -27,6 +27,7 @@
 #include "MonotoneAdv.h"
 #include "VertAdv.h"
 #include "VertRemap.h"
+#include "Kpp.h"
 #include "VertMixStep.h"
 #include "BarotropicMode.h"
 #include "SplitExplicitStepper.h"
@@ -105,6 +106,9 @@ struct omg_redi {
 };
 struct omg_vremap {
    std::unique_ptr<VertRemap> R;
+};
+struct omg_kpp {
+   std::unique_ptr<Kpp> K;
 };
 
 static thread_local std::string LastError;
@@ -2341,6 +2345,117 @@ int omg_stepper_attach_vert_remap(omg_stepper *st, omg_vremap *r) {
    OMG_TRY
    OMG_ARG(st);
    splitExplicit(st, "attachVertRemap")->attachVertRemap(r ? r->R.get() : nullptr);
+   OMG_CATCH
+}
+
+// ---- Kpp (Kpp.h)
+int omg_kpp_config_default(omg_kpp_config *c) {
+   OMG_TRY
+   OMG_ARG(c);
+   const KppConfig V;
+   c->VonKarman            = V.VonKarman;
+   c->CritBulkRichardson   = V.CritBulkRichardson;
+   c->SurfaceLayerFraction = V.SurfaceLayerFraction;
+   c->Cv                   = V.Cv;
+   c->EntrainmentRatio     = V.EntrainmentRatio;
+   c->CStar                = V.CStar;
+   OMG_CATCH
+}
+int omg_kpp_create(const omg_mesh *m, const omg_vcoord *v, omg_vertmix *x, const omg_kpp_config *c, omg_kpp **out) {
+   OMG_TRY
+   OMG_ARG(m && out);
+   KppConfig Cfg;
+   if (c) {
+      Cfg.VonKarman = c->VonKarman, Cfg.CritBulkRichardson = c->CritBulkRichardson;
+      Cfg.SurfaceLayerFraction = c->SurfaceLayerFraction, Cfg.Cv = c->Cv;
+      Cfg.EntrainmentRatio = c->EntrainmentRatio, Cfg.CStar = c->CStar;
+   }
+   newHandle(out, [&](omg_kpp &H) {
+      H.K.reset(new Kpp("Default", m->M.get(), v ? v->V.get() : nullptr, x ? x->X.get() : nullptr, Cfg));
+   });
+   OMG_CATCH
+}
+int omg_kpp_destroy(omg_kpp *k) {
+   delete k;
+   return 0;
+}
+int omg_kpp_compute(omg_kpp *k, const double *normal_velocity, const double *tangential_velocity, void *stream) {
+   OMG_TRY
+   OMG_ARG(k && normal_velocity && tangential_velocity);
+   const int NE = k->K->Mesh->NEdgesSize, K = k->K->NVertLayers;
+   k->K->compute(levelView(normal_velocity, NE, K), levelView(tangential_velocity, NE, K), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_kpp_compute_arrays(omg_kpp *k, const double *normal_velocity, const double *tangential_velocity, const double *bvf,
+                           const double *z_mid, const double *z_interface, double *vert_diff, double *vert_visc,
+                           void *stream) {
+   OMG_TRY
+   OMG_ARG(k && normal_velocity && tangential_velocity && bvf && z_mid && z_interface && vert_diff && vert_visc);
+   const int NE = k->K->Mesh->NEdgesSize, NC = k->K->Mesh->NCellsSize, K = k->K->NVertLayers;
+   k->K->compute(levelView(normal_velocity, NE, K), levelView(tangential_velocity, NE, K), levelView(bvf, NC, K),
+                 levelView(z_mid, NC, K), levelView(z_interface, NC, K + 1), levelView(vert_diff, NC, K),
+                 levelView(vert_visc, NC, K), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_kpp_apply_non_local(omg_kpp *k, const double *layer_thickness, double *tracers, int ntracers, double dt,
+                            const double *surface_flux, void *stream) {
+   OMG_TRY
+   OMG_ARG(k && layer_thickness && ntracers >= 0 && (tracers || ntracers == 0));
+   const int NC = k->K->Mesh->NCellsSize, K = k->K->NVertLayers;
+   k->K->applyNonLocalTracerFlux(levelView(layer_thickness, NC, K), tracerView(tracers, ntracers, NC, K), ntracers, dt,
+                                 fluxView(surface_flux, ntracers, NC), (hipStream_t)stream);
+   OMG_CATCH
+}
+int omg_kpp_constants(const omg_kpp *k, double *vt_coef, double *non_local_coeff) {
+   OMG_TRY
+   OMG_ARG(k && vt_coef && non_local_coeff);
+   k->K->constants(*vt_coef, *non_local_coeff);
+   OMG_CATCH
+}
+int omg_kpp_launch_count(const omg_kpp *k, int64_t *n) {
+   OMG_TRY
+   OMG_ARG(k && n);
+   *n = k->K->LaunchCount;
+   OMG_CATCH
+}
+static ArrRef kppLookup(const Kpp &P, const char *Name) {
+   return findNamed<ArrRef>({{"FrictionVelocity", arrRef(P.FrictionVelocity)},
+                             {"SurfaceBuoyancyFlux", arrRef(P.SurfaceBuoyancyFlux)},
+                             {"BoundaryLayerDepth", arrRef(P.BoundaryLayerDepth)},
+                             {"BulkRichardson", arrRef(P.BulkRichardson)},
+                             {"NonLocalShape", arrRef(P.NonLocalShape)}},
+                            Name, "Kpp: no array named ");
+}
+OMG_NAMED_ARRAYS(omg_kpp_copy_to_host, omg_kpp_copy_to_device, omg_kpp_device_ptr, omg_kpp, k, kppLookup(*k->K, name))
+static const Array1DI4 &kppLookupI4(const Kpp &P, const char *Name) {
+   return *findNamed<const Array1DI4 *>({{"BoundaryLayerIndex", &P.BoundaryLayerIndex}}, Name,
+                                        "Kpp: no int array named ");
+}
+int omg_kpp_copy_to_host_i4(const omg_kpp *k, const char *name, int32_t *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(k && name && host);
+   const Array1DI4 &A = kppLookupI4(*k->K, name);
+   if (n < A.size())
+      OMEGA_ABORT(std::string("output buffer too small for ") + name);
+   HIP_CHECK(hipDeviceSynchronize());
+   copyToHost(host, A.Ptr, A.bytes());
+   OMG_CATCH
+}
+int omg_kpp_copy_to_device_i4(omg_kpp *k, const char *name, const int32_t *host, size_t n) {
+   OMG_TRY
+   OMG_ARG(k && name && host);
+   const Array1DI4 &A = kppLookupI4(*k->K, name);
+   if (n != A.size())
+      OMEGA_ABORT(std::string("size mismatch for ") + name);
+   HIP_CHECK(hipDeviceSynchronize());
+   copyToDevice(A.Ptr, host, A.bytes());
+   HIP_CHECK(hipDeviceSynchronize());
+   OMG_CATCH
+}
+int omg_vmix_step_attach_kpp(omg_vertmix_step *ms, omg_kpp *k) {
+   OMG_TRY
+   OMG_ARG(ms);
+   ms->M->attachKpp(k ? k->K.get() : nullptr);
    OMG_CATCH
 }
 
