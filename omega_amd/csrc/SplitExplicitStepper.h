@@ -85,7 +85,9 @@
 // the stepper must have a VertMixStep attached (attachVertMix) and that VertMixStep this same Redi (VertMixStep::
 // attachRedi): it then adds VertDiffusivity, from the slopes of step 5c, to VertMix's VertDiff before the tracer solve
 // of the new level.  Redi moves tracers only: the velocity and the thickness of the step are those of the unattached
-// step bit for bit.  With nothing attached the step, its launch count and its bits are what they were.
+// step bit for bit.  With nothing attached the step, its launch count and its bits are what they were.  The attached
+// step -- alone, with the GentMcWilliams, the MonotoneAdv and a Kpp, on ragged ranges -- equals the host composition of
+// tests/model_step_reference.py bit for bit.
 //
 // With a VertRemap attached (attachVertRemap; VertRemap.h) the step is a vertical Lagrangian one followed by a remap:
 // without a VertAdv the thickness of steps 6-7 moves with the horizontal divergence alone, and between steps 8 and 9 the
@@ -97,7 +99,9 @@
 // Tendencies is the other way of holding the layers to the coordinate: the two together are refused, at the attachment
 // and again in every step, and with them a MonotoneAdv that owns that VertAdv (its 3-D form needs it on the Tendencies).
 // The remap comes after everything else of the step that moves the state explicitly, so steps 1-8 are those of the
-// unattached step bit for bit.  With nothing attached the step, its launch count and its bits are what they were.
+// unattached step bit for bit.  With nothing attached the step, its launch count and its bits are what they were.  The
+// attached step -- at the three orders, and together with the GentMcWilliams, the MonotoneAdv, the Redi and a Kpp, on
+// ragged ranges -- equals the host composition of tests/model_step_reference.py bit for bit.
 //
 // What a step carries to the next one besides the state: nothing of the BarotropicMode -- step 2 writes BtrThickEdge and
 // BtrVelocity on every edge and SSH on every column with layers, and steps 3-4 the rest, before anything reads them --

@@ -19,8 +19,10 @@
 //      counter-gradient redistribution of the surface flux, before the solve that applies the flux itself
 //   5. VMix->applyTracerVertMix(h, Tracers, NTracers, Dt, SurfaceTracerFlux, S)
 //   6. VMix->applyVelocityVertMix(h, u, Dt, Boundary, NormalStressEdge if UseWindStress, TangentialVelocity, S)
-// The result equals these six (with a Redi: seven; with a Kpp: two more) public calls made by hand, bit for bit.  Step 6 takes the bottom speed from the velocity
-// before the solve and the tangential velocity of step 3.
+// The result equals these six (with a Redi: seven; with a Kpp: two more) public calls made by hand, bit for bit.  Step 6
+// takes the bottom speed from the velocity before the solve and the tangential velocity of step 3.  As the hook of a
+// split-explicit step the sequence -- with a Kpp, with a Redi and with both, in the order 4, 4a, 4b, 4c, 5 -- equals the
+// host composition of tests/model_step_reference.py bit for bit, wherever the Kpp evaluates no cbrt (Kpp.h).
 //
 // One rank only as a stepper hook: the shear of step 4 and the tangential velocity read halo edges, so mixing inside a
 // multi-rank step needs the halo of the new level before the sequence and again after the solves; that path is not

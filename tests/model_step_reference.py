@@ -1,7 +1,8 @@
 """One Split-Explicit step on the host: the sequence of omega_amd/csrc/SplitExplicitStepper.h and VertMixStep.h composed
 from the restatements the pieces are already pinned against -- the C oracle for the three tendencies and the tangential
 reconstruction, tests/column_reference.py for the column pass, and the NumPy restatements of PressureGrad, VertAdv,
-BarotropicMode and the stepper's glue, MonotoneAdv (2-D, 3-D, high order), GentMcWilliams and the forced VertMix solves.
+BarotropicMode and the stepper's glue, MonotoneAdv (2-D, 3-D, high order), GentMcWilliams, Redi, VertRemap, Kpp and the
+forced VertMix solves.
 Nothing here calls a device: the mesh tables come from an oa.HorzMesh (host-only will do) and, for the high-order
 flux, from omg_monoadv_high_order_tables, as the CPU tests of the pieces take them.
 
@@ -19,12 +20,15 @@ import numpy as np
 from oracle import oracle as O
 from tests import column_reference as CR
 from tests import gent_mcwilliams_reference as GR
+from tests import kpp_reference as KR
 from tests import monotone_adv_reference as MR
 from tests import pressure_grad_reference as PR
+from tests import redi_reference as RR
 from tests import split_explicit_reference as SR
 from tests import vert_adv_reference as VR
 from tests import vert_mix_forcing_reference as FR
 from tests import vert_mix_reference as XR
+from tests import vert_remap_reference as WR
 from tests.barotropic_fixtures import GRAVITY, btr_mesh
 from tests.column_reference import RHO0
 
@@ -42,6 +46,16 @@ DEVIATIONS = (
     "btr_velocity_reset",         # BtrVelocity reset between steps: before step 1 of every time step, where it is dead
                                   # (step 2 rewrites it on every edge), and between steps 5 and 8 of the sequence,
                                   # where it is live (step 8 adds the velocity the sub-cycle ended with)
+    "redi_slopes_of_the_new_level",       # step 5c fed h[Next] / NextTracers as they stand
+    "redi_before_mono",                   # the two addTracerTend calls of steps 6-7 swapped (another rounding)
+    "redi_diffusivity_from_new_slopes",   # step 4b on slopes recomputed from step 9's pass
+    "redi_diffusivity_before_kpp",        # step 4b before 4a: Redi's part is lost inside the boundary layer
+    "non_local_after_the_solve",          # step 4c after the tracer solve
+    "kpp_on_the_old_level",               # step 4a fed the velocity of level n
+    "remap_after_mix",                    # step 8b after step 9
+    "remap_target_from_h_cur",            # the target from the column totals of h[Cur]
+    "remap_leaves_h",                     # h[Next] not set to the target
+    "remap_skips_velocity",               # the velocity not remapped
 )
 
 
@@ -49,13 +63,24 @@ def options(**over):
     """What is attached, and how.  pgrad / gm / mix: bool; vert_adv: None or VertAdv's TracerFluxOrder; tracer_term:
     VertAdv::TracerTermEnable; mono: None or (order, Coef3rdOrder); mono_3d: the MonotoneAdv has the VertAdv attached;
     eos: "teos10" or "linear" with `linear` = (DRhoDT, DRhoDS, RhoT0S0); upwind: FluxThicknessUpwind (the MonotoneAdv's
-    too); mix_config: VertMix's; cd, ra, wind: VertMixStep's boundary."""
+    too); mix_config: VertMix's; cd, ra, wind: VertMixStep's boundary; redi / kpp: bool, each needs mix (the Redi at the
+    class's SlopeMax and N2Floor, the Kpp at its default configuration); remap: None or VertRemap's order 1, 2 or 3,
+    refused with a VertAdv (and so with the 3-D MonotoneAdv) as SplitExplicitStepper::attachVertRemap refuses it."""
     o = dict(pgrad=False, vert_adv=None, tracer_term=True, mono=None, mono_3d=False, gm=False, mix=False, eos="teos10",
-             linear=(-0.2, 0.8, 1000.0), upwind=False, gm_speed=0.3, mix_config=None, cd=0.0, ra=0.0, wind=False)
+             linear=(-0.2, 0.8, 1000.0), upwind=False, gm_speed=0.3, mix_config=None, cd=0.0, ra=0.0, wind=False,
+             redi=False, kpp=False, remap=None)
     for k, v in over.items():
         if k not in o:
             raise KeyError(k)
         o[k] = v
+    for k in ("redi", "kpp"):
+        if o[k] and not o["mix"]:
+            raise ValueError(f"{k} needs mix")
+    if o["remap"] is not None:
+        if o["remap"] not in (1, 2, 3):
+            raise ValueError("remap: the order is 1, 2 or 3")
+        if o["vert_adv"] is not None or o["mono_3d"]:
+            raise ValueError("remap with a VertAdv is refused")
     return o
 
 
@@ -65,11 +90,19 @@ class HostModel:
     second holds the rig's seed); lo, hi: MinLayerCell / MaxLayerCell [NCellsSize]; bottom, ref: BottomDepth
     [NCellsSize], RefLayerThickness [NCellsSize][K]; forcing: dict SurfacePressure, TidalPotential,
     SelfAttractionLoading [NCellsSize] (one set: the stepper requires the objects' sets to be equal), Kappa,
-    NormalStressEdge [NEdgesSize], SurfaceTracerFlux [NT][NCellsSize]; column: the column fields as they stand before
-    the first step (dict of COLUMN_FIELDS); opt: options()."""
+    NormalStressEdge [NEdgesSize], SurfaceTracerFlux [NT][NCellsSize], with a Redi RediKappa [NEdgesSize], with a Kpp
+    FrictionVelocity and SurfaceBuoyancyFlux [NCellsSize]; column: the column fields as they stand before the first
+    step (dict of COLUMN_FIELDS); opt: options(); seeds: what SlopeInterface, VertDiffusivity and the VertRemap's
+    LayerThicknessTarget (kept here as RemapTarget: the VertCoord has an array of that name too) hold where no call
+    writes them (default: zero, as the constructors leave them).  kpp_constants: (VtCoef, NonLocalCoeff), the
+    restatement's own unless a rig replaces them by the library's (tests/kpp_fixtures.py).
+
+    Of each step's Kpp call the per-column flags are kept too (kpp_flags: a list with one dict per step of `valid`,
+    `used_cbrt`, `marginal`, `inside` and `VertDiffBefore` / `VertDiffAfter`, the VertDiff of step 4 and of step 4a), and
+    of each step's remap the thickness it came from (lagrangian_h)."""
 
     def __init__(self, mesh, g, oracle, K, nt, h, u, tr, lo, hi, bottom, ref, forcing, column, opt, dt, nsub,
-                 deviations=()):
+                 deviations=(), seeds=None):
         for d in deviations:
             if d not in DEVIATIONS:
                 raise KeyError(d)
@@ -112,6 +145,17 @@ class HostModel:
             if order != 2:
                 self.tables = MR.HoTables.of(self.mono_mesh, mesh, g, order, coef)
         self.mix_config = XR.config(**(opt["mix_config"] or {}))
+        seeds = seeds or {}
+        seed = lambda name, shape: np.array(seeds[name], dtype=np.float64) if name in seeds else np.zeros(shape)  # noqa: E731
+        self.SlopeInterface = seed("SlopeInterface", (self.ne_size, K))
+        self.VertDiffusivity = seed("VertDiffusivity", (self.nc_size, K))
+        self.RemapTarget = seed("RemapTarget", (self.nc_size, K))
+        self.redi_tables = RR.tables(mesh) if opt["redi"] else None
+        self.BoundaryLayerDepth, self.BoundaryLayerIndex = np.zeros(self.nc_size), np.full(self.nc_size, -1, np.int32)
+        self.BulkRichardson, self.NonLocalShape = np.zeros((self.nc_size, K)), np.zeros((self.nc_size, K))
+        self.kpp_config = KR.config()
+        self.kpp_constants = KR.constants(self.kpp_config)
+        self.kpp_flags, self.lagrangian_h = [], None
         self.steps_done = 0
 
     # ---- the named arrays of the BarotropicMode
@@ -160,6 +204,31 @@ class HostModel:
                           self.hi_e, self.ne, RHO0, self.opt["gm_speed"], self.BolusVelocity, self.StreamFunction,
                           u_transport)
 
+    def slopes(self, h, tr):
+        """step 5c: SlopeInterface of (h, tr): the column pass is step 5b's where a GentMcWilliams has just run it"""
+        if "redi_slopes_of_the_new_level" in self.dev:
+            h, tr = self.h[1], self.tr[1]
+            self.column_pass(h, tr, True)
+        elif not self.opt["gm"]:
+            self.column_pass(h, tr, True)
+        self.slope_of_the_column(h, self.SlopeInterface)
+
+    def slope_of_the_column(self, h, out):
+        c = self.column
+        RR.slope(h, c["SpecVol"], c["SpecVolDisplaced"], c["ZMid"], self.coe, self.dc, self.lo_e, self.hi_e, self.ne, RHO0, out)
+
+    def remap(self, h, u, tr):
+        """step 8b: VertRemap::remap's four calls, in place"""
+        o, dev = self.opt, self.dev
+        self.lagrangian_h = h.copy()
+        WR.compute_target(self.h[0] if "remap_target_from_h_cur" in dev else h, self.ref, self.weights, self.lo, self.hi,
+                          self.nc, self.RemapTarget)
+        WR.remap_tracers(h, self.RemapTarget, tr, self.nt, self.lo, self.hi, self.nc, o["remap"])
+        if "remap_skips_velocity" not in dev:
+            WR.remap_velocity(h, self.RemapTarget, u, self.coe, self.lo_e, self.hi_e, self.ne, self.nc_size, o["remap"])
+        if "remap_leaves_h" not in dev:
+            WR.adopt_target(h, self.RemapTarget, self.lo, self.hi, self.nc)
+
     def limited_advection(self, tend, h_old, h_new, u, tr):
         o = self.opt
         MR.add_tracer_tend(self.mono_mesh, tend, h_old, h_new, u, tr, self.nt, self.dt, o["upwind"], self.ScaleIn, self.ScaleOut,
@@ -175,6 +244,8 @@ class HostModel:
             self.split.vel[:] = 0.0
         if o["gm"]:
             self.bolus(h_next if "gm_reads_h_next" in dev else h, tr, u_transport)
+        if o["redi"]:
+            self.slopes(h, tr)
         self.transporting_velocity = u_transport.copy()
         # 6
         th = orc.compute_thickness_tendencies(h, u_transport)
@@ -187,16 +258,25 @@ class HostModel:
         tt = orc.compute_tracer_tendencies(h, u_transport, tr)
         if o["vert_adv"] is not None and o["tracer_term"]:
             VR.add_tracer_tend(tt[: self.nt], h, tr, self.VerticalTransport, self.lo, self.hi, n, o["vert_adv"])
-        if o["mono"] is not None:
-            self.limited_advection(tt, h, h if "mono_reads_h_cur_as_new" in dev else h_next,
-                                   self.u[0] if "mono_reads_u_cur" in dev else u_transport, tr)
+        def limited():
+            if o["mono"] is not None:
+                self.limited_advection(tt, h, h if "mono_reads_h_cur_as_new" in dev else h_next,
+                                       self.u[0] if "mono_reads_u_cur" in dev else u_transport, tr)
+
+        def isoneutral():
+            if o["redi"]:
+                RR.add_tracer_tend(tt[: self.nt], h, tr, self.nt, self.column["ZMid"], self.SlopeInterface, self.f["RediKappa"],
+                                   self.redi_tables, self.lo, self.hi, self.lo_e, self.hi_e)
+
+        for term in ((isoneutral, limited) if "redi_before_mono" in dev else (limited, isoneutral)):
+            term()
         with np.errstate(all="ignore"):
             den = h if "tracers_divided_by_h_cur" in dev else h_next
             tr_next[:, :n] = (tr[:, :n] * h[:n] + self.dt * tt[: self.nt, :n]) / den[:n]
 
     def mix(self, h, u, tr):
-        """step 9: the six calls of VertMixStep::apply, in place on u and tr"""
-        o, n = self.opt, self.nc
+        """step 9: the calls of VertMixStep::apply (six; 4b with a Redi, 4a and 4c with a Kpp), in place on u and tr"""
+        o, n, dev, f = self.opt, self.nc, self.dev, self.f
         self.column_pass(h, tr, True)
         c = self.column
         self.BruntVaisalaFreqSq = XR.bvf(c["SpecVol"], c["SpecVolDisplaced"], c["ZMid"], self.lo, self.hi, n, RHO0)
@@ -205,11 +285,47 @@ class HostModel:
         self.VertVisc, self.VertDiff = XR.coefficients(u, self.TangentialVelocity, self.BruntVaisalaFreqSq, c["ZMid"],
                                                        self.lo, self.hi, n, self.neoc, self.eoc, self.dc, self.dv, self.area,
                                                        self.mix_config)
+
+        def boundary_layer():                                                                       # 4a
+            if not o["kpp"]:
+                return
+            before = self.VertDiff.copy()
+            r = KR.compute(self.u[0] if "kpp_on_the_old_level" in dev else u, self.TangentialVelocity,
+                           self.BruntVaisalaFreqSq, c["ZMid"], c["ZInterface"], self.VertDiff, self.VertVisc,
+                           f["FrictionVelocity"], f["SurfaceBuoyancyFlux"], self.lo, self.hi, n, self.neoc, self.eoc, self.dc,
+                           self.dv, self.area, self.mix_config["BackgroundViscosity"], self.mix_config["BackgroundDiffusivity"],
+                           *self.kpp_constants, self.kpp_config)
+            for name in ("BoundaryLayerDepth", "BoundaryLayerIndex", "BulkRichardson", "NonLocalShape", "VertDiff", "VertVisc"):
+                setattr(self, name, r[name])
+            self.kpp_flags.append(dict(valid=r["valid"], used_cbrt=r["used_cbrt"], marginal=r["marginal"], inside=r["inside"],
+                                       VertDiffBefore=before, VertDiffAfter=r["VertDiff"].copy()))
+
+        def slope_squared():                                                                        # 4b
+            if not o["redi"]:
+                return
+            slopes = self.SlopeInterface
+            if "redi_diffusivity_from_new_slopes" in dev:
+                slopes = self.SlopeInterface.copy()
+                self.slope_of_the_column(h, slopes)
+            RR.vert_diffusivity(self.VertDiffusivity, self.VertDiff, slopes, f["RediKappa"], self.redi_tables, self.lo, self.hi,
+                                self.lo_e, self.hi_e)
+
+        def non_local():                                                                            # 4c
+            if o["kpp"]:
+                tr[:] = KR.apply_non_local(h, tr, self.nt, self.dt_seconds, f["SurfaceTracerFlux"], self.NonLocalShape, self.lo,
+                                           self.hi, self.nc_own)
+
+        for part in ((slope_squared, boundary_layer) if "redi_diffusivity_before_kpp" in dev else (boundary_layer, slope_squared)):
+            part()
         self.unmixed = (u.copy(), tr.copy())
+        if "non_local_after_the_solve" not in dev:
+            non_local()
         tr[:] = FR.tracer_mix_forced(h, self.VertDiff, tr, self.nt, self.dt_seconds, self.lo, self.hi, self.nc_own,
-                                     self.f["SurfaceTracerFlux"])
+                                     f["SurfaceTracerFlux"])
+        if "non_local_after_the_solve" in dev:
+            non_local()
         u[:] = FR.velocity_mix_forced(h, self.VertVisc, u, self.dt_seconds, self.coe, self.lo_e, self.hi_e, self.ne_own,
-                                      cd=o["cd"], ra=o["ra"], stress=self.f["NormalStressEdge"] if o["wind"] else None,
+                                      cd=o["cd"], ra=o["ra"], stress=f["NormalStressEdge"] if o["wind"] else None,
                                       ut=self.TangentialVelocity, edge_mask=self.mask, rho0=RHO0)
 
     # ---- the step
@@ -224,9 +340,14 @@ class HostModel:
         if "bolus_left_in_velocity" in self.dev:
             u_new[self.e_range] = u_new[self.e_range] + self.BolusVelocity[self.e_range]
         self.u[1][:] = u_new
+        remap = self.opt["remap"] is not None
+        if remap and "remap_after_mix" not in self.dev:                                             # 8b
+            self.remap(self.h[1], self.u[1], self.tr[1])
         if self.opt["mix"]:                                                                         # 9
             level = 0 if "mix_on_the_old_level" in self.dev else 1
             self.mix(self.h[level], self.u[level], self.tr[level])
+        if remap and "remap_after_mix" in self.dev:
+            self.remap(self.h[1], self.u[1], self.tr[1])
         for a in (self.h, self.u, self.tr):
             a.reverse()
         self.steps_done += 1

@@ -1,7 +1,10 @@
 """The all-host Split-Explicit step (tests/model_step_reference.py) by itself, and the rig's power to see mistakes: what
 two host steps on the periodic rig conserve and keep, every named deviation of the sequence changing the state on every
 rig the GPU comparison (tests/test_model_step_gpu.py) runs, and the empty rung equal to the oracle-fed
-split_explicit_reference.step written out on the spot.  No device."""
+split_explicit_reference.step written out on the spot.  For the rungs that attach the Redi, the Kpp and the VertRemap
+also: volume and tracer content conserved on every one of them, a constant tracer constant through Redi and remap, and
+the conditions on the inputs under which the Kpp rungs can be compared bit for bit (no cbrt evaluated, no marginal
+column, and a boundary layer that does something).  No device."""
 from fractions import Fraction
 
 import numpy as np
@@ -10,7 +13,7 @@ import pytest
 from oracle import oracle as O
 from tests import split_explicit_reference as SR
 from tests.barotropic_fixtures import GRAVITY, btr_mesh
-from tests.model_step_fixtures import DT, NSUB, RUNGS, ModelRig, deviations_of
+from tests.model_step_fixtures import DT, NEW_RUNGS, NSUB, RUNGS, ModelRig, deviations_of
 from tests.model_step_reference import DEVIATIONS
 
 EPS = np.finfo(np.float64).eps
@@ -176,6 +179,193 @@ def test_rest_with_flat_layers_stays_at_rest():
     assert not np.array_equal(tr[:, :n], x.start[2][:, :n])  # the surface fluxes and the mixing moved them
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the rungs with the Redi, the Kpp and the VertRemap
+# ---------------------------------------------------------------------------------------------------------------------
+KPP_RUNGS = [r for r in NEW_RUNGS if RUNGS[r]["opt"].get("kpp")]
+
+
+def _masked(x, field):
+    """the field on the rows < NCellsAll with 0.0 outside the layer ranges"""
+    return np.where(x.c_range[: x.nc], field[: x.nc], 0.0)
+
+
+def _closed_coast(g, G):
+    """No flow through the coast: the rigs draw a velocity on every edge, those with one cell included, and what
+    passes such an edge is a source of volume.  (Its velocity then stays 0.0: EdgeMask.)"""
+    G["un"][np.asarray(g["cellsOnEdge"]).min(axis=1) < 0] = 0.0
+
+
+def _closed(g, G):
+    _closed_coast(g, G)
+    _no_surface_flux(g, G)
+
+
+@pytest.mark.parametrize("rung", KPP_RUNGS)
+def test_the_kpp_rungs_evaluate_no_cbrt_and_have_a_boundary_layer_at_work(rung):
+    """What lets the GPU comparison ask for bits on a rung with a Kpp, shown on the host reference alone, in both steps.
+    The forcing: with sw <= eps under Bf < 0 every velocity scale is evaluated at z = kappa sig h Bf with sig <= eps and
+    h at most the column's depth d, and the cbrt branches are taken below ZetaM u3 = -0.2 us^3 (wM) and -us^3 (wS): none
+    is, where kappa eps d |Bf| <= 0.2 us^3.  The restatement's own flags say the same and that no comparison of the
+    contract is within rounding of flipping.  And the layer is not an empty one: the non-local shape is there under
+    Bf < 0, both signs of Bf occur, the layer ends inside at least a quarter of the columns of three or more layers and
+    reaches the bottom of others, and inside it VertDiff is no longer what step 4 wrote."""
+    x = ModelRig(rung, device=False).host
+    n, lo, hi = x.nc, x.lo[: x.nc].astype(np.int64), x.hi[: x.nc].astype(np.int64)
+    us, bf = x.f["FrictionVelocity"][:n], x.f["SurfaceBuoyancyFlux"][:n]
+    cfg = x.kpp_config
+    for step in range(STEPS):
+        h, _, _ = x.step()
+        flags = x.kpp_flags[step]
+        valid = flags["valid"][:n]
+        assert np.array_equal(valid, x.c_range[:n].any(axis=1)) and valid.any()
+        depth = _masked(x, h).sum(axis=1)
+        assert np.all((cfg["VonKarman"] * cfg["SurfaceLayerFraction"] * depth * np.abs(bf))[valid] <= (0.2 * us**3)[valid])
+        assert not flags["used_cbrt"][:n][valid].any() and not flags["marginal"][:n][valid].any()
+        shape = (x.NonLocalShape[:n] > 0.0).any(axis=1)
+        assert (valid & (bf < 0.0) & shape).any() and (valid & (bf >= 0.0)).any() and not (shape & (bf >= 0.0)).any()
+        kb = x.BoundaryLayerIndex[:n].astype(np.int64)
+        deep = valid & (hi - lo + 1 >= 3)
+        inside_column, to_the_bottom = deep & (lo < kb) & (kb <= hi), deep & (kb == hi + 1)
+        print(f"{rung}, step {step + 1}: of {deep.sum()} columns of >= 3 layers the layer ends inside {inside_column.sum()} and "
+              f"reaches the bottom of {to_the_bottom.sum()}; NonLocalShape > 0 in {(valid & shape).sum()} columns")
+        assert 4 * inside_column.sum() >= deep.sum() and to_the_bottom.any()
+        assert np.all(x.BoundaryLayerDepth[:n][valid] > 0.0)
+        inside = flags["inside"][:n]
+        assert inside.any() and np.all(flags["VertDiffAfter"][:n][inside] != flags["VertDiffBefore"][:n][inside])
+    assert len(x.kpp_flags) == STEPS
+
+
+def _remap_volume_roundings(x, h_new):
+    """What VertRemap's computeTarget and adoptTarget add to the change of sum A h, in units of eps/2, first order.
+    Exactly, sum_K Ref (1 + Coeff W / SumWh) = SumRef + Coeff = SumH.  In floating point, for a column of n layers with
+    H, HRef the totals of |h| and |Ref|: SumH and SumRef round n - 1 times each at no more than H and HRef, so does
+    Coeff = SumH - SumRef, once more at |Coeff|; SumWh takes n products and n - 1 additions, so the quotient
+    (Coeff W) / SumWh carries 2 n + 1 relative roundings of a term whose sum over the column is |Coeff|; 1.0 + q and the
+    product with Ref round once each at the target: (n - 1) (H + HRef) + (2 n + 2) |Coeff| + 2 HTarget."""
+    n = x.nc
+    count = x.c_range[:n].sum(axis=1)
+    H, href, target = (np.abs(_masked(x, a)).sum(axis=1) for a in (x.lagrangian_h, x.ref, h_new))
+    per_column = np.maximum(count - 1, 0) * (H + href) + (2 * count + 2) * np.abs(H - href) + 2.0 * target
+    return float((x.area[:n] * per_column).sum())
+
+
+@pytest.mark.parametrize("rung", NEW_RUNGS)
+def test_total_volume_is_conserved_on_the_new_rungs(rung):
+    """test_total_volume_is_conserved on every rung that attaches a Redi, a Kpp or a VertRemap: the same bound,
+    eps/2 sum A (|hNew| + 12 D) -- Redi and Kpp move no thickness -- and with a VertRemap, where hNew is the Lagrangian
+    thickness the remap starts from, the roundings of its target on top (_remap_volume_roundings).  The sum is over
+    every level of every cell: the Tendencies know no layer ranges, so on the ragged rigs a level outside a cell's range
+    trades volume with its neighbours like any other, and the sum over the ranges alone is not conserved.  The coast is
+    closed (_closed_coast)."""
+    x = ModelRig(rung, device=False, change=_closed_coast).host
+    n, area = x.nc, x.area
+    assert np.all(x.u[0][: x.ne][x.mask[: x.ne] == 0.0] == 0.0)
+    before = _exact(area[:n], x.h[0][:n])
+    for step in range(STEPS):
+        h, u, _ = x.step()
+        assert np.all(u[: x.ne][x.mask[: x.ne] == 0.0] == 0.0)
+        after = _exact(area[:n], h[:n])
+        moved = x.lagrangian_h if x.opt["remap"] is not None else h
+        units = float((area[:n, None] * (np.abs(moved[:n]) + 12.0 * _transport_scale(x))).sum())
+        if x.opt["remap"] is not None:
+            units += _remap_volume_roundings(x, h)
+        bound = EPS / 2 * units
+        err = abs(float(after - before))
+        print(f"{rung}, step {step + 1}: |change of sum A h| = {err:.3e} m^3 of {float(after):.3e}, bound {bound:.3e} "
+              f"({err / bound:.3f})")
+        assert err <= bound * (1.0 + 1.0e-6)
+        assert not np.array_equal(h[:n], x.h[1][:n])
+        before = after
+
+
+@pytest.mark.parametrize("rung", NEW_RUNGS)
+def test_total_tracer_content_is_conserved_on_the_new_rungs(rung):
+    """test_total_tracer_content_is_conserved_without_surface_fluxes on every rung that attaches a Redi, a Kpp or a
+    VertRemap, summed over every level of every cell with the coast closed (as the volume is, above), to the bound
+    derived there and no other.  The terms the new objects add fit
+    in it as they are: Redi's two explicit parts are flux-form (FluxE is formed alike by the two cells of an edge, WBot
+    of a layer is WTop of the one below: Redi.h), its S.S part rides in the implicit solve; the Kpp's non-local term
+    telescopes to NonLocalShape[KMin] = 0 and vanishes anyway with the surface flux; the remap integrates each source
+    cell's parabola exactly over the target layers."""
+    x = ModelRig(rung, device=False, change=_closed).host
+    n, area, K = x.nc, x.area, x.K
+    assert np.all(x.f["SurfaceTracerFlux"] == 0.0) and x.opt["mix"]
+    levels = int(np.ceil(np.log2(K)))
+    rng = x.c_range[:n]
+    before = [_exact(area[:n], x.h[0][:n], x.tr[0][t, :n]) for t in range(x.nt)]
+    for step in range(STEPS):
+        old_tr, old_h = x.tr[0].copy(), x.h[0].copy()
+        h, _, tr = x.step()
+        D = _transport_scale(x)
+        hs = [h[:n], old_h[:n]] + ([x.lagrangian_h[:n]] if x.opt["remap"] is not None else [])
+        h_max, h_min = max(a.max() for a in hs), min(a.min() for a in hs)
+        g_max = x.VertDiff[:n][rng].max() * x.dt_seconds / h_min
+        for t in range(x.nt):
+            p_max = max(np.abs(tr[t, :n]).max(), np.abs(old_tr[t, :n]).max())
+            spread = old_tr[t, :n].max() - old_tr[t, :n].min()
+            d_diff = x.dt * x.orc.c.EddyDiff2 * 6.0 * (x.dv[: x.ne] / x.dc[: x.ne]).max() * h_max * spread / area[:n].min()
+            per = 4.0 * h_max * p_max + 16.0 * (p_max * D + d_diff) + (8 * levels + 6) * (h_max * (1.0 + 4.0 * g_max) * p_max + h_max * p_max)
+            bound = EPS / 2 * float(area[:n].sum() * K * per)
+            after = _exact(area[:n], h[:n], tr[t, :n])
+            err = abs(float(after - before[t]))
+            print(f"{rung}, step {step + 1}, tracer {t}: |change of sum A h phi| = {err:.3e} of {float(after):.3e}, "
+                  f"bound {bound:.3e} ({err / bound:.3f})")
+            assert err <= bound
+            before[t] = after
+        assert not np.array_equal(tr[:, :n], old_tr[:, :n])
+
+
+def test_a_constant_tracer_stays_constant_through_redi_and_the_remap():
+    """Temperature = 10 everywhere, no surface flux of it, on planar_hex(8, 8) with K = 5: PressureGrad, the 2-D
+    MonotoneAdv at order 4, GentMcWilliams, Redi, the VertMixStep hook and the PPM VertRemap.  Two parts are exact.  Redi's
+    term is built from differences of phi alone (GradPhi, PhiZ, GInt): every one is 0.0 and the tendency keeps its bits.
+    The remap of a constant column has aL = aR = a and a6 = 0.0 in every cell, and whatever the quadrature rounds to, the
+    final clamp to the range of the source cells, [a, a], returns a.  Both are shown on the rig's own arrays after the
+    steps.  The rest is rounding: the advection as in
+    test_a_constant_tracer_stays_constant_under_the_3d_limiter_and_the_bolus_flow, eps/2 (4 + 32 C) per step, and the
+    implicit solve of step 9, M phi = h phi0 with a matrix that is diagonally dominant by rows with margin h (so
+    |M^-1| <= 1 / hMin) and, as the content test has it, a residual of at most (8 L + 6) roundings of
+    |A| |x| + |b| <= (h (1 + 4 G) + h) phi0: relative eps/2 (8 L + 6) (2 + 4 G) hMax / hMin per step."""
+    from tests import redi_reference as RR
+    from tests import vert_remap_reference as WR
+    from tests.model_step_fixtures import CD, RA
+    phi0 = 10.0
+
+    def constant(g, G):
+        G["tr"][0][:] = phi0
+        G["SurfaceTracerFlux"][0][:] = 0.0
+
+    spec = dict(mesh="planar8", K=5, opt=dict(pgrad=True, mono=(4, 0.25), gm=True, mix=True, cd=CD, ra=RA, wind=True, redi=True,
+                                              remap=3))
+    x = ModelRig(spec, device=False, change=constant).host
+    n, K = x.nc, x.K
+    levels = int(np.ceil(np.log2(K)))
+    bound = 0.0
+    for step in range(STEPS):
+        h_old = x.h[0].copy()
+        h, _, tr = x.step()
+        h_min = min(h[:n].min(), h_old[:n].min(), x.lagrangian_h[:n].min())
+        h_max = max(h[:n].max(), h_old[:n].max(), x.lagrangian_h[:n].max())
+        c = _transport_scale(x) / h_min
+        g_max = x.VertDiff[:n].max() * x.dt_seconds / h_min
+        bound += EPS / 2 * ((4.0 + 32.0 * c) + (8 * levels + 6) * (2.0 + 4.0 * g_max) * h_max / h_min)
+        dev = np.abs(tr[0, :n] / phi0 - 1.0).max()
+        print(f"step {step + 1}: max |T / T0 - 1| = {dev:.3e}, bound {bound:.3e}, C = {c:.3e}, G = {g_max:.3e}")
+        assert dev <= bound * (1.0 + 1.0e-6)
+    assert np.abs(x.SlopeInterface[: x.ne]).max() > 0.0 and np.abs(x.VertDiffusivity[:n, 1:]).max() > 0.0
+    assert not np.array_equal(x.h[0][:n], x.lagrangian_h[:n])
+    assert not np.array_equal(tr[1, :n], x.start[2][1, :n])  # the salinity went through all of it
+    # the two exact parts, on the arrays the last step left
+    flat = np.full((1, x.nc_size, K), phi0)
+    tend = np.full((1, x.nc_size, K), 0.375)
+    RR.add_tracer_tend(tend, x.h[1], flat, 1, x.column["ZMid"], x.SlopeInterface, x.f["RediKappa"], x.redi_tables, x.lo, x.hi,
+                       x.lo_e, x.hi_e)
+    assert np.all(tend == 0.375)
+    WR.remap_tracers(x.lagrangian_h, x.RemapTarget, flat, 1, x.lo, x.hi, n, 3)
+    assert np.all(flat == phi0)
+
+
 _BASE = {}
 
 
@@ -190,14 +380,21 @@ def _base(rung):
     if rung not in _BASE:
         x = _two_steps(rung)
         assert all(np.isfinite(a[0]).all() for a in (x.h, x.u, x.tr))
-        _BASE[rung] = (x.h[0], x.u[0], x.tr[0])
+        _BASE[rung] = (x.h[0], x.u[0], x.tr[0], {name: np.array(getattr(x, name)) for name in ("TracerTend",)})
     return _BASE[rung]
+
+
+# A mistake that only reorders a sum changes the last bit of a tendency, which the update it feeds mostly rounds away
+# (Dt TracerTend is some 2^-15 of h phi on these rigs).  The GPU comparison sees the tendency itself; so does this test,
+# for the mistakes named here and for no other.
+ALSO_COMPARED = {"redi_before_mono": ("TracerTend",)}
 
 
 @pytest.mark.parametrize("deviation", DEVIATIONS)
 def test_a_deviation_changes_the_state_on_every_rig_it_is_used_with(deviation):
     """Two steps of the sequence with one mistake in it differ from two steps of the sequence in at least one bit of
-    (h, u, tracers), on the rig of every rung of the GPU comparison that attaches what the mistake is about.
+    (h, u, tracers), on the rig of every rung of the GPU comparison that attaches what the mistake is about (for a
+    mistake of ALSO_COMPARED: of the state or of the kept arrays named there, which the GPU comparison reads as well).
 
     btr_velocity_reset zeroes BtrVelocity between steps in both senses: between two time steps, which alone changes
     nothing on any rig -- step 2 of the sequence, splitVelocityAndSSH, writes BtrVelocity on every edge < NEdgesAll before
@@ -208,8 +405,11 @@ def test_a_deviation_changes_the_state_on_every_rig_it_is_used_with(deviation):
     blind = []
     for rung in rungs:
         got = _two_steps(rung, (deviation,))
-        differs = [not np.array_equal(a[0], b) for a, b in zip((got.h, got.u, got.tr), _base(rung))]
-        print(f"{deviation} on {rung}: h, u, tracers differ: {differs}")
+        base = _base(rung)
+        differs = [not np.array_equal(a[0], b) for a, b in zip((got.h, got.u, got.tr), base)]
+        also = {name: not np.array_equal(getattr(got, name), base[3][name]) for name in ALSO_COMPARED.get(deviation, ())}
+        print(f"{deviation} on {rung}: h, u, tracers differ: {differs} {also or ''}")
+        differs += list(also.values())
         if not any(differs):
             blind.append(rung)
     assert not blind, f"{deviation} changes nothing on {blind}"
@@ -220,8 +420,12 @@ def test_every_deviation_is_used_on_some_rung():
     for spec in RUNGS.values():
         used |= set(deviations_of(spec["opt"]))
     assert used == set(DEVIATIONS)
-    everything = set(deviations_of(RUNGS["G"]["opt"]))
-    assert everything == set(DEVIATIONS)  # and all of them on the rung with everything attached
+    # all of the sequence up to the VertMixStep hook on the rung that attaches all of that ...
+    assert set(deviations_of(RUNGS["G"]["opt"])) == set(DEVIATIONS[:9]) and DEVIATIONS[8] == "btr_velocity_reset"
+    # ... and all of them on the two ragged rungs that attach everything between them (the VertRemap and the VertAdv
+    # refuse each other)
+    both = set(deviations_of(RUNGS["L_vertadv"]["opt"])) | set(deviations_of(RUNGS["L_remap"]["opt"]))
+    assert both == set(DEVIATIONS) and len(DEVIATIONS) == 19
 
 
 @pytest.mark.parametrize("rung", ["F", "G"])
