@@ -6,6 +6,12 @@ HorzMesh, OceanState, Tracers, AuxiliaryState, VertCoord, Eos, VertMix, VertMixS
 TimeStepper).  There is no
 Python or CPU implementation of the hot path here: if the shared library is missing,
 importing the binding raises, and without a HIP device every device call fails.
+
+The header is also the binding's statement of what the functions take: omega_amd/header.py reads it, lib() sets the
+argtypes and restype of every declared function from it and hands out no other symbol, and the struct mirrors are
+built from its struct bodies.  So call sites pass plain Python values -- an int for an int, a size or an address of
+any width, a float for a double, bytes for a string, None for NULL -- and a wrong type or count is a ctypes error
+before the library is entered.  numpy integers are not addresses to ctypes: int(x) where one may arrive.
 """
 from __future__ import annotations
 
@@ -15,8 +21,11 @@ import subprocess
 
 import numpy as np
 
+from . import header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMEGA_AMD_LIB", os.path.join(_HERE, "lib", "libomega_amd.so"))
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "omega_amd.h")
 
 ON_CELL, ON_EDGE, ON_VERTEX = 0, 1, 2
 
@@ -37,26 +46,30 @@ def build(force: bool = False) -> str:
     return LIB_PATH
 
 
+try:
+    _FUNCTIONS, _STRUCTS = header.read(HEADER_PATH)
+except (OSError, header.HeaderError) as e:   # a missing header, or a declaration the reader does not know
+    raise OmegaAmdError(f"the binding takes its prototypes and structs from include/omega_amd.h: {e}") from None
+_MEMBER = {"int32_t": C.c_int32, "double": C.c_double, "const int32_t *": PI, "const double *": PD}
+
+
+def _mirror(struct: str) -> list:
+    """the _fields_ of the header's struct, in its order"""
+    return [(name, _MEMBER[kind]) for name, kind in _STRUCTS[struct]]
+
+
 class GlobalMeshC(C.Structure):
-    _I = ("cellsOnCell", "edgesOnCell", "verticesOnCell", "cellsOnEdge", "verticesOnEdge", "edgesOnEdge",
-          "cellsOnVertex", "edgesOnVertex")
-    _R = ("xCell", "yCell", "zCell", "lonCell", "latCell", "xEdge", "yEdge", "zEdge", "lonEdge", "latEdge",
-          "xVertex", "yVertex", "zVertex", "lonVertex", "latVertex", "areaCell", "areaTriangle",
-          "kiteAreasOnVertex", "dcEdge", "dvEdge", "angleEdge", "weightsOnEdge", "fCell", "fEdge", "fVertex",
-          "bottomDepth")
-    _fields_ = ([(n, C.c_int32) for n in ("nCells", "nEdges", "nVertices", "maxEdges", "vertexDegree")]
-                + [(n, PI) for n in _I] + [(n, PD) for n in _R])
-
-
-CONFIG_FLAGS = ("ThicknessFluxTendencyEnable", "PVTendencyEnable", "KETendencyEnable", "SSHTendencyEnable",
-                "VelDiffTendencyEnable", "VelHyperDiffTendencyEnable", "WindForcingTendencyEnable",
-                "BottomDragTendencyEnable", "TracerHorzAdvTendencyEnable", "TracerDiffTendencyEnable",
-                "TracerHyperDiffTendencyEnable", "FluxThicknessUpwind", "FluxTracerUpwind", "WindInterpIsotropic")
-CONFIG_REALS = ("ViscDel2", "ViscDel4", "DivFactor", "EddyDiff2", "EddyDiff4", "Density0", "BottomDragCoeff")
+    _fields_ = _mirror("omg_global_mesh")
+    _I = tuple(n for n, t in _fields_ if t is PI)
+    _R = tuple(n for n, t in _fields_ if t is PD)
 
 
 class TendConfig(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in CONFIG_FLAGS] + [(n, C.c_double) for n in CONFIG_REALS]
+    _fields_ = _mirror("omg_tend_config")
+
+
+CONFIG_FLAGS = tuple(n for n, t in TendConfig._fields_ if t is C.c_int32)
+CONFIG_REALS = tuple(n for n, t in TendConfig._fields_ if t is C.c_double)
 
 
 TRANSPORT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, PI, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -65,20 +78,39 @@ TRANSPORT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, PI, C.POINTER(C.c_void_
 CUSTOM_TEND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                              C.c_int, C.c_double, C.c_void_p)
 
+_ARGTYPE = {"int": C.c_int, "double": C.c_double, "size_t": C.c_size_t, "int64_t": C.c_int64,
+            "const char *": C.c_char_p, "char *": C.c_char_p}   # every other kind is a pointer: c_void_p
+_RESTYPE = {"int": C.c_int, "void": None, "const char *": C.c_char_p}
+
+
+class _Library:
+    """The functions include/omega_amd.h declares, each with the header's prototype set, and no other attribute."""
+
+    def __init__(self, dll):
+        missing = [name for name in _FUNCTIONS if not hasattr(dll, name)]
+        if missing:
+            raise OmegaAmdError(f"{LIB_PATH} does not export what {HEADER_PATH} declares: {', '.join(missing)}")
+        for name, (ret, params) in _FUNCTIONS.items():
+            fn = getattr(dll, name)
+            fn.restype, fn.argtypes = _RESTYPE[ret], [_ARGTYPE.get(kind, C.c_void_p) for kind in params]
+            setattr(self, name, fn)
+
+    def __getattr__(self, name):
+        raise AttributeError(f"{name} is not declared in include/omega_amd.h: the binding hands out no other symbol")
+
+
 _lib = None
 
 
 def lib():
-    """The loaded library; raises if it has not been built (no fallback)."""
+    """The loaded library with the header's prototypes applied; raises if it has not been built (no fallback)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise OmegaAmdError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc, gfx950). omega_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        L.omg_last_error.restype = C.c_char_p
-        _lib = L
+        _lib = _Library(C.CDLL(LIB_PATH))
         # test / measurement plumbing (this file, not the library): OMEGA_AMD_OPTIONS="MergeL1=0,Pair=0" is turned into
         # omg_set_option calls, so that a whole pytest or bench.py run can be repeated under another kernel structure
         for item in filter(None, os.environ.get("OMEGA_AMD_OPTIONS", "").split(",")):
@@ -89,18 +121,28 @@ def lib():
 
 def set_option(name: str, value: int):
     """omg_set_option (omega_amd/csrc/Tuning.h): measurement / test switches; the library never reads the environment."""
-    _chk(lib().omg_set_option(name.encode(), int(value)))
+    _chk(lib().omg_set_option(name.encode(), value))
 
 
 def get_option(name: str) -> int:
-    v = C.c_int()
-    _chk(lib().omg_get_option(name.encode(), C.byref(v)))
-    return v.value
+    return _out(C.c_int, lib().omg_get_option, name.encode())
+
+
+def last_error() -> str:
+    """omg_last_error: the message of the last failure on the calling thread"""
+    return lib().omg_last_error().decode()
 
 
 def _chk(rc):
     if rc != 0:
-        raise OmegaAmdError(lib().omg_last_error().decode())
+        raise OmegaAmdError(last_error())
+
+
+def _out(ctype, fn, *args):
+    """what `fn` writes through its last parameter, a pointer to a `ctype`"""
+    v = ctype()
+    _chk(fn(*args, C.byref(v)))
+    return v.value
 
 
 def _pd(a):
@@ -124,9 +166,7 @@ class _Handle:
 
     def _create(self, symbol: str, *args):
         """self.h from a create / open function whose last argument receives the handle"""
-        h = C.c_void_p()
-        _chk(getattr(lib(), symbol)(*args, C.byref(h)))
-        self.h = h
+        self.h = C.c_void_p(_out(C.c_void_p, getattr(lib(), symbol), *args))
 
     def _release(self):
         if self.h:
@@ -141,9 +181,7 @@ class _Handle:
 
 
 def device_count() -> int:
-    n = C.c_int(0)
-    _chk(lib().omg_device_count(C.byref(n)))
-    return n.value
+    return _out(C.c_int, lib().omg_device_count)
 
 
 def device_init(dev: int = 0):
@@ -158,9 +196,7 @@ class Stream:
     def __init__(self, handle=None):
         self.own = handle is None
         if handle is None:
-            h = C.c_void_p()
-            _chk(lib().omg_stream_create(C.byref(h)))
-            handle = h.value
+            handle = _out(C.c_void_p, lib().omg_stream_create)
         self.h = C.c_void_p(handle)
 
     def synchronize(self):
@@ -184,12 +220,11 @@ class Event(_Handle):
         _chk(lib().omg_event_record(self.h, stream.h if stream else None))
 
     def elapsed_ms(self, stop: "Event") -> float:
-        ms = C.c_float()
-        _chk(lib().omg_event_elapsed_ms(self.h, stop.h, C.byref(ms)))
-        return ms.value
+        return _out(C.c_float, lib().omg_event_elapsed_ms, self.h, stop.h)
 
 
 def _sh(s):
+    """the handle of a Stream or of any object that owns one, NULL for None"""
     return s.h if s is not None else None
 
 
@@ -202,14 +237,10 @@ class GlobalMesh:
         s = GlobalMeshC()
         s.nCells, s.nEdges, s.nVertices = g["nCells"], g["nEdges"], g["nVertices"]
         s.maxEdges, s.vertexDegree = g["maxEdges"], g["vertexDegree"]
-        for n in GlobalMeshC._I:
-            a = np.ascontiguousarray(g[n], dtype=np.int32)
-            self.keep[n] = a
-            setattr(s, n, _pi(a))
-        for n in GlobalMeshC._R:
-            a = np.ascontiguousarray(g[n], dtype=np.float64)
-            self.keep[n] = a
-            setattr(s, n, _pd(a))
+        for names, dtype, pointer in ((GlobalMeshC._I, np.int32, _pi), (GlobalMeshC._R, np.float64, _pd)):
+            for n in names:
+                self.keep[n] = np.ascontiguousarray(g[n], dtype=dtype)
+                setattr(s, n, pointer(self.keep[n]))
         self.s = s
 
 
@@ -218,24 +249,22 @@ def write_restart(path, decomp, state, tracers, K, NT, simulation_time, steps_do
     level 0) at their global positions.  `barrier` (callable) separates the two phases when there are
     several ranks."""
     if rank == 0:
-        _chk(lib().omg_restart_create(os.fsencode(path), C.c_int64(decomp.get_int("NCellsGlobal")),
-                                      C.c_int64(decomp.get_int("NEdgesGlobal")), K, NT, C.c_double(simulation_time),
-                                      C.c_int64(steps_done)))
+        _chk(lib().omg_restart_create(os.fsencode(path), decomp.get_int("NCellsGlobal"), decomp.get_int("NEdgesGlobal"),
+                                      K, NT, simulation_time, steps_done))
     if barrier is not None:
         barrier()
-    f = C.c_void_p()
-    _chk(lib().omg_restart_open(os.fsencode(path), 1, C.byref(f)))
+    f = _out(C.c_void_p, lib().omg_restart_open, os.fsencode(path), 1)
     try:
         nc, ne = decomp.get_int("NCellsOwned"), decomp.get_int("NEdgesOwned")
         cid = np.ascontiguousarray(decomp.get_array("CellID")[:nc], dtype=np.int32)
         eid = np.ascontiguousarray(decomp.get_array("EdgeID")[:ne], dtype=np.int32)
         h, u = state.copy_to_host(0)
-        _chk(lib().omg_restart_write_rows(f, b"layerThickness", 0, _pi(cid), C.c_int64(nc), _pd(np.ascontiguousarray(h[:nc]))))
-        _chk(lib().omg_restart_write_rows(f, b"normalVelocity", 0, _pi(eid), C.c_int64(ne), _pd(np.ascontiguousarray(u[:ne]))))
+        _chk(lib().omg_restart_write_rows(f, b"layerThickness", 0, _pi(cid), nc, _pd(np.ascontiguousarray(h[:nc]))))
+        _chk(lib().omg_restart_write_rows(f, b"normalVelocity", 0, _pi(eid), ne, _pd(np.ascontiguousarray(u[:ne]))))
         if NT > 0:
             tr = tracers.copy_to_host(0)
             for l in range(NT):
-                _chk(lib().omg_restart_write_rows(f, b"tracers", l, _pi(cid), C.c_int64(nc), _pd(np.ascontiguousarray(tr[l, :nc]))))
+                _chk(lib().omg_restart_write_rows(f, b"tracers", l, _pi(cid), nc, _pd(np.ascontiguousarray(tr[l, :nc]))))
     finally:
         lib().omg_restart_close(f)
     if barrier is not None:
@@ -245,18 +274,14 @@ def write_restart(path, decomp, state, tracers, K, NT, simulation_time, steps_do
 def write_history(path, decomp, state, tracers, aux, contents="State,Tracers,AuxiliaryState", simulation_time=0.0,
                   time_level=0, create_file=True, stream=None) -> int:
     """One history dump (omg_history_write): field names / groups as in the reference's History stream Contents."""
-    n = C.c_int()
-    _chk(lib().omg_history_write(os.fsencode(path), decomp.h, state.h, tracers.h if tracers is not None else None, aux.h,
-                                 contents.encode(), C.c_double(simulation_time), time_level, int(create_file), _sh(stream),
-                                 C.byref(n)))
-    return n.value
+    return _out(C.c_int, lib().omg_history_write, os.fsencode(path), decomp.h, state.h, _sh(tracers), aux.h,
+                contents.encode(), simulation_time, time_level, create_file, _sh(stream))
 
 
 def read_restart(path, decomp, mesh, state, tracers, K, NT):
     """Restart load: every rank reads the rows of ALL its local cells / edges (owned and halo, by global
     id) into time level 0, so no halo exchange is needed afterwards.  Returns (simulation_time, steps_done)."""
-    f = C.c_void_p()
-    _chk(lib().omg_restart_open(os.fsencode(path), 0, C.byref(f)))
+    f = _out(C.c_void_p, lib().omg_restart_open, os.fsencode(path), 0)
     try:
         info = [C.c_int64(), C.c_int64(), C.c_int(), C.c_int(), C.c_double(), C.c_int64()]
         _chk(lib().omg_restart_info(f, *[C.byref(x) for x in info]))
@@ -269,17 +294,17 @@ def read_restart(path, decomp, mesh, state, tracers, K, NT):
         h = np.zeros((mesh.NCellsSize, K))
         u = np.zeros((mesh.NEdgesSize, K))
         rows = np.empty((nc, K))
-        _chk(lib().omg_restart_read_rows(f, b"layerThickness", 0, _pi(cid), C.c_int64(nc), _pd(rows)))
+        _chk(lib().omg_restart_read_rows(f, b"layerThickness", 0, _pi(cid), nc, _pd(rows)))
         h[:nc] = rows
         rows = np.empty((ne, K))
-        _chk(lib().omg_restart_read_rows(f, b"normalVelocity", 0, _pi(eid), C.c_int64(ne), _pd(rows)))
+        _chk(lib().omg_restart_read_rows(f, b"normalVelocity", 0, _pi(eid), ne, _pd(rows)))
         u[:ne] = rows
         state.copy_to_device(h, u, 0)
         if NT > 0:
             tr = np.zeros((NT, mesh.NCellsSize, K))
             rows = np.empty((nc, K))
             for l in range(NT):
-                _chk(lib().omg_restart_read_rows(f, b"tracers", l, _pi(cid), C.c_int64(nc), _pd(rows)))
+                _chk(lib().omg_restart_read_rows(f, b"tracers", l, _pi(cid), nc, _pd(rows)))
                 tr[l, :nc] = rows
             tracers.copy_to_device(tr, 0)
         return info[4].value, info[5].value
@@ -304,17 +329,14 @@ class MeshFile(_Handle):
         self.gm = gm
 
     def dim(self, name: str) -> int:
-        v = C.c_int64()
-        _chk(lib().omg_mesh_file_dim(self.h, name.encode(), C.byref(v)))
-        return v.value
+        return _out(C.c_int64, lib().omg_mesh_file_dim, self.h, name.encode())
 
     def read(self, name: str, record: int = -1) -> np.ndarray:
-        n = C.c_int64()
-        _chk(lib().omg_mesh_file_var_size(self.h, name.encode(), C.c_int64(record), C.byref(n)))
-        if n.value < 0:
+        n = _out(C.c_int64, lib().omg_mesh_file_var_size, self.h, name.encode(), record)
+        if n < 0:
             raise KeyError(name)
-        out = np.empty(n.value, dtype=np.float64)
-        _chk(lib().omg_mesh_file_read_f64(self.h, name.encode(), C.c_int64(record), _pd(out), C.c_size_t(n.value)))
+        out = np.empty(n, dtype=np.float64)
+        _chk(lib().omg_mesh_file_read_f64(self.h, name.encode(), record, _pd(out), n))
         return out
 
     def arrays(self) -> dict:
@@ -342,19 +364,17 @@ class DeviceBuffer:
 
     def __init__(self, host: np.ndarray):
         self.host = np.ascontiguousarray(host)
-        p = C.c_void_p()
-        _chk(lib().omg_device_malloc(C.c_size_t(self.host.nbytes), C.byref(p)))
-        self.ptr = p.value
-        _chk(lib().omg_copy_to_device(C.c_void_p(self.ptr), self.host.ctypes.data_as(C.c_void_p), C.c_size_t(self.host.nbytes)))
+        self.ptr = _out(C.c_void_p, lib().omg_device_malloc, self.host.nbytes)
+        _chk(lib().omg_copy_to_device(self.ptr, self.host.ctypes.data, self.host.nbytes))
 
     def to_host(self) -> np.ndarray:
         out = np.empty_like(self.host)
-        _chk(lib().omg_copy_to_host(out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr), C.c_size_t(out.nbytes)))
+        _chk(lib().omg_copy_to_host(out.ctypes.data, self.ptr, out.nbytes))
         return out
 
     def __del__(self):
         try:
-            lib().omg_device_free(C.c_void_p(self.ptr))
+            lib().omg_device_free(self.ptr)
         except Exception:
             pass
 
@@ -362,7 +382,7 @@ class DeviceBuffer:
 def copy_to_device(dev_ptr: int, host: np.ndarray):
     """omg_copy_to_device: a contiguous host array to raw device memory (synchronous)"""
     a = np.ascontiguousarray(host)
-    _chk(lib().omg_copy_to_device(C.c_void_p(dev_ptr), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes)))
+    _chk(lib().omg_copy_to_device(dev_ptr, a.ctypes.data, a.nbytes))
 
 
 def combine_dd(pairs) -> tuple:
@@ -376,7 +396,7 @@ def combine_dd(pairs) -> tuple:
 def local_sum_dd(a_ptr: int, n: int, b_ptr: int = 0, stream=None) -> tuple:
     """Double-double sum of n device doubles at a_ptr (times those at b_ptr if given)."""
     out = (C.c_double * 2)()
-    _chk(lib().omg_local_sum_dd(C.c_void_p(a_ptr), C.c_void_p(b_ptr) if b_ptr else None, C.c_size_t(n), _sh(stream), out))
+    _chk(lib().omg_local_sum_dd(a_ptr, b_ptr or None, n, _sh(stream), out))
     return out[0], out[1]
 
 
@@ -388,16 +408,13 @@ def level_pitch(k: int) -> int:
 def local_weighted_sum_dd(w_ptr: int, a_ptr: int, nrows: int, k: int, b_ptr: int = 0, stream=None, row_pitch: int = 0) -> tuple:
     """row_pitch: pitch of the [rows][k] arrays in values (level_pitch(k) for arrays owned by the library, 0 = compact)"""
     out = (C.c_double * 2)()
-    _chk(lib().omg_local_weighted_sum_dd(C.c_void_p(w_ptr), C.c_void_p(a_ptr), C.c_void_p(b_ptr) if b_ptr else None,
-                                         nrows, k, row_pitch, _sh(stream), out))
+    _chk(lib().omg_local_weighted_sum_dd(w_ptr, a_ptr, b_ptr or None, nrows, k, row_pitch, _sh(stream), out))
     return out[0], out[1]
 
 
 def device_resource_count() -> int:
     """omg_device_resource_count: device buffers, streams and events the library has created so far"""
-    n = C.c_int64()
-    _chk(lib().omg_device_resource_count(C.byref(n)))
-    return n.value
+    return _out(C.c_int64, lib().omg_device_resource_count)
 
 
 _TRIDIAG = {("general", "pcr"): "omg_tridiag_pcr_solve", ("general", "thomas"): "omg_tridiag_thomas_solve",
@@ -415,8 +432,7 @@ def _tridiag(form, algorithm, coeffs, x, stream, nbatch, nrow, row_pitch):
     if isinstance(x, (int, np.integer)):
         if nbatch is None or nrow is None:
             raise ValueError("the device-address form needs nbatch and nrow")
-        ptrs = [C.c_void_p(int(a)) for a in coeffs] + [C.c_void_p(int(x))]
-        _chk(fn(*ptrs, int(nbatch), int(nrow), int(row_pitch), _sh(stream)))
+        _chk(fn(*[int(a) for a in (*coeffs, x)], nbatch, nrow, row_pitch, _sh(stream)))
         return None
     arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (*coeffs, x)]
     shape = arrs[-1].shape
@@ -424,7 +440,7 @@ def _tridiag(form, algorithm, coeffs, x, stream, nbatch, nrow, row_pitch):
         raise OmegaAmdError(f"tridiagonal solve: every array must be [NBatch][NRow] of one shape, got "
                             f"{[a.shape for a in arrs]}")
     bufs = [DeviceBuffer(a) for a in arrs]
-    _chk(fn(*[C.c_void_p(b.ptr) for b in bufs], shape[0], shape[1], 0, _sh(stream)))
+    _chk(fn(*[b.ptr for b in bufs], shape[0], shape[1], 0, _sh(stream)))
     if stream is not None:
         stream.synchronize()
     return bufs[-1].to_host()
@@ -469,9 +485,7 @@ def read_partition_file(path: str) -> np.ndarray:
 def partition_cells(gm: GlobalMesh, nparts: int, method: str = "graph"):
     """(cell_task[nCells], edge_cut) of the built-in partitioners: "rcb" or "graph" (omg_partition_cells)."""
     out = np.zeros(gm.s.nCells, dtype=np.int32)
-    cut = C.c_int64()
-    _chk(lib().omg_partition_cells(C.byref(gm.s), nparts, method.encode(), _pi(out), C.byref(cut)))
-    return out, cut.value
+    return out, _out(C.c_int64, lib().omg_partition_cells, C.byref(gm.s), nparts, method.encode(), _pi(out))
 
 
 class Decomp(_Handle):
@@ -488,9 +502,7 @@ class Decomp(_Handle):
                      {"global": 0, "curve": 1, "hilbert": 2, "kd": 3}[local_order])
 
     def get_int(self, name: str) -> int:
-        v = C.c_int32()
-        _chk(lib().omg_decomp_get_int(self.h, name.encode(), C.byref(v)))
-        return v.value
+        return _out(C.c_int32, lib().omg_decomp_get_int, self.h, name.encode())
 
     def get_array(self, name: str) -> np.ndarray:
         hw = self.get_int("HaloWidth")
@@ -500,7 +512,7 @@ class Decomp(_Handle):
                   "NCellsHalo": (hw,), "NEdgesHalo": (hw,), "NVerticesHalo": (hw,),
                   "CellTask": (self.get_int("NCellsGlobal"),)}
         out = np.zeros(shapes[name], dtype=np.int32)
-        _chk(lib().omg_decomp_get_array(self.h, name.encode(), _pi(out), C.c_size_t(out.size)))
+        _chk(lib().omg_decomp_get_array(self.h, name.encode(), _pi(out), out.size))
         return out
 
 
@@ -550,7 +562,7 @@ class PeerWire(_Handle):
     HANDLE_BYTES = 160
 
     def __init__(self, nranks: int, rank: int, mailbox_bytes: int):
-        self._create("omg_peer_create", nranks, rank, C.c_size_t(mailbox_bytes))
+        self._create("omg_peer_create", nranks, rank, mailbox_bytes)
         self.nranks = nranks
 
     def handle(self) -> bytes:
@@ -569,7 +581,7 @@ class PeerWire(_Handle):
         return {"exchanges": e.value, "status": s.value}
 
     def set_timeout(self, seconds: float):
-        _chk(lib().omg_peer_set_timeout(self.h, C.c_double(seconds)))
+        _chk(lib().omg_peer_set_timeout(self.h, seconds))
 
     def close(self):
         self._release()
@@ -586,26 +598,17 @@ class Halo(_Handle):
 
     @property
     def neighbors(self):
-        n = C.c_int()
-        _chk(lib().omg_halo_num_neighbors(self.h, C.byref(n)))
-        out = []
-        for i in range(n.value):
-            t = C.c_int()
-            _chk(lib().omg_halo_neighbor_task(self.h, i, C.byref(t)))
-            out.append(t.value)
-        return out
+        n = _out(C.c_int, lib().omg_halo_num_neighbors, self.h)
+        return [_out(C.c_int, lib().omg_halo_neighbor_task, self.h, i) for i in range(n)]
 
     def get_list(self, i: int, elem: int, recv: bool) -> np.ndarray:
-        n = C.c_int()
-        _chk(lib().omg_halo_list_size(self.h, i, elem, int(recv), C.byref(n)))
-        out = np.zeros(max(n.value, 1), dtype=np.int32)
-        _chk(lib().omg_halo_get_list(self.h, i, elem, int(recv), _pi(out)))
-        return out[: n.value]
+        n = _out(C.c_int, lib().omg_halo_list_size, self.h, i, elem, recv)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        _chk(lib().omg_halo_get_list(self.h, i, elem, recv, _pi(out)))
+        return out[:n]
 
     def required_bytes(self, i: int, per_cell: int, per_edge: int, per_vertex: int = 0) -> int:
-        b = C.c_size_t()
-        _chk(lib().omg_halo_required_bytes(self.h, i, C.c_size_t(per_cell), C.c_size_t(per_edge), C.c_size_t(per_vertex), C.byref(b)))
-        return b.value
+        return _out(C.c_size_t, lib().omg_halo_required_bytes, self.h, i, per_cell, per_edge, per_vertex)
 
     def use_rccl(self, comm: "RcclComm"):
         """Route the exchanges through RCCL send / recv issued inside the library (production wire)."""
@@ -626,7 +629,7 @@ class Halo(_Handle):
 
     def exchange_state(self, state, tracers=None, time_level: int = 0, tracers_time_level: int | None = None, stream=None):
         """omg_halo_exchange_state: h, u and the tracers as ONE message per neighbour (what the time steppers do after a stage)"""
-        _chk(lib().omg_halo_exchange_state(self.h, state.h, time_level, tracers.h if tracers is not None else None,
+        _chk(lib().omg_halo_exchange_state(self.h, state.h, time_level, _sh(tracers),
                                            time_level if tracers_time_level is None else tracers_time_level, _sh(stream)))
 
     def check(self):
@@ -634,9 +637,7 @@ class Halo(_Handle):
         _chk(lib().omg_halo_check(self.h))
 
     def recv_rows(self, per_cell: int, per_edge: int, per_vertex: int = 0) -> int:
-        r = C.c_size_t()
-        _chk(lib().omg_halo_recv_rows(self.h, C.c_size_t(per_cell), C.c_size_t(per_edge), C.c_size_t(per_vertex), C.byref(r)))
-        return r.value
+        return _out(C.c_size_t, lib().omg_halo_recv_rows, self.h, per_cell, per_edge, per_vertex)
 
     def set_transport(self, fn):
         """fn(tasks, send_ptrs, send_bytes, recv_ptrs, recv_bytes, stream_handle) -> int"""
@@ -656,10 +657,9 @@ class Halo(_Handle):
         """Halo::exchangeFullArrayHalo on a raw device array [nt][rows_size][row_pitch or k] of elem_bytes-byte values
         (8: R8 / I8, 4: I4 / R4); rank 1 is nt = 1, k = 1."""
         if elem_bytes == 8:
-            _chk(lib().omg_halo_exchange(self.h, C.cast(C.c_void_p(dev_ptr), PD), nt, rows_size, k, row_pitch, elem, _sh(stream)))
+            _chk(lib().omg_halo_exchange(self.h, dev_ptr, nt, rows_size, k, row_pitch, elem, _sh(stream)))
         else:
-            _chk(lib().omg_halo_exchange_bytes(self.h, C.c_void_p(dev_ptr), elem_bytes, nt, rows_size, k, row_pitch, elem,
-                                               _sh(stream)))
+            _chk(lib().omg_halo_exchange_bytes(self.h, dev_ptr, elem_bytes, nt, rows_size, k, row_pitch, elem, _sh(stream)))
 
 
 _MESH_I4 = {"CellsOnCell": ("C", "ME"), "EdgesOnCell": ("C", "ME"), "NEdgesOnCell": ("C",),
@@ -680,13 +680,11 @@ class HorzMesh(_Handle):
 
     def __init__(self, decomp: Decomp, nvertlayers: int, host_only: bool = False):
         self.decomp = decomp
-        self._create("omg_mesh_create", decomp.h, nvertlayers, int(host_only))
+        self._create("omg_mesh_create", decomp.h, nvertlayers, host_only)
         self._dims = None
 
     def get_int(self, name: str) -> int:
-        v = C.c_int32()
-        _chk(lib().omg_mesh_get_int(self.h, name.encode(), C.byref(v)))
-        return v.value
+        return _out(C.c_int32, lib().omg_mesh_get_int, self.h, name.encode())
 
     def __getattr__(self, name):
         if name.startswith("N") or name in ("MaxEdges", "MaxEdges2", "VertexDegree"):
@@ -707,10 +705,10 @@ class HorzMesh(_Handle):
     def get_array(self, name: str) -> np.ndarray:
         if name in _MESH_I4:
             out = np.zeros(self._shape(_MESH_I4[name]), dtype=np.int32)
-            _chk(lib().omg_mesh_get_array_i4(self.h, name.encode(), _pi(out), C.c_size_t(out.size)))
+            _chk(lib().omg_mesh_get_array_i4(self.h, name.encode(), _pi(out), out.size))
         else:
             out = np.zeros(self._shape(_MESH_R8[name]), dtype=np.float64)
-            _chk(lib().omg_mesh_get_array_r8(self.h, name.encode(), _pd(out), C.c_size_t(out.size)))
+            _chk(lib().omg_mesh_get_array_r8(self.h, name.encode(), _pd(out), out.size))
         return out
 
     def local_arrays(self) -> dict:
@@ -742,9 +740,9 @@ class HorzOperators:
         din = DeviceBuffer(x)
         dout = DeviceBuffer(np.zeros((rows_out,) if one_d else (rows_out, k)))
         if one_d:
-            _chk(fn(self.mesh.h, C.c_void_p(din.ptr), C.c_void_p(dout.ptr), *extra, n, None))
+            _chk(fn(self.mesh.h, din.ptr, dout.ptr, *extra, n, None))
         else:
-            _chk(fn(self.mesh.h, C.c_void_p(din.ptr), C.c_void_p(dout.ptr), k, 0, n, None))
+            _chk(fn(self.mesh.h, din.ptr, dout.ptr, k, 0, n, None))
         device_synchronize()
         return dout.to_host()
 
@@ -761,17 +759,23 @@ class HorzOperators:
         return self._run(lib().omg_horz_tangential_recon, vec_edge, self.mesh.NEdgesSize, n)
 
     def interp_cell_to_edge(self, array_cell, isotropic: bool, n=-1):
-        return self._run(lib().omg_horz_interp_cell_to_edge, array_cell, self.mesh.NEdgesSize, n, int(isotropic))
+        return self._run(lib().omg_horz_interp_cell_to_edge, array_cell, self.mesh.NEdgesSize, n, isotropic)
 
 
-def default_config(**over) -> TendConfig:
-    c = TendConfig()
-    lib().omg_tend_config_default(C.byref(c))
+def _config(cls, default: str, over: dict):
+    """A `cls` struct with the library's defaults (the function `default`) and the fields in `over` replaced; an
+    unknown field raises KeyError."""
+    c = cls()
+    _chk(getattr(lib(), default)(C.byref(c)) or 0)   # (omg_tend_config_default returns nothing)
     for k, v in over.items():
-        if not hasattr(c, k):
+        if k not in {f[0] for f in cls._fields_}:
             raise KeyError(k)
         setattr(c, k, v)
     return c
+
+
+def default_config(**over) -> TendConfig:
+    return _config(TendConfig, "omg_tend_config_default", over)
 
 
 class OceanState(_Handle):
@@ -791,9 +795,7 @@ class OceanState(_Handle):
         return h, u
 
     def device_ptr(self, which: int, time_level: int = 0) -> int:
-        p = PD()
-        _chk(lib().omg_state_device_ptr(self.h, time_level, which, C.byref(p)))
-        return C.cast(p, C.c_void_p).value
+        return _out(C.c_void_p, lib().omg_state_device_ptr, self.h, time_level, which)
 
     def exchange_halo(self, time_level: int = 0, stream=None):
         _chk(lib().omg_state_exchange_halo(self.h, time_level, _sh(stream)))
@@ -819,9 +821,7 @@ class Tracers(_Handle):
         return tr
 
     def device_ptr(self, time_level: int = 0) -> int:
-        p = PD()
-        _chk(lib().omg_tracers_device_ptr(self.h, time_level, C.byref(p)))
-        return C.cast(p, C.c_void_p).value
+        return _out(C.c_void_p, lib().omg_tracers_device_ptr, self.h, time_level)
 
     def exchange_halo(self, time_level: int = 0, stream=None):
         _chk(lib().omg_tracers_exchange_halo(self.h, time_level, _sh(stream)))
@@ -843,24 +843,24 @@ class _NamedArrays:
     def get(self, name: str) -> np.ndarray:
         if name in self._i4:
             out = np.zeros(self._shape(name), dtype=np.int32)
-            self._array_call("copy_to_host_i4", name, _pi(out), C.c_size_t(out.size))
+            self._array_call("copy_to_host_i4", name, _pi(out), out.size)
         else:
             out = np.zeros(self._shape(name))
-            self._array_call("copy_to_host", name, _pd(out), C.c_size_t(out.size))
+            self._array_call("copy_to_host", name, _pd(out), out.size)
         return out
 
     def set(self, name: str, values: np.ndarray):
         if name in self._i4:
             v = np.ascontiguousarray(values, dtype=np.int32)
-            self._array_call("copy_to_device_i4", name, _pi(v), C.c_size_t(v.size))
+            self._array_call("copy_to_device_i4", name, _pi(v), v.size)
         else:
             v = np.ascontiguousarray(values, dtype=np.float64)
-            self._array_call("copy_to_device", name, _pd(v), C.c_size_t(v.size))
+            self._array_call("copy_to_device", name, _pd(v), v.size)
 
     def device_ptr(self, name: str) -> int:
-        p = PD()
+        p = C.c_void_p()
         self._array_call("device_ptr", name, C.byref(p), None)
-        return C.cast(p, C.c_void_p).value
+        return p.value
 
 
 AUX_SHAPES = {"KineticEnergyCell": "C", "VelocityDivCell": "C", "FluxLayerThickEdge": "E", "MeanLayerThickEdge": "E",
@@ -878,8 +878,7 @@ class AuxiliaryState(_Handle, _NamedArrays):
         self._create("omg_aux_create", mesh.h, halo.h if halo else None, nvertlayers, ntracers)
 
     def set_options(self, flux_thickness_upwind=False, flux_tracer_upwind=False, wind_interp_isotropic=True):
-        _chk(lib().omg_aux_set_options(self.h, int(flux_thickness_upwind), int(flux_tracer_upwind),
-                                       int(wind_interp_isotropic)))
+        _chk(lib().omg_aux_set_options(self.h, flux_thickness_upwind, flux_tracer_upwind, wind_interp_isotropic))
 
     def compute_mom_aux(self, state: OceanState, thick_tl=0, vel_tl=0, stream=None):
         _chk(lib().omg_aux_compute_mom_aux(self.h, state.h, thick_tl, vel_tl, _sh(stream)))
@@ -901,7 +900,8 @@ class AuxiliaryState(_Handle, _NamedArrays):
 def _stage_levels(x, lead: tuple, k: int, keep: "list | None" = None):
     """A level-indexed array as (device pointer, staged buffer or None): an int is taken as the device address of
     [*lead][level_pitch(k)] doubles and passed through; a numpy array [*lead][k] is staged into a padded device copy
-    (also appended to `keep`, if given, to stay alive there)."""
+    (also appended to `keep`, if given, to stay alive there).  The pointer is a c_void_p object, as every handle is:
+    callers read its address as `.value`."""
     if isinstance(x, (int, np.integer)):
         return C.c_void_p(int(x)), None
     a = np.asarray(x, dtype=np.float64)
@@ -933,15 +933,7 @@ def _level_dev(x, rows: int, k: int, keep: list):
 
 def _cell_dev(x, rows: int, keep: list):
     """A per-cell input as a device pointer: None (NULL: read as zero), an int device address or a numpy array."""
-    if x is None:
-        return None
-    if isinstance(x, (int, np.integer)):
-        return C.c_void_p(int(x))
-    a = np.ascontiguousarray(x, dtype=np.float64)
-    assert a.shape == (rows,), f"expected shape {(rows,)}, got {a.shape}"
-    b = DeviceBuffer(a)
-    keep.append(b)
-    return C.c_void_p(b.ptr)
+    return None if x is None else _flat_dev(x, (rows,), keep)
 
 
 def _flat_dev(x, shape: tuple, keep: list):
@@ -971,14 +963,13 @@ class Eos(_Handle, _NamedArrays):
     def __init__(self, mesh: HorzMesh, nvertlayers: int, eos_type: str = "teos10", drhodt: float = -0.2,
                  drhods: float = 0.8, rhot0s0: float = 1000.0):
         self.mesh, self.K = mesh, nvertlayers
-        self._create("omg_eos_create", mesh.h, nvertlayers, eos_type.encode(), C.c_double(drhodt), C.c_double(drhods),
-                     C.c_double(rhot0s0))
+        self._create("omg_eos_create", mesh.h, nvertlayers, eos_type.encode(), drhodt, drhods, rhot0s0)
 
     def compute_spec_vol(self, conserv_temp, abs_salinity, pressure, p_scale: float = 1.0, stream=None):
         keep, n = [], self.mesh.NCellsSize
         _chk(lib().omg_eos_compute_spec_vol(self.h, _level_dev(conserv_temp, n, self.K, keep),
                                             _level_dev(abs_salinity, n, self.K, keep),
-                                            _level_dev(pressure, n, self.K, keep), C.c_double(p_scale), _sh(stream)))
+                                            _level_dev(pressure, n, self.K, keep), p_scale, _sh(stream)))
         if keep:
             device_synchronize()
 
@@ -987,8 +978,7 @@ class Eos(_Handle, _NamedArrays):
         keep, n = [], self.mesh.NCellsSize
         _chk(lib().omg_eos_compute_spec_vol_disp(self.h, _level_dev(conserv_temp, n, self.K, keep),
                                                  _level_dev(abs_salinity, n, self.K, keep),
-                                                 _level_dev(pressure, n, self.K, keep), int(kdisp),
-                                                 C.c_double(p_scale), _sh(stream)))
+                                                 _level_dev(pressure, n, self.K, keep), kdisp, p_scale, _sh(stream)))
         if keep:
             device_synchronize()
 
@@ -1016,8 +1006,7 @@ class VertCoord(_Handle, _NamedArrays):
         d = decomp if decomp is not None else getattr(mesh, "decomp", None)
         mn = None if min_level_cell is None else np.ascontiguousarray(min_level_cell, dtype=np.int32)
         mx = None if max_level_cell is None else np.ascontiguousarray(max_level_cell, dtype=np.int32)
-        self._create("omg_vcoord_create", mesh.h, d.h if d is not None else None, nvertlayers, C.c_double(rho0),
-                     movement_weight_type.encode(), _pi(mn), _pi(mx))
+        self._create("omg_vcoord_create", mesh.h, _sh(d), nvertlayers, rho0, movement_weight_type.encode(), _pi(mn), _pi(mx))
 
     def min_max_layer_edge(self, stream=None):
         _chk(lib().omg_vcoord_min_max_layer_edge(self.h, _sh(stream)))
@@ -1076,29 +1065,17 @@ class VertCoord(_Handle, _NamedArrays):
         return (rows[spec],)
 
     def get_real(self, name: str) -> float:
-        v = C.c_double()
-        _chk(lib().omg_vcoord_get_real(self.h, name.encode(), C.byref(v)))
-        return v.value
+        return _out(C.c_double, lib().omg_vcoord_get_real, self.h, name.encode())
 
 
 class VertMixConfig(C.Structure):
     """omg_vertmix_config (VerticalMixingCoeff.md section 4.1.1)"""
-    _fields_ = [("BackgroundViscosity", C.c_double), ("BackgroundDiffusivity", C.c_double),
-                ("EnableShearMix", C.c_int32), ("ShearNuZero", C.c_double), ("ShearAlpha", C.c_double),
-                ("ShearExponent", C.c_double), ("EnableConvectiveMix", C.c_int32),
-                ("ConvectiveDiffusivity", C.c_double), ("ConvectiveTriggerBVF", C.c_double)]
+    _fields_ = _mirror("omg_vertmix_config")
 
 
 def vertmix_config(**over) -> VertMixConfig:
     """The defaults (omg_vertmix_config_default) with the given fields replaced; an unknown field raises KeyError."""
-    c = VertMixConfig()
-    _chk(lib().omg_vertmix_config_default(C.byref(c)))
-    names = {f[0] for f in VertMixConfig._fields_}
-    for k, v in over.items():
-        if k not in names:
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return _config(VertMixConfig, "omg_vertmix_config_default", over)
 
 
 class VertMix(_Handle, _NamedArrays):
@@ -1112,7 +1089,7 @@ class VertMix(_Handle, _NamedArrays):
         self.mesh, self.vcoord = mesh, vcoord
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
         self.config = vertmix_config(**config)
-        self._create("omg_vertmix_create", mesh.h, vcoord.h if vcoord is not None else None, C.byref(self.config))
+        self._create("omg_vertmix_create", mesh.h, _sh(vcoord), C.byref(self.config))
 
     def compute_bvf(self, eos: Eos, stream=None):
         _chk(lib().omg_vertmix_compute_bvf(self.h, eos.h, _sh(stream)))
@@ -1134,10 +1111,10 @@ class VertMix(_Handle, _NamedArrays):
         h = _level_dev(layer_thickness, n, self.K, keep)
         p, buf = _stage_levels(tracers, (int(ntracers), n), self.K)
         if surface_flux is None:
-            _chk(lib().omg_vertmix_apply_tracers(self.h, h, p, int(ntracers), C.c_double(dt), _sh(stream)))
+            _chk(lib().omg_vertmix_apply_tracers(self.h, h, p, ntracers, dt, _sh(stream)))
         else:
             f = _flat_dev(surface_flux, (int(ntracers), n), keep)
-            _chk(lib().omg_vertmix_apply_tracers_forced(self.h, h, p, int(ntracers), C.c_double(dt), f, _sh(stream)))
+            _chk(lib().omg_vertmix_apply_tracers_forced(self.h, h, p, ntracers, dt, f, _sh(stream)))
             if keep:
                 device_synchronize()
         return _read_back(buf, self.K, stream)
@@ -1151,14 +1128,13 @@ class VertMix(_Handle, _NamedArrays):
         h = _level_dev(layer_thickness, self.mesh.NCellsSize, self.K, keep)
         p, buf = _stage_levels(normal_velocity, (self.mesh.NEdgesSize,), self.K)
         if boundary is None and stress is None and ut is None:
-            _chk(lib().omg_vertmix_apply_velocity(self.h, h, p, C.c_double(dt), _sh(stream)))
+            _chk(lib().omg_vertmix_apply_velocity(self.h, h, p, dt, _sh(stream)))
         else:
             cd, ra = boundary if boundary is not None else (0.0, 0.0)
             ne = self.mesh.NEdgesSize
             t = None if stress is None else _flat_dev(stress, (ne,), keep)
             v = None if ut is None else _level_dev(ut, ne, self.K, keep)
-            _chk(lib().omg_vertmix_apply_velocity_forced(self.h, h, p, C.c_double(dt), C.c_double(cd), C.c_double(ra),
-                                                         t, v, _sh(stream)))
+            _chk(lib().omg_vertmix_apply_velocity_forced(self.h, h, p, dt, cd, ra, t, v, _sh(stream)))
             if keep:
                 device_synchronize()
         return _read_back(buf, self.K, stream)
@@ -1178,36 +1154,32 @@ class VertMixStep(_Handle, _NamedArrays):
                  ntracers: int):
         self.mesh, self.vert_mix, self.vcoord, self.eos, self.NT = mesh, vert_mix, vcoord, eos, int(ntracers)
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        self._create("omg_vertmix_step_create", mesh.h, vert_mix.h if vert_mix is not None else None,
-                     vcoord.h if vcoord is not None else None, eos.h if eos is not None else None, int(ntracers))
+        self._create("omg_vertmix_step_create", mesh.h, _sh(vert_mix), _sh(vcoord), _sh(eos), ntracers)
 
     def set_boundary(self, bottom_drag_coeff: float = 0.0, rayleigh_drag_coeff: float = 0.0,
                      use_wind_stress: bool = False):
-        _chk(lib().omg_vertmix_step_set_boundary(self.h, C.c_double(bottom_drag_coeff), C.c_double(rayleigh_drag_coeff),
-                                                 int(use_wind_stress)))
+        _chk(lib().omg_vertmix_step_set_boundary(self.h, bottom_drag_coeff, rayleigh_drag_coeff, use_wind_stress))
 
     def attach_redi(self, redi: "Redi | None"):
         """VertMixStep::attachRedi: apply adds `redi`'s VertDiffusivity (from the slopes it last computed) to the
         VertMix's VertDiff before the tracer solve; None detaches."""
-        _chk(lib().omg_vertmixstep_attach_redi(self.h, redi.h if redi is not None else None))
+        _chk(lib().omg_vertmixstep_attach_redi(self.h, _sh(redi)))
         self._redi = redi  # the library keeps a pointer to it
 
     def attach_kpp(self, kpp: "Kpp | None"):
         """VertMixStep::attachKpp: apply runs `kpp`'s compute after the coefficients and its non-local redistribution
         of SurfaceTracerFlux before the tracer solve; None detaches."""
-        _chk(lib().omg_vmix_step_attach_kpp(self.h, kpp.h if kpp is not None else None))
+        _chk(lib().omg_vmix_step_attach_kpp(self.h, _sh(kpp)))
         self._kpp = kpp  # the library keeps a pointer to it
 
     def apply(self, layer_thickness: int, normal_velocity: int, tracers: int, dt: float, stream=None):
         """On device addresses: thickness [NCellsSize][pitch]; velocity [NEdgesSize][pitch] and tracers
         [NT][NCellsSize][pitch] are mixed in place, asynchronously on `stream`."""
-        _chk(lib().omg_vertmix_step_apply(self.h, C.c_void_p(int(layer_thickness)), C.c_void_p(int(normal_velocity)),
-                                          C.c_void_p(int(tracers)), C.c_double(dt), _sh(stream)))
+        _chk(lib().omg_vertmix_step_apply(self.h, int(layer_thickness), int(normal_velocity), int(tracers), dt, _sh(stream)))
 
     def apply_state(self, state: OceanState, tracers: Tracers, dt: float, time_level: int = 0,
                     tracer_time_level: int = 0, stream=None):
-        _chk(lib().omg_vertmix_step_apply_state(self.h, state.h, int(time_level), tracers.h, int(tracer_time_level),
-                                                C.c_double(dt), _sh(stream)))
+        _chk(lib().omg_vertmix_step_apply_state(self.h, state.h, time_level, tracers.h, tracer_time_level, dt, _sh(stream)))
 
     def _shape(self, name):
         m = self.mesh
@@ -1217,20 +1189,12 @@ class VertMixStep(_Handle, _NamedArrays):
 
 class KppConfig(C.Structure):
     """omg_kpp_config (omega_amd/csrc/Kpp.h)"""
-    _fields_ = [("VonKarman", C.c_double), ("CritBulkRichardson", C.c_double), ("SurfaceLayerFraction", C.c_double),
-                ("Cv", C.c_double), ("EntrainmentRatio", C.c_double), ("CStar", C.c_double)]
+    _fields_ = _mirror("omg_kpp_config")
 
 
 def kpp_config(**over) -> KppConfig:
     """The defaults (omg_kpp_config_default) with the given fields replaced; an unknown field raises KeyError."""
-    c = KppConfig()
-    _chk(lib().omg_kpp_config_default(C.byref(c)))
-    names = {f[0] for f in KppConfig._fields_}
-    for k, v in over.items():
-        if k not in names:
-            raise KeyError(k)
-        setattr(c, k, v)
-    return c
+    return _config(KppConfig, "omg_kpp_config_default", over)
 
 
 class Kpp(_Handle, _NamedArrays):
@@ -1246,8 +1210,7 @@ class Kpp(_Handle, _NamedArrays):
         self.mesh, self.vcoord, self.vert_mix = mesh, vcoord, vert_mix
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
         self.config = kpp_config(**config)
-        self._create("omg_kpp_create", mesh.h, vcoord.h if vcoord is not None else None,
-                     vert_mix.h if vert_mix is not None else None, C.byref(self.config))
+        self._create("omg_kpp_create", mesh.h, _sh(vcoord), _sh(vert_mix), C.byref(self.config))
 
     def constants(self) -> tuple:
         """(VtCoef, NonLocalCoeff) as formed at creation"""
@@ -1292,16 +1255,14 @@ class Kpp(_Handle, _NamedArrays):
         h = _level_dev(layer_thickness, n, self.K, keep)
         p, buf = _stage_levels(tracers, (int(ntracers), n), self.K)
         f = None if surface_flux is None else _flat_dev(surface_flux, (int(ntracers), n), keep)
-        _chk(lib().omg_kpp_apply_non_local(self.h, h, p, int(ntracers), C.c_double(dt), f, _sh(stream)))
+        _chk(lib().omg_kpp_apply_non_local(self.h, h, p, ntracers, dt, f, _sh(stream)))
         if keep:
             device_synchronize()
         return _read_back(buf, self.K, stream)
 
     def launch_count(self) -> int:
         """kernel launches compute and apply_non_local have issued on this object so far"""
-        n = C.c_int64(0)
-        _chk(lib().omg_kpp_launch_count(self.h, C.byref(n)))
-        return n.value
+        return _out(C.c_int64, lib().omg_kpp_launch_count, self.h)
 
     def _shape(self, name):
         m = self.mesh
@@ -1319,14 +1280,13 @@ class _ColumnPass:
     def _create_on(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", *args):
         self.mesh, self.vcoord, self.eos = mesh, vcoord, eos
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        self._create(self._arrays + "_create", mesh.h, vcoord.h if vcoord is not None else None,
-                     eos.h if eos is not None else None, *args)
+        self._create(self._arrays + "_create", mesh.h, _sh(vcoord), _sh(eos), *args)
 
     def _update_column(self, layer_thickness, tracers, ntracers: int, stream):
         keep, n = [], self.mesh.NCellsSize
         h = _level_dev(layer_thickness, n, self.K, keep)
         t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
-        _chk(getattr(lib(), self._arrays + "_update_column")(self.h, h, t, int(ntracers), _sh(stream)))
+        _chk(getattr(lib(), self._arrays + "_update_column")(self.h, h, t, ntracers, _sh(stream)))
         if keep:
             device_synchronize()
 
@@ -1386,19 +1346,17 @@ class VertAdv(_Handle, _NamedArrays):
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", tracer_flux_order: int = 2):
         self.mesh, self.vcoord, self.order = mesh, vcoord, tracer_flux_order
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        self._create("omg_vertadv_create", mesh.h, vcoord.h if vcoord is not None else None, int(tracer_flux_order))
+        self._create("omg_vertadv_create", mesh.h, _sh(vcoord), tracer_flux_order)
 
     @staticmethod
     def max_layers() -> int:
-        n = C.c_int()
-        _chk(lib().omg_vertadv_max_layers(C.byref(n)))
-        return n.value
+        return _out(C.c_int, lib().omg_vertadv_max_layers)
 
     def compute_transport(self, thickness_tend, add_thickness: bool = False, stream=None):
         """VerticalTransport from the horizontal thickness tendency; add_thickness: also the thickness update, in the
         same launch (computeAndAddThickness)"""
         p, buf = _stage_levels(thickness_tend, (self.mesh.NCellsSize,), self.K)
-        _chk(lib().omg_vertadv_compute_transport(self.h, p, int(bool(add_thickness)), _sh(stream)))
+        _chk(lib().omg_vertadv_compute_transport(self.h, p, bool(add_thickness), _sh(stream)))
         return _read_back(buf, self.K, stream)
 
     def add_thickness(self, thickness_tend, stream=None):
@@ -1411,7 +1369,7 @@ class VertAdv(_Handle, _NamedArrays):
         h = _level_dev(layer_thickness, n, self.K, keep)
         t = _stage_levels(tracers, (int(ntracers), n), self.K, keep)[0]
         p, buf = _stage_levels(tracer_tend, (int(ntracers), n), self.K)
-        _chk(lib().omg_vertadv_add_tracers(self.h, p, h, t, int(ntracers), _sh(stream)))
+        _chk(lib().omg_vertadv_add_tracers(self.h, p, h, t, ntracers, _sh(stream)))
         if keep:
             device_synchronize()
         return _read_back(buf, self.K, stream)
@@ -1420,7 +1378,7 @@ class VertAdv(_Handle, _NamedArrays):
         """VertAdv::TracerTermEnable (default on): off, a Tendencies this object is attached to leaves its tracer term
         out -- for a MonotoneAdv that limits the vertical flux itself (MonotoneAdv.attach_vert_adv).  add_tracers
         called directly does not look at it."""
-        _chk(lib().omg_vertadv_set_tracer_term(self.h, int(bool(on))))
+        _chk(lib().omg_vertadv_set_tracer_term(self.h, bool(on)))
 
     def add_velocity(self, velocity_tend, layer_thickness, normal_velocity, stream=None):
         keep = []
@@ -1443,8 +1401,8 @@ def monotone_adv_high_order_tables(mesh: "HorzMesh", order: int, coef_3rd_order:
     n, me = mesh.NCellsSize, mesh.MaxEdges
     out = {"FitCell": np.zeros(n), "HessWeight": np.zeros((n, me, 3)), "EdgeDirOwn": np.zeros((n, me, 3)),
            "EdgeDirAcross": np.zeros((n, me, 3))}
-    _chk(lib().omg_monoadv_high_order_tables(mesh.h, int(order), C.c_double(coef_3rd_order), C.c_double(sphere_radius),
-                                             C.c_double(x_period), C.c_double(y_period), *(_pd(a) for a in out.values())))
+    _chk(lib().omg_monoadv_high_order_tables(mesh.h, order, coef_3rd_order, sphere_radius, x_period, y_period,
+                                             *(_pd(a) for a in out.values())))
     return out
 
 
@@ -1459,13 +1417,12 @@ class MonotoneAdv(_Handle, _NamedArrays):
     def __init__(self, mesh: HorzMesh, nvertlayers: int, max_tracers: int, flux_thickness_upwind: bool = False):
         self.mesh, self.K, self.max_tracers = mesh, int(nvertlayers), int(max_tracers)
         self.flux_thickness_upwind = bool(flux_thickness_upwind)
-        self._create("omg_monoadv_create", mesh.h if mesh is not None else None, int(nvertlayers), int(max_tracers),
-                     int(bool(flux_thickness_upwind)))
+        self._create("omg_monoadv_create", _sh(mesh), nvertlayers, max_tracers, self.flux_thickness_upwind)
 
     def attach_vert_adv(self, vert_adv: "VertAdv | None"):
         """MonotoneAdv::attachVertAdv: while attached add_tracers limits the vertical flux of `vert_adv`'s
         VerticalTransport (as it stands) together with the horizontal ones; None detaches."""
-        _chk(lib().omg_monoadv_attach_vert_adv(self.h, vert_adv.h if vert_adv is not None else None))
+        _chk(lib().omg_monoadv_attach_vert_adv(self.h, _sh(vert_adv)))
         self.vert_adv = vert_adv  # (the C++ object keeps the pointer)
 
     def add_tracers(self, tracer_tend, h_old, h_new, normal_velocity, tracers, ntracers: int, dt: float, stream=None):
@@ -1475,7 +1432,7 @@ class MonotoneAdv(_Handle, _NamedArrays):
         u = _level_dev(normal_velocity, self.mesh.NEdgesSize, self.K, keep)
         t = _stage_levels(tracers, (nt, n), self.K, keep)[0]
         p, buf = _stage_levels(tracer_tend, (nt, n), self.K)
-        _chk(lib().omg_monoadv_add_tracers(self.h, p, ho, hn, u, t, int(ntracers), C.c_double(dt), _sh(stream)))
+        _chk(lib().omg_monoadv_add_tracers(self.h, p, ho, hn, u, t, ntracers, dt, _sh(stream)))
         if keep:
             device_synchronize()
         return _read_back(buf, self.K, stream)
@@ -1487,15 +1444,12 @@ class MonotoneAdv(_Handle, _NamedArrays):
         tables from the mesh's cell positions -- on a sphere of `sphere_radius` (0: planar, with the periods of a
         periodic mesh) -- and add the named arrays "Hess" [max_tracers][3][NCellsSize][K], "HessWeight", "EdgeDirOwn",
         "EdgeDirAcross" [NCellsSize][MaxEdges][3] and "FitCell" [NCellsSize]; add_tracers then makes three launches."""
-        _chk(lib().omg_monoadv_set_horz_order(self.h, int(order), C.c_double(coef_3rd_order), C.c_double(sphere_radius),
-                                              C.c_double(x_period), C.c_double(y_period)))
+        _chk(lib().omg_monoadv_set_horz_order(self.h, order, coef_3rd_order, sphere_radius, x_period, y_period))
         self.horz_order = int(order)
 
     def launch_count(self) -> int:
         """kernel launches add_tracers has issued on this object so far"""
-        n = C.c_int64(0)
-        _chk(lib().omg_monoadv_launch_count(self.h, C.byref(n)))
-        return n.value
+        return _out(C.c_int64, lib().omg_monoadv_launch_count, self.h)
 
     def _shape(self, name):
         if name == "Hess":
@@ -1522,13 +1476,11 @@ class BarotropicMode(_Handle, _NamedArrays):
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", gravity: float = 9.80616):
         self.mesh, self.vcoord, self.gravity = mesh, vcoord, float(gravity)
         self.K = vcoord.K if vcoord is not None else mesh.NVertLayers
-        self._create("omg_btr_create", mesh.h, vcoord.h if vcoord is not None else None, C.c_double(gravity))
+        self._create("omg_btr_create", mesh.h, _sh(vcoord), gravity)
 
     @staticmethod
     def max_layers() -> int:
-        n = C.c_int()
-        _chk(lib().omg_btr_max_layers(C.byref(n)))
-        return n.value
+        return _out(C.c_int, lib().omg_btr_max_layers)
 
     def _edge_call(self, symbol, layer_thickness, edge_field, *args, stream=None):
         keep = []
@@ -1540,7 +1492,7 @@ class BarotropicMode(_Handle, _NamedArrays):
 
     def split_velocity(self, layer_thickness, normal_velocity, with_ssh: bool = False, stream=None):
         """BtrThickEdge, BtrVelocity and BclVelocity; with_ssh: also compute_ssh, in the same launch"""
-        self._edge_call("omg_btr_split_velocity", layer_thickness, normal_velocity, int(bool(with_ssh)), stream=stream)
+        self._edge_call("omg_btr_split_velocity", layer_thickness, normal_velocity, bool(with_ssh), stream=stream)
 
     def compute_forcing(self, layer_thickness, velocity_tend, stream=None):
         self._edge_call("omg_btr_compute_forcing", layer_thickness, velocity_tend, stream=stream)
@@ -1560,7 +1512,7 @@ class BarotropicMode(_Handle, _NamedArrays):
         return _read_back(buf, self.K, stream)
 
     def subcycle(self, nsub: int, dt_btr: float, stream=None):
-        _chk(lib().omg_btr_subcycle(self.h, int(nsub), C.c_double(dt_btr), _sh(stream)))
+        _chk(lib().omg_btr_subcycle(self.h, nsub, dt_btr, _sh(stream)))
 
     def compute_residual_forcing(self, layer_thickness, velocity_tend, stream=None):
         """BtrTendMean (the vertical mean of velocity_tend) and BtrForcing = BtrTendMean less the sub-step's bracket at
@@ -1570,13 +1522,12 @@ class BarotropicMode(_Handle, _NamedArrays):
     def transport_velocity(self, velocity_old, velocity_out, stream=None):
         """velocity_out = BclVelocity + BtrFluxMean/BtrThickEdge on each edge's level range, velocity_old elsewhere;
         device addresses of [NEdgesSize][level_pitch(K)] doubles"""
-        _chk(lib().omg_btr_transport_velocity(self.h, C.c_void_p(velocity_old), C.c_void_p(velocity_out), _sh(stream)))
+        _chk(lib().omg_btr_transport_velocity(self.h, velocity_old, velocity_out, _sh(stream)))
 
     def advance_velocity(self, velocity_old, velocity_tend, dt: float, velocity_out, stream=None):
         """velocity_out = (BclVelocity + dt*(velocity_tend - BtrTendMean)) + BtrVelocity on each edge's level range,
         velocity_old + dt*velocity_tend elsewhere; device addresses, velocity_out may be velocity_old"""
-        _chk(lib().omg_btr_advance_velocity(self.h, C.c_void_p(velocity_old), C.c_void_p(velocity_tend), C.c_double(dt),
-                                            C.c_void_p(velocity_out), _sh(stream)))
+        _chk(lib().omg_btr_advance_velocity(self.h, velocity_old, velocity_tend, dt, velocity_out, _sh(stream)))
 
     def _shape(self, name):
         s = BTR_ARRAYS.get(name, "E")  # (an unknown name: the library says so)
@@ -1599,7 +1550,7 @@ class GentMcWilliams(_Handle, _NamedArrays, _ColumnPass):
 
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", kappa: float = 600.0,
                  grav_wave_speed: float = 0.3):
-        self._create_on(mesh, vcoord, eos, C.c_double(kappa), C.c_double(grav_wave_speed))
+        self._create_on(mesh, vcoord, eos, kappa, grav_wave_speed)
 
     def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
         """The fused column pass with the displaced volume (kdisp = 1) from raw arrays: thickness [NCellsSize][K],
@@ -1646,7 +1597,7 @@ class Redi(_Handle, _NamedArrays, _ColumnPass):
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", eos: "Eos | None", max_tracers: int,
                  kappa: float = 600.0, slope_max: float = 0.01, n2_floor: float = 1.0e-10):
         self.max_tracers = int(max_tracers)
-        self._create_on(mesh, vcoord, eos, int(max_tracers), C.c_double(kappa), C.c_double(slope_max), C.c_double(n2_floor))
+        self._create_on(mesh, vcoord, eos, max_tracers, kappa, slope_max, n2_floor)
 
     def update_column(self, layer_thickness, tracers, ntracers: int, stream=None):
         """The fused column pass with the displaced volume (kdisp = 1) from raw arrays, as
@@ -1674,7 +1625,7 @@ class Redi(_Handle, _NamedArrays, _ColumnPass):
         t = _stage_levels(tracers, (nt, n), self.K, keep)[0]
         z = None if z_mid is None else _level_dev(z_mid, n, self.K, keep)
         p, buf = _stage_levels(tracer_tend, (nt, n), self.K)
-        _chk(lib().omg_redi_add_tracer_tend(self.h, p, h, t, int(ntracers), z, _sh(stream)))
+        _chk(lib().omg_redi_add_tracer_tend(self.h, p, h, t, ntracers, z, _sh(stream)))
         if keep:
             device_synchronize()
         return _read_back(buf, self.K, stream)
@@ -1687,9 +1638,7 @@ class Redi(_Handle, _NamedArrays, _ColumnPass):
 
     def launch_count(self) -> int:
         """kernel launches the three compute calls have issued on this object so far"""
-        n = C.c_int64(0)
-        _chk(lib().omg_redi_launch_count(self.h, C.byref(n)))
-        return n.value
+        return _out(C.c_int64, lib().omg_redi_launch_count, self.h)
 
     def _shape(self, name):
         s = REDI_ARRAYS.get(name, "C")  # (an unknown name: the library says so)
@@ -1708,14 +1657,11 @@ class VertRemap(_Handle, _NamedArrays):
     def __init__(self, mesh: HorzMesh, vcoord: "VertCoord | None", max_tracers: int, order: int = 3):
         self.mesh, self.vcoord, self.order, self.max_tracers = mesh, vcoord, int(order), int(max_tracers)
         self.K = vcoord.K if vcoord is not None else (mesh.NVertLayers if mesh is not None else 0)
-        self._create("omg_vremap_create", mesh.h if mesh is not None else None, vcoord.h if vcoord is not None else None,
-                     int(order), int(max_tracers))
+        self._create("omg_vremap_create", _sh(mesh), _sh(vcoord), order, max_tracers)
 
     @staticmethod
     def max_layers() -> int:
-        n = C.c_int()
-        _chk(lib().omg_vremap_max_layers(C.byref(n)))
-        return n.value
+        return _out(C.c_int, lib().omg_vremap_max_layers)
 
     def compute_target(self, layer_thickness, stream=None):
         keep = []
@@ -1728,7 +1674,7 @@ class VertRemap(_Handle, _NamedArrays):
         keep, n, nt = [], self.mesh.NCellsSize, max(int(ntracers), 0)
         h = _level_dev(layer_thickness, n, self.K, keep)
         p, buf = _stage_levels(tracers, (nt, n), self.K)
-        _chk(lib().omg_vremap_remap_tracers(self.h, h, p, int(ntracers), _sh(stream)))
+        _chk(lib().omg_vremap_remap_tracers(self.h, h, p, ntracers, _sh(stream)))
         if keep:
             device_synchronize()
         return _read_back(buf, self.K, stream)
@@ -1754,14 +1700,12 @@ class VertRemap(_Handle, _NamedArrays):
         ph, bh = _stage_levels(layer_thickness, (n,), self.K)
         pu, bu = _stage_levels(normal_velocity, (self.mesh.NEdgesSize,), self.K)
         pt, bt = (None, None) if tracers is None else _stage_levels(tracers, (nt, n), self.K)
-        _chk(lib().omg_vremap_remap(self.h, ph, pu, pt, int(ntracers), _sh(stream)))
+        _chk(lib().omg_vremap_remap(self.h, ph, pu, pt, ntracers, _sh(stream)))
         return tuple(_read_back(b, self.K, stream) for b in (bh, bu, bt))
 
     def launch_count(self) -> int:
         """kernel launches the five calls have issued on this object so far"""
-        n = C.c_int64(0)
-        _chk(lib().omg_vremap_launch_count(self.h, C.byref(n)))
-        return n.value
+        return _out(C.c_int64, lib().omg_vremap_launch_count, self.h)
 
     def _shape(self, name):
         return (self.mesh.NCellsSize, self.K)
@@ -1771,8 +1715,8 @@ def fused_limit(ncells_size: int, nedges_size: int, nvertices_size: int, max_edg
     """omg_tend_fused_limit: (True, "") if the fused RHS covers arrays of these row counts (sentinel row included), else
     (False, reason).  Sizes only: needs neither a mesh nor a device."""
     ok, why = C.c_int(), C.create_string_buffer(1024)
-    _chk(lib().omg_tend_fused_limit(C.c_int64(ncells_size), C.c_int64(nedges_size), C.c_int64(nvertices_size), int(max_edges),
-                                    int(nvertlayers), C.byref(ok), why, C.c_size_t(1024)))
+    _chk(lib().omg_tend_fused_limit(ncells_size, nedges_size, nvertices_size, max_edges, nvertlayers, C.byref(ok), why,
+                                    len(why)))
     return bool(ok.value), why.value.decode()
 
 
@@ -1789,22 +1733,22 @@ class Tendencies(_Handle):
                      mesh.h, nvertlayers, ntracers, C.byref(self.config))
 
     def set_fused(self, on: bool):
-        _chk(lib().omg_tend_set_fused(self.h, int(on)))
+        _chk(lib().omg_tend_set_fused(self.h, on))
 
     def attach_pressure_grad(self, pgrad: "PressureGrad | None"):
         """Tendencies::attachPressureGrad: the layered pressure gradient as an opt-in velocity term (None detaches);
         raises while SSHTendencyEnable is on."""
-        _chk(lib().omg_tend_attach_pressure_grad(self.h, pgrad.h if pgrad is not None else None))
+        _chk(lib().omg_tend_attach_pressure_grad(self.h, _sh(pgrad)))
         self._pgrad = pgrad  # the library keeps a pointer to it
 
     def attach_vert_adv(self, vert_adv: "VertAdv | None"):
         """Tendencies::attachVertAdv: vertical transport and advection as opt-in terms of all three tendencies (None
         detaches)."""
-        _chk(lib().omg_tend_attach_vert_adv(self.h, vert_adv.h if vert_adv is not None else None))
+        _chk(lib().omg_tend_attach_vert_adv(self.h, _sh(vert_adv)))
         self._vert_adv = vert_adv  # the library keeps a pointer to it
 
     def set_graphs(self, on: bool):
-        _chk(lib().omg_tend_set_graphs(self.h, int(on)))
+        _chk(lib().omg_tend_set_graphs(self.h, on))
 
     def graph_stats(self):
         c, r = C.c_int64(), C.c_int64()
@@ -1838,8 +1782,7 @@ class Tendencies(_Handle):
         update_tracers_by_tend leave there; with keep_tendencies the tendency arrays are the transport call's, without
         it their contents are unspecified."""
         _chk(lib().omg_tend_compute_transport_update(self.h, state.h, aux.h, tracers.h, tracer_tl, thick_tl, vel_tl,
-                                                     next_thick_tl, next_tracer_tl, C.c_double(coeff),
-                                                     int(bool(keep_tendencies)), _sh(stream)))
+                                                     next_thick_tl, next_tracer_tl, coeff, bool(keep_tendencies), _sh(stream)))
 
     def compute_momentum_tendencies(self, state, aux, tracers, tracer_tl=0, thick_tl=0, vel_tl=0, stream=None):
         """Tendencies::computeMomentumTendencies: NormalVelocityTend and LayerThicknessTend as compute_all_tendencies
@@ -1859,8 +1802,7 @@ class Tendencies(_Handle):
 
     def use_manufactured_solution(self, mesh, wavelength_x: float, wavelength_y: float, amplitude: float):
         """Tendencies config UseCustomTendency + ManufacturedSolutionTendency (CustomTendencyTerms.cpp)."""
-        _chk(lib().omg_tend_use_manufactured_solution(self.h, mesh.h, C.c_double(wavelength_x), C.c_double(wavelength_y),
-                                                      C.c_double(amplitude)))
+        _chk(lib().omg_tend_use_manufactured_solution(self.h, mesh.h, wavelength_x, wavelength_y, amplitude))
 
     def set_custom_tendency(self, which: int, fn):
         """Tendencies::CustomThicknessTend (which 0) / CustomVelocityTend (which 1) as a Python callable
@@ -1868,7 +1810,7 @@ class Tendencies(_Handle):
         if not hasattr(self, "_custom"):
             self._custom = {}
         if fn is None:
-            _chk(lib().omg_tend_set_custom_tendency(self.h, which, C.cast(None, CUSTOM_TEND_FN), None))
+            _chk(lib().omg_tend_set_custom_tendency(self.h, which, None, None))
             self._custom.pop(which, None)
             return
 
@@ -1888,35 +1830,33 @@ class Tendencies(_Handle):
 
     def set_time(self, seconds: float):
         """model time (s since the reference time) the custom tendencies see in direct compute_* calls"""
-        _chk(lib().omg_tend_set_time(self.h, C.c_double(seconds)))
+        _chk(lib().omg_tend_set_time(self.h, seconds))
 
     def kernel_timing(self, on: bool):
-        _chk(lib().omg_tend_kernel_timing(self.h, int(on)))
+        _chk(lib().omg_tend_kernel_timing(self.h, on))
 
     def collect_kernel_times(self):
         """[(kernel name, mean ms)] over the RHS evaluations recorded since kernel_timing(True)."""
         ms = (C.c_double * 16)()
         nk, ns = C.c_int(), C.c_int()
         _chk(lib().omg_tend_collect_kernel_times(self.h, ms, C.byref(nk), C.byref(ns)))
-        L = lib()
-        L.omg_tend_kernel_name.restype = C.c_char_p
         if ns.value == 0:
             return []
-        out = [(L.omg_tend_kernel_name(i).decode(), ms[i] / ns.value) for i in range(nk.value)]
+        out = [(lib().omg_tend_kernel_name(i).decode(), ms[i] / ns.value) for i in range(nk.value)]
         return [(k, v) for k, v in out if k]
 
     def device_ptr(self, which: int):
         """omg_tend_device_ptr: (device address, number of values incl. the row padding) of LayerThicknessTend (0),
         NormalVelocityTend (1), TracerTend (2)"""
-        p, n = C.POINTER(C.c_double)(), C.c_size_t()
+        p, n = C.c_void_p(), C.c_size_t()
         _chk(lib().omg_tend_device_ptr(self.h, which, C.byref(p), C.byref(n)))
-        return C.cast(p, C.c_void_p).value, n.value
+        return p.value, n.value
 
     def get(self, which: int) -> np.ndarray:
         m = self.mesh
         shape = [(m.NCellsSize, self.K), (m.NEdgesSize, self.K), (max(self.NT, 1), m.NCellsSize, self.K)][which]
         out = np.zeros(shape)
-        _chk(lib().omg_tend_copy_to_host(self.h, which, _pd(out), C.c_size_t(out.size)))
+        _chk(lib().omg_tend_copy_to_host(self.h, which, _pd(out), out.size))
         return out
 
 
@@ -1926,26 +1866,25 @@ class TimeStepper(_Handle):
     def __init__(self, kind: str, dt: float, tend: Tendencies, aux: AuxiliaryState, mesh: HorzMesh,
                  halo: Halo | None, tracers: Tracers):
         self.refs = (tend, aux, mesh, halo, tracers)
-        self._create("omg_stepper_create", kind.encode(), C.c_double(dt), tend.h, aux.h, mesh.h, halo.h if halo else None,
-                     tracers.h)
+        self._create("omg_stepper_create", kind.encode(), dt, tend.h, aux.h, mesh.h, halo.h if halo else None, tracers.h)
 
     def attach_vert_mix(self, vert_mix_step: "VertMixStep | None"):
         """TimeStepper::attachVertMix: every do_step runs the mixing sequence on the new time level before the time
         levels rotate (None detaches); raises for another mesh, layer or tracer count and for a halo with neighbours."""
-        _chk(lib().omg_stepper_attach_vert_mix(self.h, vert_mix_step.h if vert_mix_step is not None else None))
+        _chk(lib().omg_stepper_attach_vert_mix(self.h, _sh(vert_mix_step)))
         self._vert_mix_step = vert_mix_step  # the library keeps a pointer to it
 
     def attach_barotropic(self, btr: "BarotropicMode", nsub: int):
         """SplitExplicitStepper::attachBarotropic: required before the first do_step of a "Split-Explicit" stepper;
         raises on any other kind, for another mesh or layer count, nsub < 1 and a halo with neighbours."""
-        _chk(lib().omg_stepper_attach_barotropic(self.h, btr.h if btr is not None else None, int(nsub)))
+        _chk(lib().omg_stepper_attach_barotropic(self.h, _sh(btr), nsub))
         self._barotropic = btr  # the library keeps a pointer to it
 
     def attach_monotone_adv(self, mono: "MonotoneAdv | None"):
         """SplitExplicitStepper::attachMonotoneAdv: the step's horizontal tracer advection through `mono` (None
         detaches); raises on any other kind, for another mesh or layer count, too few tracers, a flux-thickness option
         that differs from the AuxiliaryState's, and while the Tendencies' own TracerHorzAdvTendencyEnable is on."""
-        _chk(lib().omg_stepper_attach_monotone_adv(self.h, mono.h if mono is not None else None))
+        _chk(lib().omg_stepper_attach_monotone_adv(self.h, _sh(mono)))
         self._monotone_adv = mono  # the library keeps a pointer to it
 
     def attach_gent_mcwilliams(self, gm: "GentMcWilliams | None"):
@@ -1953,7 +1892,7 @@ class TimeStepper(_Handle):
         stratification to its transporting velocity (None detaches); raises on any other kind, for another mesh or layer
         count, fewer than 2 tracers, and, with a PressureGrad attached to the Tendencies, for a `gm` on another VertCoord
         or Eos than its (the caller keeps the forcing arrays of the two equal)."""
-        _chk(lib().omg_stepper_attach_gm(self.h, gm.h if gm is not None else None))
+        _chk(lib().omg_stepper_attach_gm(self.h, _sh(gm)))
         self._gent_mcwilliams = gm  # the library keeps a pointer to it
 
     def attach_redi(self, redi: "Redi | None"):
@@ -1961,43 +1900,41 @@ class TimeStepper(_Handle):
         isoneutral cross terms to the tracer tendency before the tracer update (None detaches); raises on any other
         kind, for another mesh or layer count, too few tracers, another VertCoord or Eos than an attached
         GentMcWilliams's or PressureGrad's, and unless a VertMixStep with this same `redi` attached is attached."""
-        _chk(lib().omg_stepper_attach_redi(self.h, redi.h if redi is not None else None))
+        _chk(lib().omg_stepper_attach_redi(self.h, _sh(redi)))
         self._redi = redi  # the library keeps a pointer to it
 
     def attach_vert_remap(self, vert_remap: "VertRemap | None"):
         """SplitExplicitStepper::attachVertRemap: every step remaps the new time level back onto the VertCoord's target
         grid (VertRemap.remap) between the velocity update and the vertical mixing (None detaches); raises on any other
         kind, for another mesh or layer count, too few tracers, and while a VertAdv is attached to the Tendencies."""
-        _chk(lib().omg_stepper_attach_vert_remap(self.h, vert_remap.h if vert_remap is not None else None))
+        _chk(lib().omg_stepper_attach_vert_remap(self.h, _sh(vert_remap)))
         self._vert_remap = vert_remap  # the library keeps a pointer to it
 
     def set_fused_transport(self, on: bool):
         """SplitExplicitStepper::UseFusedTransport (default on): the step's thickness and tracer tendencies through
         Tendencies.compute_transport_tendencies instead of the two group calls; raises on any other kind."""
-        _chk(lib().omg_stepper_set_fused_transport(self.h, int(on)))
+        _chk(lib().omg_stepper_set_fused_transport(self.h, on))
 
     def set_momentum_rhs(self, on: bool):
         """SplitExplicitStepper::UseMomentumRHS: the step's first evaluation through
         Tendencies.compute_momentum_tendencies instead of compute_all_tendencies; raises on any other kind."""
-        _chk(lib().omg_stepper_set_momentum_rhs(self.h, int(on)))
+        _chk(lib().omg_stepper_set_momentum_rhs(self.h, on))
 
     def set_folded_updates(self, on: bool):
         """SplitExplicitStepper::FoldUpdates: with the fused transport on, the transport tendencies and the thickness
         and tracer updates through Tendencies.compute_transport_tendencies_and_update (not with tracers and their
         hyperdiffusion term off: no faster there); raises on any other kind."""
-        _chk(lib().omg_stepper_set_folded_updates(self.h, int(on)))
+        _chk(lib().omg_stepper_set_folded_updates(self.h, on))
 
     def do_step(self, state: OceanState, stream=None):
         _chk(lib().omg_stepper_do_step(self.h, state.h, _sh(stream)))
 
     def set_start_time(self, seconds: float):
-        _chk(lib().omg_stepper_set_start_time(self.h, C.c_double(seconds)))
+        _chk(lib().omg_stepper_set_start_time(self.h, seconds))
 
     @property
     def time(self) -> float:
-        v = C.c_double()
-        _chk(lib().omg_stepper_get_time(self.h, C.byref(v)))
-        return v.value
+        return _out(C.c_double, lib().omg_stepper_get_time, self.h)
 
     def graph_stats(self):
         c, r = C.c_int64(), C.c_int64()
@@ -2005,29 +1942,25 @@ class TimeStepper(_Handle):
         return {"captures": c.value, "replays": r.value}
 
     def change_time_step(self, dt: float):
-        _chk(lib().omg_stepper_change_time_step(self.h, C.c_double(dt)))
+        _chk(lib().omg_stepper_change_time_step(self.h, dt))
 
     def set_option(self, name: str, value: bool):
         """RungeKutta4: "FuseStageUpdates" (default on), "StoreStageTendencies" (default off)."""
-        _chk(lib().omg_stepper_set_option(self.h, name.encode(), int(value)))
+        _chk(lib().omg_stepper_set_option(self.h, name.encode(), value))
 
 
 def update_by_tend(out_ptr: int, in_ptr: int, tend_ptr: int, coeff: float, n_rows: int, k: int, stream_handle=None):
     """out = in + coeff * tend on raw [n_rows][k] device arrays (TimeStepper::update*ByTend's kernel)."""
-    _chk(lib().omg_update_by_tend(C.c_void_p(out_ptr), C.c_void_p(in_ptr), C.c_void_p(tend_ptr), C.c_double(coeff),
-                                  n_rows, k, C.c_void_p(stream_handle) if stream_handle else None))
+    _chk(lib().omg_update_by_tend(out_ptr, in_ptr, tend_ptr, coeff, n_rows, k, stream_handle or None))
 
 
 def update_tracers_by_tend(next_ptr: int, cur_ptr: int, h_next_ptr: int, h_cur_ptr: int, tend_ptr: int, coeff: float,
                            n_tracers: int, n_rows: int, rows_size: int, k: int, stream_handle=None):
     """next = (cur*h_cur + coeff*tend)/h_next on raw device arrays of row length k, tracer planes rows_size rows apart
     (TimeStepper::updateTracersByTend's kernel)."""
-    _chk(lib().omg_update_tracers_by_tend(C.c_void_p(next_ptr), C.c_void_p(cur_ptr), C.c_void_p(h_next_ptr),
-                                          C.c_void_p(h_cur_ptr), C.c_void_p(tend_ptr), C.c_double(coeff), n_tracers,
-                                          n_rows, rows_size, k, C.c_void_p(stream_handle) if stream_handle else None))
+    _chk(lib().omg_update_tracers_by_tend(next_ptr, cur_ptr, h_next_ptr, h_cur_ptr, tend_ptr, coeff, n_tracers, n_rows,
+                                          rows_size, k, stream_handle or None))
 
 
 def coeff_seconds(mult: float, dt: float) -> float:
-    out = C.c_double()
-    _chk(lib().omg_stepper_coeff_seconds(C.c_double(mult), C.c_double(dt), C.byref(out)))
-    return out.value
+    return _out(C.c_double, lib().omg_stepper_coeff_seconds, mult, dt)

@@ -19,10 +19,7 @@ ARRAYS = ("BtrVelocity", "BtrThickEdge", "BtrForcing", "BtrFluxMean", "SSH", "Bc
 G = C.c_double(GRAVITY)
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared():

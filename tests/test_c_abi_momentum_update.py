@@ -27,10 +27,7 @@ SIGNATURES = {
 }
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared_with_their_signatures():

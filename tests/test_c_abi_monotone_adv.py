@@ -15,10 +15,7 @@ SYMBOLS = ("omg_monoadv_create", "omg_monoadv_destroy", "omg_monoadv_add_tracers
            "omg_monoadv_copy_to_host", "omg_monoadv_copy_to_device", "omg_stepper_attach_monotone_adv")
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared():

@@ -18,10 +18,7 @@ SYMBOLS = ("omg_monoadv_set_horz_order", "omg_monoadv_high_order_tables", "omg_m
 ARRAYS = (b"Hess", b"HessWeight", b"EdgeDirOwn", b"EdgeDirAcross", b"FitCell")
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def _d(x):

@@ -21,10 +21,7 @@ D = C.c_double
 PDBL = C.POINTER(C.c_double)
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared():

@@ -18,10 +18,7 @@ SYMBOLS = ("omg_btr_compute_residual_forcing", "omg_btr_transport_velocity", "om
            "omg_stepper_attach_barotropic")
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared():

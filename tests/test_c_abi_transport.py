@@ -14,10 +14,7 @@ from tests.split_explicit_fixtures import StepRig
 SYMBOLS = ("omg_tend_compute_transport", "omg_stepper_set_fused_transport")
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared():

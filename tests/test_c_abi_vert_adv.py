@@ -15,10 +15,7 @@ SYMBOLS = ("omg_vertadv_create", "omg_vertadv_destroy", "omg_vertadv_max_layers"
            "omg_vertadv_copy_to_host", "omg_vertadv_copy_to_device", "omg_tend_attach_vert_adv")
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared():

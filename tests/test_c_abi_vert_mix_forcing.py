@@ -13,10 +13,7 @@ SYMBOLS = ("omg_vertmix_apply_tracers_forced", "omg_vertmix_apply_velocity_force
            "omg_vertmix_step_device_ptr", "omg_stepper_attach_vert_mix")
 
 
-def _err():
-    L = oa.lib()
-    L.omg_last_error.restype = C.c_char_p
-    return L.omg_last_error().decode()
+_err = oa.last_error
 
 
 def test_symbols_are_exported_and_declared():
